@@ -8,7 +8,9 @@ samples, L = 256).  N > 1 is launched by torch.distributed.run, one rank per GPU
 categories (--shard class: one more category of the same shape per GPU, no gradient collective -- categories share nothing,
 train.py:58-64 -- weak scaling; --scaling strong --classes 16 is BASELINE.json configs[2] on a fixed global batch);
 --shard ray splits the rays of every category instead (one all-reduce of the flat gradient per step).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does what that line's headline needs (set-up, warm-up, the timed steps);
+--full adds the legs beside it: long_run, roofline, extra_legs, cpu_baseline (one GPU), strong_configs2 and the checks (N GPUs).
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds on the same inputs.
 """
 import argparse
 import json
@@ -141,6 +143,32 @@ def cpu_baseline(cfg_shape, seconds=12.0):
             "cpu_model": model, "physical_cores": phys, "logical_cpus": logical, "phase_ms": phase_ms,
             "sample": f"{len(times)} steps of the same {C}x{R}x{S} (L={L}) train step, median {med * 1e3:.1f} ms, "
                       f"torch fp32 oracle with {cores} threads (best of 8/16/32/64/default on 3-step medians)"}
+
+
+def step_outputs(tr):
+    """What the timed path (FusedCategoryTrainer.run) leaves its caller after its last step: the parameters that step wrote,
+    its loss terms (and those of every step of the last graph launch) and its per-ray renders."""
+    b = tr.bufs
+    return {"theta": tr.theta, "losses": tr.losses, "loss_history": tr.loss_history(), "depth": b["depth"], "rgb": b["rgb"],
+            "opacity": b["opa"]}
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32, at most DUMP_BYTES in all.  An array larger than its even
+    share is replaced by a fixed sample of its elements (seeded, in flat-index order), so that two builds still compare element
+    for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > cap:
+            keep = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
 
 
 def fp8_leg(args):
@@ -449,12 +477,18 @@ def main():
                     help="N > 1: categories in total of the strong_configs2 leg (BASELINE.json configs[2]'s stand-in count); 0 = skip")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="seconds the self-started N-rank child tree may take before its process group is killed")
-    ap.add_argument("--pre-warm-seconds", type=float, default=0.25,
-                    help="seconds of untimed steps in FRONT of the W warm-up steps (reported as pre_warm_steps): the graph captures "
-                         "before them are ~50 ms of host work with the GPU idle, and a 20-step region right behind that ran 3 us "
-                         "per step slower than the same region in a running job; 0 = none")
+    ap.add_argument("--pre-warm-steps", type=int, default=4500,
+                    help="untimed steps in FRONT of the W warm-up steps, rounded down to whole graph launches (reported as "
+                         "pre_warm_steps; ~0.25 s at configs[1]): the graph captures before them are ~50 ms of host work with the GPU "
+                         "idle, and a 20-step region right behind that ran 3 us per step slower than the same region in a running job. "
+                         "A count, not a time, so that the state the timed steps start from depends on the arguments alone; 0 = none")
     ap.add_argument("--host-wait", choices=("spin", "default"), default="spin",
                     help="how torch.cuda.synchronize() waits: spin = hipDeviceScheduleSpin (host_wait_spin), default = the runtime's")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: long_run, roofline, extra_legs and cpu_baseline on one GPU, "
+                         "strong_configs2, params_in_sync and the ranks check on N")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (step_outputs) as DIR/<name>.npy, float32")
     ap.add_argument("--launch-check", action="store_true",
                     help="bring the ranks up, all-reduce a one over the process group and print the world size the "
                          "backend reports -- no kernel runs (a check of the launcher, not a benchmark)")
@@ -561,81 +595,75 @@ def main():
     # the W warm-up steps come LAST, directly in front of the timed region: the captures above are ~50 ms of host work with the GPU
     # idle, and the first region after them ran 2 us per step slower than every later one (tools/exp/region200.py)
     pre_warm_steps = 0
-    if args.pre_warm_seconds > 0:      # the card back at its running-job clocks (the long_run leg below measures that state too)
-        # a step COUNT, the same on every rank (a class-sharded epoch end is a collective: ranks must not run different numbers of steps)
-        torch.cuda.synchronize()
-        t_pw = time.perf_counter()
-        tr.run(tr.unroll)
-        torch.cuda.synchronize()
-        est = (time.perf_counter() - t_pw) / tr.unroll
-        n_pw = max(int(args.pre_warm_seconds / max(est, 1e-6)) // tr.unroll, 1) * tr.unroll
-        if world > 1:
-            tp = torch.tensor([n_pw], device=dev, dtype=torch.int64)
-            torch.distributed.all_reduce(tp, op=torch.distributed.ReduceOp.MAX)
-            n_pw = int(tp.item())
-        for _ in range(n_pw // tr.unroll):     # one group at a time: 200 graph launches queued ahead of the GPU left the NEXT region's
+    if args.pre_warm_steps > 0:        # the card back at its running-job clocks (the long_run leg of --full measures that state too)
+        # the same count on every rank (a class-sharded epoch end is a collective: ranks must not run different numbers of steps)
+        groups = max(args.pre_warm_steps // tr.unroll, 1)
+        for _ in range(groups):                # one group at a time: 200 graph launches queued ahead of the GPU left the NEXT region's
             tr.run(tr.unroll)                  # launch slow (67-77 us per step over the 20 steps behind them, measured)
             torch.cuda.synchronize()
-        pre_warm_steps = n_pw + tr.unroll
+        pre_warm_steps = groups * tr.unroll
     tr.run(max(args.warmup, 4))
     dbg("warmup issued")
     dt = timed(args.steps)                      # EXACTLY --steps steps between barriers + synchronize, max over ranks
     dbg("timed region done")
     ms_per_step = dt / args.steps * 1e3
     rays_per_s = rays_per_step_global * args.steps / dt
-    # the same measurement over >= 2 s of steps (a 20-step region at 0.06 ms per step is 1.2 ms long -- shorter than any utilisation
-    # sampler's period): reported beside it, never instead of it
-    n_long = max(args.steps, int(args.long_seconds / max(dt / args.steps, 1e-6)) + 1)
-    if world > 1:
-        tl = torch.tensor([n_long], device=dev, dtype=torch.int64)
-        torch.distributed.all_reduce(tl, op=torch.distributed.ReduceOp.MAX)
-        n_long = int(tl.item())
-    dt_long = timed(n_long)
-    long_run = {"steps": n_long, "seconds": dt_long, "ms_per_step": dt_long / n_long * 1e3,
-                "value": rays_per_step_global * n_long / dt_long}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tr))
+    if args.full:
+        # the same measurement over >= 2 s of steps (a 20-step region at 0.06 ms per step is 1.2 ms long -- shorter than any utilisation
+        # sampler's period): reported beside it, never instead of it
+        n_long = max(args.steps, int(args.long_seconds / max(dt / args.steps, 1e-6)) + 1)
+        if world > 1:
+            tl = torch.tensor([n_long], device=dev, dtype=torch.int64)
+            torch.distributed.all_reduce(tl, op=torch.distributed.ReduceOp.MAX)
+            n_long = int(tl.item())
+        dt_long = timed(n_long)
+        long_run = {"steps": n_long, "seconds": dt_long, "ms_per_step": dt_long / n_long * 1e3,
+                    "value": rays_per_step_global * n_long / dt_long}
 
-    # ---- roofline leg: the dominant kernel (fused backward) timed with HIP events on its launch stream ----
-    bwd_name = "cnr_field_bwd_pipe"
-    names = [bwd_name, "cnr_field_train", "cnr_field_fwd", "cnr_field_fwd_render", "cnr_step_prologue", "cnr_render_loss",
-             "cnr_step_tail", "cnr_step_grad"]
-    tr.use_graph = False                                           # eager so that events bracket single launches
-    cnr_amd._C.enable_kernel_timing(names)
-    for _ in range(min(args.steps, 50)):
-        tr.step()
-    tms = cnr_amd._C.kernel_timings_ms()
-    tr.use_graph = not args.no_graph
-    avg = {k: (sum(v) / len(v) if v else 0.0) for k, v in tms.items()}
-    # the dominant call again, back to back (no host gaps between launches): this is the duration rocprofv3 reports
-    # for its kernels (field kernel + reduce_records), and the one the roofline entry uses
-    if tr._ft_blocks:        # the one-launch step body is the dominant call; the two-call form is not on this path
-        bwd_name = "cnr_field_train"
-        eager_bwd_ms = avg[bwd_name]
-        avg[bwd_name] = tr.time_field_train(250)
-    else:
-        eager_bwd_ms = avg[bwd_name]
-        avg[bwd_name] = tr.time_field_bwd(50)
-    dom = max((bwd_name, "cnr_field_fwd", "cnr_field_fwd_render"), key=lambda k: avg[k])
-    # the backward call = the field kernel(s) (pipe: one launch; split: texture + geometry launches) + reduce_records:
-    # its duration is the sum of those (rocprof lists them separately, profiles/).
-    # algorithmic FLOP of that call: fwd = 27 422 / sample; backward (recomputes the forward) or the one-launch forward +
-    # backward = fwd + dX + dW = 82 140
-    flop_per_sample = 82140 if dom == bwd_name else 27422
-    achieved = C * R * S * flop_per_sample / (avg[dom] * 1e-3) / 1e12 if avg[dom] > 0 else 0.0
-    # HBM bytes of that call from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 --pmc passes,
-    # gfx950 corrections per MI355X_MICROARCH.md): measured offline on this shape, kept in profiles/
-    traffic = None
-    for tname in ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if dom == bwd_name and (C, R, S) == (1, 2048, 64) and os.path.exists(tpath):
-            traffic = json.load(open(tpath)).get(bwd_name + "_call_hbm_bytes")
-            break
-    roofline = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_MFMA_F16_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / PEAK_MFMA_F16_TFLOPS, "traffic": traffic,
-                "variant": "pipe8 (4 chain + 4 weight-gradient waves per workgroup, two per SIMD)",
-                "kernel_ms": {k: round(v, 5) for k, v in avg.items()},
-                "kernel_ms_note": "HIP events on the launch stream; %s back to back, median of five batches of 50 launches (one launch at a time in the "
-                                  "eager step, gaps included: %.5f), the others one launch at a time" % (bwd_name, eager_bwd_ms),
-                "step_tflops": rays_per_step_global * S * FLOP_PER_SAMPLE_STEP / (dt / args.steps) / 1e12}
+        # ---- roofline leg: the dominant kernel (fused backward) timed with HIP events on its launch stream ----
+        bwd_name = "cnr_field_bwd_pipe"
+        names = [bwd_name, "cnr_field_train", "cnr_field_fwd", "cnr_field_fwd_render", "cnr_step_prologue", "cnr_render_loss",
+                 "cnr_step_tail", "cnr_step_grad"]
+        tr.use_graph = False                                           # eager so that events bracket single launches
+        cnr_amd._C.enable_kernel_timing(names)
+        for _ in range(min(args.steps, 50)):
+            tr.step()
+        tms = cnr_amd._C.kernel_timings_ms()
+        tr.use_graph = not args.no_graph
+        avg = {k: (sum(v) / len(v) if v else 0.0) for k, v in tms.items()}
+        # the dominant call again, back to back (no host gaps between launches): this is the duration rocprofv3 reports
+        # for its kernels (field kernel + reduce_records), and the one the roofline entry uses
+        if tr._ft_blocks:        # the one-launch step body is the dominant call; the two-call form is not on this path
+            bwd_name = "cnr_field_train"
+            eager_bwd_ms = avg[bwd_name]
+            avg[bwd_name] = tr.time_field_train(250)
+        else:
+            eager_bwd_ms = avg[bwd_name]
+            avg[bwd_name] = tr.time_field_bwd(50)
+        dom = max((bwd_name, "cnr_field_fwd", "cnr_field_fwd_render"), key=lambda k: avg[k])
+        # the backward call = the field kernel(s) (pipe: one launch; split: texture + geometry launches) + reduce_records:
+        # its duration is the sum of those (rocprof lists them separately, profiles/).
+        # algorithmic FLOP of that call: fwd = 27 422 / sample; backward (recomputes the forward) or the one-launch forward +
+        # backward = fwd + dX + dW = 82 140
+        flop_per_sample = 82140 if dom == bwd_name else 27422
+        achieved = C * R * S * flop_per_sample / (avg[dom] * 1e-3) / 1e12 if avg[dom] > 0 else 0.0
+        # HBM bytes of that call from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate rocprofv3 --pmc passes,
+        # with the gfx950 corrections): measured offline on this shape, kept in profiles/
+        traffic = None
+        for tname in ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", tname)
+            if dom == bwd_name and (C, R, S) == (1, 2048, 64) and os.path.exists(tpath):
+                traffic = json.load(open(tpath)).get(bwd_name + "_call_hbm_bytes")
+                break
+        roofline = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_MFMA_F16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / PEAK_MFMA_F16_TFLOPS, "traffic": traffic,
+                    "variant": "pipe8 (4 chain + 4 weight-gradient waves per workgroup, two per SIMD)",
+                    "kernel_ms": {k: round(v, 5) for k, v in avg.items()},
+                    "kernel_ms_note": "HIP events on the launch stream; %s back to back, median of five batches of 50 launches (one launch at a time in the "
+                                      "eager step, gaps included: %.5f), the others one launch at a time" % (bwd_name, eager_bwd_ms),
+                    "step_tflops": rays_per_step_global * S * FLOP_PER_SAMPLE_STEP / (dt / args.steps) / 1e12}
 
     par = "1 GPU" if world == 1 else (
         f"{world} GPUs, whole categories per GPU ({C_glob} in total), no gradient collective, empty-mask flags all-reduced once per epoch"
@@ -656,24 +684,27 @@ def main():
                                        "miss north_star's 1e-3 parity bar (3.9e-3 / 5.1e-3, BASELINE.md section 4), f16 has the "
                                        "same MFMA rate on gfx950 and three more mantissa bits",
                       "hipgraph": (f"{tr.unroll} steps per graph launch (halving group sizes down to single steps at epoch ends)" if not tr.grad_exchange else "two graphs around the all-reduce, per state parity") if not args.no_graph else False,
-                      "n_cu": info["n_cu"]},
-           "long_run": long_run, "roofline": roofline}
+                      "n_cu": info["n_cu"]}}
+    if args.full:
+        out["long_run"], out["roofline"] = long_run, roofline
     if world > 1:
+        out["world_size"], out["dist_backend"] = world, torch.distributed.get_backend()
+    if args.full and world > 1:
         ranks = torch.ones(1, device=dev if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(ranks)
-        out["world_size"], out["dist_backend"], out["ranks_answering"] = world, torch.distributed.get_backend(), int(ranks.item())
+        out["ranks_answering"] = int(ranks.item())
         if args.strong_classes >= world and shard == "class":
             try:
                 out["strong_configs2"] = strong_leg(cnr_amd, cfg, dev, pg, rank, world, args.strong_classes, args.rays, n_obj,
                                                     max(args.steps, 20), sync, timed_run)
             except Exception as e:          # never lose the main line over the extra leg
                 out["strong_configs2"] = f"failed: {type(e).__name__}: {e}"
-    if world > 1 and shard == "ray":   # outside the timed region: every rank must hold bitwise identical parameters after the run
+    if args.full and world > 1 and shard == "ray":   # outside the timed region: every rank must hold bitwise identical parameters after the run
         try:
             out["config"]["params_in_sync"] = bool(cnr_amd.parallel.params_in_sync(tr.theta.contiguous(), pg))
         except Exception as e:      # never lose the bench line over the check
             out["config"]["params_in_sync"] = f"check failed: {e}"
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         # the reference's REAL batch shape (configs/Replica/config_replica_room0.json:25-28: 120 rays per object, 1 + 9
         # samples): rays padded to 16 sample slots, two per tile, on the same one-launch step body
         try:
@@ -722,7 +753,7 @@ def main():
                 "category_rays_per_s": R * 500 / d3, "all_rays_per_s": (R + 1200) * 500 / d3}
         except Exception as e:
             out["extra_legs"]["full_iteration_bg_plus_category"] = f"failed: {e}"
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         # the two tiers behind the reference's call surface, side by side (VERDICT r03 row h): train.py's own loop on the drop-in
         # modules, and the fused step built from the same sceneCategory objects
         try:
@@ -753,7 +784,7 @@ def main():
         except Exception as e:
             out["extra_legs"]["split_graph_step_1gpu"] = f"failed: {type(e).__name__}: {e}"
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline((C, R, n1, n2, L, n_obj), args.cpu_seconds)
         print(json.dumps(out))
     if world > 1:

@@ -12,8 +12,13 @@ def test_sampling(name):
     for c in range(g.C):
         T, dirs = g.t("pool_T")[c], g.t("pool_dirs")[c]
         o, d = (O.origin_dirs_W if g.single_obj else O.origin_dirs_O)(T, dirs)
-        assert torch.equal(o, g.t("origins")[c]) and torch.equal(d, g.t("dirs_o")[c])
-        out = O.sample_3d_points(g.t("pool_rgbs")[c], g.t("pool_depth")[c], o, d, g.t("u")[c], g.t("g")[c],
+        o_ref, d_ref = g.t("origins")[c], g.t("dirs_o")[c]
+        # the pose inverse is a LAPACK call whose last bits follow the kernels MKL picks for the host CPU's instruction set, so
+        # on another CPU model than the fixtures' the transform agrees to a few fp32 ulps (|o| < 6, |d| < 5), not bit for bit ...
+        torch.testing.assert_close(o, o_ref, rtol=0, atol=2e-6)
+        torch.testing.assert_close(d, d_ref, rtol=0, atol=2e-6)
+        # ... and the sampling on the reference's own origins and directions bit for bit
+        out = O.sample_3d_points(g.t("pool_rgbs")[c], g.t("pool_depth")[c], o_ref, d_ref, g.t("u")[c], g.t("g")[c],
                                  g.n1, g.n2, g.eps, g.stop_eps)
         assert torch.equal(out[5], g.t("z")[c])
         assert torch.equal(out[4], g.t("pts")[c])
