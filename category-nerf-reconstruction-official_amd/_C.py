@@ -83,6 +83,10 @@ SIGNATURES = {
     "cnr_bg_backward_render_workspace_bytes": [_i],
     "cnr_bg_backward_render": [_vp, _vp],
     "cnr_bg_tail_sample": [_vp, _vp],
+    "cnr_mc_workspace_bytes": [_i],
+    "cnr_mc_count": [_vp, _i, _f, _vp, _vp, _vp],
+    "cnr_mc_emit": [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "cnr_grid_points": [_i, _f, _f, _vp, _vp, _vp, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
@@ -142,7 +146,8 @@ def struct_type(name):
 
 
 _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_bytes", "cnr_render_loss_workspace_bytes",
-              "cnr_dense_bwd_workspace_bytes", "cnr_field_fwd_render_workspace_bytes", "cnr_field_train_workspace_bytes", "cnr_pack_fp8_bytes", "cnr_bg_pack_bytes", "cnr_bg_backward_render_workspace_bytes"}
+              "cnr_dense_bwd_workspace_bytes", "cnr_field_fwd_render_workspace_bytes", "cnr_field_train_workspace_bytes", "cnr_pack_fp8_bytes", "cnr_bg_pack_bytes", "cnr_bg_backward_render_workspace_bytes",
+              "cnr_mc_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -30,6 +30,10 @@ class Config:
         self.net_hyperparams = md["net_hyperparams"]
         self.learning_rate, self.code_learning_rate = op["lr"], op["code_lr"]
         self.weight_decay, self.code_weight_decay = op["weight_decay"], op["code_weight_decay"]
+        vis = config.get("vis", {})           # meshing cadence and resolution (src/cfg.py:81-83), when present
+        for key in ("live_voxel_size", "grid_dim", "mesh_it"):
+            if key in vis:
+                setattr(self, key, vis[key])
 
 
 def synthetic_config(device="cuda:0", latent_dim=256, obj_scale=2.0, n_bins_cam2surface=8, n_bins=56):
@@ -49,4 +53,5 @@ def synthetic_config(device="cuda:0", latent_dim=256, obj_scale=2.0, n_bins_cam2
     c.net_hyperparams = dict(shape_blocks=2, texture_blocks=1, W=32, latent_dim=latent_dim)
     c.learning_rate = c.code_learning_rate = 0.001
     c.weight_decay = c.code_weight_decay = 0.013
+    c.grid_dim, c.live_voxel_size, c.mesh_it = 256, 0.005, 10000
     return c

@@ -7,6 +7,18 @@ import torch
 from .ops import CompositeFn, TerminationFn
 
 
+def make_3D_grid(occ_range=[-1., 1.], dim=256, device="cuda:0", transform=None, scale=None):
+    """src/render_rays.py:97-121 in one launch (cnr_grid_points): (dim, dim, dim, 3) points of torch.linspace(*occ_range, dim)
+    meshgrid 'ij', times `scale` (3,), then rotated and translated by `transform` (4,4) as the reference sums it."""
+    from . import _C
+    dev = torch.device(device)
+    out = torch.empty(dim, dim, dim, 3, device=dev, dtype=torch.float32)
+    sc = None if scale is None else torch.as_tensor(scale, dtype=torch.float32, device=dev).reshape(3).contiguous()
+    tr = None if transform is None else torch.as_tensor(transform, dtype=torch.float32, device=dev)[:3, :4].contiguous()
+    _C.call("cnr_grid_points", int(dim), float(occ_range[0]), float(occ_range[1]), sc, tr, out)
+    return out
+
+
 def occupancy_activation(alpha, distances=None):
     return torch.sigmoid(alpha)  # UniSurf style, `distances` ignored (src/render_rays.py:3-7)
 

@@ -1,14 +1,14 @@
 """Model holder with the reference's surface (src/trainer.py:11-60,125-151): ``.pe``,
 ``.fc_occ_map``, ``.shape_codes``, ``.texture_codes``, ``.inst_id_to_index``, ``.n_obj``,
-``.obj_scale``, ``.emb_size1/2``, ``.eval_points``.  Meshing (marching cubes / trimesh) is out of
-scope."""
+``.obj_scale``, ``.emb_size1/2``, ``.eval_points``, ``.meshing`` (the grid evaluation, marching cubes and colour pass
+on the GPU; returns a :class:`vis.Mesh`)."""
 import math
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import embedding, model, render_rays
+from . import embedding, model, render_rays, vis
 
 
 class Trainer:
@@ -56,6 +56,81 @@ class Trainer:
         self.texture_codes.weight = nn.Parameter(torch.randn(d, embdim) / math.sqrt(embdim / 2))
         self.shape_codes = self.shape_codes.to(self.device)
         self.texture_codes = self.texture_codes.to(self.device)
+
+    def meshing(self, inst_id=None, grid_dim=256):
+        """src/trainer.py:62-123: occupancy on a grid_dim^3 grid over the object's box, marching cubes at 0.5 ('ascent'),
+        back to scene coordinates, vertex colours from eval_points.  None where the reference returns None."""
+        occ_range = [-1., 1.]
+        range_dist = occ_range[1] - occ_range[0]
+        boxed = self.cls_id == 0 or self.n_obj == 1
+        if boxed:
+            bound = self.bound if self.cls_id == 0 else self.bound_dict[inst_id]
+            scale_np = bound.extent / (range_dist * self.bound_extent)
+            scale = torch.from_numpy(np.asarray(scale_np)).float().to(self.device)
+            transform_np = np.eye(4, dtype=np.float32)
+            transform_np[:3, 3] = bound.center
+            transform_np[:3, :3] = bound.R
+            transform = torch.from_numpy(transform_np).to(self.device)
+            grid_pc = render_rays.make_3D_grid(occ_range=occ_range, dim=grid_dim, device=self.device,
+                                               scale=scale, transform=transform).view(-1, 3)
+        else:
+            extent = self.extent_dict[inst_id]
+            extent = extent / np.max(extent / 2)
+            scale_np = extent / (range_dist * self.bound_extent)
+            scale = torch.from_numpy(np.asarray(scale_np)).float().to(self.device)
+            grid_pc = render_rays.make_3D_grid(occ_range=occ_range, dim=grid_dim, device=self.device, scale=scale).view(-1, 3)
+        if self.cls_id == 0:
+            ret = self.eval_points(grid_pc)
+            occ = None if ret is None else ret[0]
+        else:
+            occ = self._grid_occupancy(grid_pc, inst_id)
+        if occ is None:
+            return None
+        mesh = vis.marching_cubes(occ.view(grid_dim, grid_dim, grid_dim))
+        if mesh is None:
+            print("marching cube failed")
+            return None
+        mesh.apply_translation([-0.5, -0.5, -0.5])      # to [-1, 1]
+        mesh.apply_scale(2)
+        mesh.apply_scale(scale_np)                       # to scene coordinates
+        if boxed:
+            mesh.apply_transform(transform_np)
+        vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
+        ret = self.eval_points(vertices_pts) if self.cls_id == 0 else self.eval_points(vertices_pts, inst_id=inst_id)
+        if ret is None:
+            return None
+        _, color = ret
+        mesh.visual.vertex_colors = (color * 255).detach().squeeze(0).cpu().numpy().astype(np.uint8)
+        return mesh
+
+    def _codenerf_rows(self, inst_id):
+        """(trunk (1,13892), B (1,21,3), bias rows (1,4,32)) of one object of this CodeNeRF category"""
+        from . import ops
+        fc = self.fc_occ_map
+        obj_idx = torch.tensor(self.inst_id_to_index[inst_id], device=self.device)
+        shape_code, texture_code = self.shape_codes(obj_idx), self.texture_codes(obj_idx)
+        trunk = torch.cat([t.reshape(1, -1) for n, _, _ in ops.TRUNK_LAYERS
+                           for t in (fc._linear(n).weight, fc._linear(n).bias)], dim=1).contiguous()
+        zlat = fc.latent_rows(shape_code.view(1, 1, -1), texture_code.view(1, 1, -1))       # (1,4,32)
+        brows = ops.bias_rows(trunk, zlat[None]).reshape(1, 4, 32).contiguous()
+        B = self.pe.B_layer.weight.reshape(1, 21, 3).contiguous()
+        return trunk, B, brows
+
+    def _grid_occupancy(self, grid_pc, inst_id):
+        """Occupancy of a whole meshing grid in ONE cnr_field_fwd launch on the precise geometry branch (packed_lo: the
+        split-weight products of DESIGN.md §3.3, 2e-6 of the exact occupancy on trained weights where plain f16 gives 1.8e-3 and
+        moves surface vertices).  None when nothing is occupied, as eval_points."""
+        from . import ops
+        with torch.no_grad():
+            trunk, B, brows = self._codenerf_rows(inst_id)
+            row = torch.zeros(1, 1, device=grid_pc.device, dtype=torch.int32)
+            sig, _ = ops.field_fwd(grid_pc.float().contiguous().view(1, 1, -1, 3), B, ops.pack_weights(trunk), brows, row,
+                                   self.pe._scale, packed_lo=ops.pack_weights_lo(trunk))
+            occ = render_rays.occupancy_activation(sig.reshape(-1))
+        if occ.max() == 0:
+            print("no occ")
+            return None
+        return occ
 
     def eval_points(self, points, inst_id=None, chunk_size=500000):
         """Forward-only occupancy / colour of (N,3) points for one object (src/trainer.py:125-151) -> (occ (N,),

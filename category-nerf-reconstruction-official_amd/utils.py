@@ -64,3 +64,24 @@ def get_transform_from_tensor_sim3(vec):
     T[:, :3, :3] = R * s[:, None, None]
     T[:, :3, 3] = t
     return T[0] if single else T
+
+
+def quad2rotation(quad):
+    """(n,4) quaternions [r, i, j, k] (need not be unit) -> (n,3,3) rotations (src/utils.py:468-491)"""
+    qr, qi, qj, qk = quad.unbind(-1)
+    two_s = 2.0 / (quad * quad).sum(-1)
+    return torch.stack([1 - two_s * (qj ** 2 + qk ** 2), two_s * (qi * qj - qk * qr), two_s * (qi * qk + qj * qr),
+                        two_s * (qi * qj + qk * qr), 1 - two_s * (qi ** 2 + qk ** 2), two_s * (qj * qk - qi * qr),
+                        two_s * (qi * qk - qj * qr), two_s * (qj * qk + qi * qr), 1 - two_s * (qi ** 2 + qj ** 2)],
+                       -1).view(-1, 3, 3)
+
+
+def get_transform_from_tensor(inputs):
+    """(7,) or (n,7) [qr, qi, qj, qk, tx, ty, tz] -> (4,4) / (n,4,4) rigid transforms (src/utils.py:411-430; train.py:232 calls
+    it on object_tensor_dict[obj][1:])."""
+    single = inputs.dim() == 1
+    v = inputs[None] if single else inputs
+    RT = torch.eye(4, device=v.device, dtype=v.dtype).repeat(v.shape[0], 1, 1)
+    RT[:, :3, :3] = quad2rotation(v[:, :4])
+    RT[:, :3, 3] = v[:, 4:7]
+    return RT[0] if single else RT

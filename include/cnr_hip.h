@@ -724,6 +724,29 @@ typedef struct cnr_bg_tail_sample_args {
 } cnr_bg_tail_sample_args;
 int cnr_bg_tail_sample(const cnr_bg_tail_sample_args* args, void* stream);
 
+/* ---- Meshing: Trainer.meshing (src/trainer.py:62-123), vis.marching_cubes (src/vis.py:6-20), make_3D_grid
+ * (src/render_rays.py:97-121).  DESIGN.md §3.6.
+ * vol (D,D,D) f32, C-contiguous, axis 0 = x: point (i0,i1,i2) at (i0 D + i1) D + i2, 2 <= D <= 512 (else CNR_E_SHAPE).
+ * A corner is inside when v > level (NaN: outside); an edge is crossed when exactly one end is inside, and its vertex lies at
+ * t = (level - v0) / (v1 - v0) clamped to [0,1] from the lower end, in index space / (D - 1).  One vertex per crossed edge,
+ * owned by the edge's lower grid point; vertices sorted by (owning point, axis), faces by (cell = its min corner, table order;
+ * table: csrc/mc_table.h, generated by tools/gen_mc_table.py).  ascent != 0: the right-hand face normal points towards
+ * increasing values; 0: the same faces with columns 1 and 2 swapped.  Normals: np.gradient-style central differences
+ * (one-sided at the border) at both ends of the edge, interpolated with t, normalised, on the faces' side (0 when zero).
+ * Two steps so that the caller allocates exact outputs:
+ *   workspace >= cnr_mc_workspace_bytes(D) bytes (CNR_E_SHAPE for a bad D);
+ *   cnr_mc_count writes counts_out (2,) i64 = {V, F} (device memory) and keeps the classification in workspace;
+ *   cnr_mc_emit, with the same vol / D / level / workspace after cnr_mc_count on the same stream, writes verts (V,3),
+ *   normals (V,3), faces (F,3) i32.  V = F = 0 when no edge crosses (then do not call cnr_mc_emit). */
+int64_t cnr_mc_workspace_bytes(int D);
+int cnr_mc_count(const float* vol, int D, float level, void* workspace, int64_t* counts_out, void* stream);
+int cnr_mc_emit(const float* vol, int D, float level, int ascent, void* workspace, float* verts, float* normals, int* faces,
+                void* stream);
+/* make_3D_grid(occ_range = [lo, hi], dim = D, transform, scale).view(-1, 3) in one pass: out (D^3, 3); scale (3,) or NULL,
+ * transform (3,4) row-major [R | t] or NULL.  torch.linspace's two-sided formula, then * scale, then r_k . p summed x, y, z
+ * left to right, then + t; 2 <= D <= 512. */
+int cnr_grid_points(int D, float lo, float hi, const float* scale, const float* transform, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
