@@ -747,6 +747,38 @@ int cnr_mc_emit(const float* vol, int D, float level, int ascent, void* workspac
  * left to right, then + t; 2 <= D <= 512. */
 int cnr_grid_points(int D, float lo, float hi, const float* scale, const float* transform, float* out, void* stream);
 
+/* ---- Mesh evaluation: metric/metrics.py, metric/eval_3D_obj.py:10-39.  DESIGN.md §3.7.  Every call is bit-identical run to
+ * run (no atomics; fixed reduction orders).  Points are (n,3) f32, C-contiguous.
+ * Nearest-neighbour distance: dist_out[i] = min_j |q_i - p_j| (Euclidean, fp32: (q - p)^2 summed per component, the min of the
+ * squares, one correctly rounded sqrt).  nq, nr >= 1 (else CNR_E_SHAPE); workspace >= cnr_nn_workspace_bytes(nq, nr). */
+int64_t cnr_nn_workspace_bytes(int64_t nq, int64_t nr);
+int cnr_nn_dist(const float* q, int64_t nq, const float* p, int64_t nr, float* dist_out, void* workspace, void* stream);
+/* *sum_out (f64, device) = sum of dist[0..n) in a fixed order, *count_out (i64, device) = #{i : dist[i] < th}; n >= 1,
+ * workspace >= cnr_dist_stats_workspace_bytes(n). */
+int64_t cnr_dist_stats_workspace_bytes(int64_t n);
+int cnr_dist_stats(const float* dist, int64_t n, float th, void* workspace, double* sum_out, int64_t* count_out, void* stream);
+/* Triangles: verts f32 and faces (F,3) i32 into verts, or faces == NULL for a soup (verts (F,3,3): what cnr_clip_box_emit
+ * writes).  area (F,) f64 = |(v1 - v0) x (v2 - v0)| / 2 in fp64, cum (F,) f64 its inclusive prefix sum; F >= 1,
+ * workspace >= cnr_face_area_workspace_bytes(F). */
+int64_t cnr_face_area_workspace_bytes(int64_t F);
+int cnr_face_area_scan(const float* verts, const int* faces, int64_t F, void* workspace, double* area, double* cum, void* stream);
+/* Area-weighted surface samples from caller-drawn uniforms u (n,3) f64 in [0,1): face = the first f with cum[f] >= u0 cum[F-1]
+ * (searchsorted, side 'left'); (a, b) = (u1, u2), reflected to (1 - a, 1 - b) when a + b > 1; out[i] (f32) =
+ * (v1 - v0) a + (v2 - v0) b + v0 in fp64, rounded once.  Same triangle forms as cnr_face_area_scan, cum from it. */
+int cnr_sample_surface(const float* verts, const int* faces, int64_t F, const double* cum, const double* u, int64_t n,
+                       float* out, void* stream);
+/* The part of the triangles inside a convex box: planes (6,6) f64 rows (origin xyz, inward normal xyz); a point is kept when
+ * (x - o) . n >= 0 for all six.  Each triangle is clipped in turn against the six planes (Sutherland-Hodgman, fp64) and the
+ * polygon left is fan-triangulated from its first vertex; output tris (T,3,3) f32 in (face, fan) order.  Two steps as for
+ * marching cubes: cnr_clip_box_count writes count_out (1,) i64 = T (device) and keeps per-workgroup offsets in workspace
+ * (>= cnr_clip_box_workspace_bytes(F)); cnr_clip_box_emit, with the same inputs and workspace after it on the same stream,
+ * writes tris (do not call it when T = 0). */
+int64_t cnr_clip_box_workspace_bytes(int64_t F);
+int cnr_clip_box_count(const float* verts, const int* faces, int64_t F, const double* planes, void* workspace,
+                       int64_t* count_out, void* stream);
+int cnr_clip_box_emit(const float* verts, const int* faces, int64_t F, const double* planes, void* workspace, float* tris,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

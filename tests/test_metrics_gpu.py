@@ -1,0 +1,281 @@
+"""GPU: csrc/metric.hip against float64 brute force and the numpy restatement (tests/metric_cpu.py), the public metrics against
+the reference's metrics.py (tests/golden/metric/), calc_3d_metric end to end on analytic shapes, and tools/eval_3d_obj.py on a
+tiny Replica-style tree."""
+import glob
+import json
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import mc_cpu as M
+import metric_cpu as K
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+METRIC_GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "metric", "*.npz")))
+
+
+@pytest.fixture(scope="module")
+def mt():
+    from cnr_amd import metrics
+    return metrics
+
+
+def _brute(q, p):
+    """float64 nearest distances by broadcasting, in query chunks of at most 2e7 pairs"""
+    q64, p64 = q.double(), p.double()
+    step = max(1, 20_000_000 // len(p64))
+    out = []
+    for i in range(0, len(q64), step):
+        out.append(((q64[i:i + step, None, :] - p64[None]) ** 2).sum(-1).min(1).values.sqrt())
+    return torch.cat(out)
+
+
+@pytest.mark.parametrize("nq,nr", [(1, 1), (1, 63), (63, 1), (64, 64), (65, 65), (1000, 1000), (63, 1000), (1000, 65),
+                                   (10000, 10000), (200000, 5000), (5000, 200000)])
+def test_nn_dist_against_float64_brute_force(mt, dev, nq, nr):
+    g = torch.Generator(device=dev).manual_seed(nq * 7 + nr)
+    q = torch.rand(nq, 3, device=dev, generator=g) * 6 - 1        # metres, away from the origin
+    p = torch.rand(nr, 3, device=dev, generator=g) * 6 - 1
+    d = mt.nn_dist(q, p)
+    ref = _brute(q, p)
+    bar = 2e-6 * (1 + q.double().norm(dim=1))
+    assert ((d.double() - ref).abs() <= bar).all(), float(((d.double() - ref).abs() - bar).max())
+    again = mt.nn_dist(q, p)
+    assert torch.equal(d, again)
+
+
+def test_nn_dist_duplicates_and_exact_hits(mt, dev):
+    g = torch.Generator(device=dev).manual_seed(3)
+    p = torch.rand(3000, 3, device=dev, generator=g) * 4 + 3
+    p = torch.cat([p, p[:1000], p[:10]])                            # duplicated reference points
+    q = torch.cat([p[500:1500], torch.rand(700, 3, device=dev, generator=g) * 4 + 3])
+    d = mt.nn_dist(q, p)
+    assert (d[:1000] == 0).all()
+    ref = _brute(q, p)
+    assert ((d.double() - ref).abs() <= 2e-6 * (1 + q.double().norm(dim=1))).all()
+    assert torch.equal(mt.nn_dist(q, q), torch.zeros(len(q), device=dev))
+
+
+def test_dist_stats(mt, dev):
+    g = torch.Generator(device=dev).manual_seed(5)
+    for n in (1, 255, 256, 257, 10000, 200001):
+        d = torch.rand(n, device=dev, generator=g) * 0.2
+        th = 0.05
+        s, c = mt.dist_stats(d, th)
+        d64 = d.double()
+        assert s == pytest.approx(float(d64.sum()), rel=1e-10, abs=1e-300)
+        if not ((d64 - th).abs() < 1e-6).any():
+            assert c == int((d < th).sum())
+        assert (s, c) == mt.dist_stats(d, th)
+
+
+def _mc_mesh(D=48, r0=0.85, centre=(0.0, 0.0, 0.0), scale=1.0):
+    from cnr_amd import vis
+    m = vis.marching_cubes(M.sphere(D, r0, 4.0, centre))
+    m.apply_translation([-0.5, -0.5, -0.5]).apply_scale(2.0 * scale)
+    return m
+
+
+def test_sample_surface_matches_the_restatement(mt, dev):
+    rng = np.random.default_rng(4)
+    meshes = [_mc_mesh(33), _mc_mesh(64, 0.6, (0.2, 0.0, 0.1), 3.0)]
+    from cnr_amd import vis
+    v = rng.normal(size=(300, 3)) * 2 + 4
+    meshes.append(vis.Mesh(v, rng.integers(0, 300, (500, 3))))
+    for m in meshes:
+        tri = mt._mesh_device(m, dev)
+        area, cum = mt._area_scan(tri)
+        T = K.triangles(m.vertices, m.faces)
+        np.testing.assert_allclose(area.cpu().numpy(), K.face_areas(T), rtol=1e-12, atol=0)
+        u = rng.random((20000, 3))
+        face, pts, cum_r = K.sample_surface(T, u)
+        np.testing.assert_allclose(cum.cpu().numpy(), cum_r, rtol=1e-12)
+        out = torch.empty(len(u), 3, device=dev)
+        from cnr_amd import _C
+        _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), out)
+        got = out.cpu().numpy()
+        # the same face wherever u0 * total is not within 1e-12 (relative) of a prefix boundary
+        target = u[:, 0] * cum_r[-1]
+        near = np.abs(cum_r[np.minimum(face, len(cum_r) - 1)] - target) < 1e-12 * cum_r[-1]
+        near |= np.abs(cum_r[np.maximum(face - 1, 0)] - target) < 1e-12 * cum_r[-1]
+        ok = ~near
+        np.testing.assert_allclose(got[ok], pts[ok], rtol=0, atol=1e-6 * (1 + np.abs(pts[ok]).max()))
+        a1 = torch.empty_like(out)
+        _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), a1)
+        assert torch.equal(out, a1)
+
+
+def _random_box(rng, centre, ext):
+    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] *= -1
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = q, -q @ np.asarray(centre)
+    return T, np.asarray(ext, np.float64)
+
+
+def test_clip_matches_the_restatement(mt, dev):
+    from cnr_amd import vis
+    rng = np.random.default_rng(6)
+    soup_v = rng.normal(size=(3000, 3)) * 0.5
+    cases = [(_mc_mesh(48), (0.1, 0.0, -0.2), (1.2, 0.9, 1.0)), (_mc_mesh(96), (0.0, 0.3, 0.0), (0.4, 2.5, 2.5)),
+             (vis.Mesh(soup_v, np.arange(3000).reshape(-1, 3)), (0.0, 0.0, 0.0), (0.7, 0.7, 0.7))]
+    for m, c, e in cases:
+        T, ext = _random_box(rng, c, e)
+        planes = mt.box_planes(T, ext)
+        tri = mt._mesh_device(m, dev)
+        out = mt._clip(tri, planes)
+        ref = K.clip_box(K.triangles(m.vertices, m.faces), planes)
+        assert out is not None and len(ref)
+        got = out[0].double().cpu().numpy().reshape(-1, 3, 3)
+        assert K.face_areas(got).sum() == pytest.approx(K.face_areas(ref).sum(), rel=1e-5)
+        loc = got.reshape(-1, 3) @ T[:3, :3].T + T[:3, 3]
+        assert (np.abs(loc) <= ext / 2 + 1e-5).all()
+        again = mt._clip(tri, planes)
+        assert torch.equal(out[0], again[0])
+        # the soup itself can be clipped and sampled again
+        assert mt._sample(out, 1000, np.random.default_rng(1)).shape == (1000, 3)
+    # outside everything: nothing
+    T, ext = _random_box(rng, (10.0, 0.0, 0.0), (0.5, 0.5, 0.5))
+    assert mt._clip(mt._mesh_device(_mc_mesh(33), dev), mt.box_planes(T, ext)) is None
+
+
+@pytest.mark.parametrize("path", METRIC_GOLDEN, ids=[os.path.basename(p)[:-4] for p in METRIC_GOLDEN])
+def test_public_metrics_match_the_reference(mt, dev, path):
+    z = np.load(path)
+    gt, rec = z["gt"], z["rec"]
+    assert mt.accuracy(gt, rec) == pytest.approx(float(z["accuracy"]), rel=1e-5)
+    assert mt.completion(gt, rec) == pytest.approx(float(z["completion"]), rel=1e-5)
+    assert mt.chamfer(torch.from_numpy(gt).to(dev), rec) == pytest.approx(float(z["chamfer"]), rel=1e-5)
+    assert mt.accuracy_ratio(gt, rec, float(z["th_acc"])) == pytest.approx(float(z["accuracy_ratio"]), rel=1e-5)
+    assert mt.completion_ratio(gt, rec, float(z["th_comp"])) == pytest.approx(float(z["completion_ratio"]), rel=1e-5)
+    assert isinstance(mt.accuracy(gt, rec), float)
+
+
+# ---- end to end ----------------------------------------------------------------------------------------------------------
+R0, DELTA = 0.40, 0.02
+
+
+def _sphere_mesh(r, D=96):
+    """a marching-cubes sphere of radius r (metres) about the origin"""
+    m = _mc_mesh(D, 0.8)
+    m.vertices = m.vertices * (r / 0.8)
+    return m
+
+
+def test_calc_3d_metric_on_concentric_spheres(mt, dev):
+    rec, gt = _sphere_mesh(R0), _sphere_mesh(R0 + DELTA)
+    out = mt.calc_3d_metric(rec, gt, N=200000)
+    acc, comp, ratio = out[0][0], out[1][0], out[2][0]
+    # the chord error of the mesh (~h^2 / 8r ~ 0.01 cm) and the sampling's tangential offset (~0.05 cm at 200k) both add
+    assert DELTA * 100 - 0.05 < acc < DELTA * 100 + 0.15, out
+    assert DELTA * 100 - 0.05 < comp < DELTA * 100 + 0.15, out
+    assert ratio == 100.0
+    assert isinstance(acc, float) and mt.calc_3d_metric(rec, gt, N=200000) == out       # seeded, deterministic
+    gt_pts, rec_pts = mt.sample_surface(gt, 50000, seed=1), mt.sample_surface(rec, 50000, seed=2)
+    assert mt.completion_ratio(gt_pts, rec_pts, 0.05) == 1.0
+    assert mt.completion_ratio(gt_pts, rec_pts, 0.01) == 0.0
+    assert mt.accuracy_ratio(gt_pts, rec_pts, 0.03) == 1.0
+
+
+def test_calc_3d_metric_crops_to_a_half_sphere(mt, dev):
+    from cnr_amd import vis
+    rec, big = _sphere_mesh(R0), _sphere_mesh(R0 + DELTA)
+    keep = (big.vertices[big.faces][:, :, 2] > 0).all(1)
+    half = vis.Mesh(big.vertices, big.faces[keep])
+    T, ext = mt.oriented_bounds(half)
+    cut = mt.slice_box(rec, T, ext)
+    assert cut.vertices[:, 2].min() > -1e-5 - 0.002                   # the half sphere's lowest vertex lies just above 0
+    area = K.face_areas(K.triangles(cut.vertices, cut.faces)).sum()
+    full = K.face_areas(K.triangles(rec.vertices, rec.faces)).sum()
+    assert 0.45 < area / full < 0.52
+    out = mt.calc_3d_metric(rec, half, N=100000)
+    # accuracy on the cropped upper half stays ~delta; completion (half GT against the whole rec) too
+    assert DELTA * 100 - 0.1 < out[0][0] < DELTA * 100 + 0.4, out
+    assert DELTA * 100 - 0.1 < out[1][0] < DELTA * 100 + 0.3, out
+    # without the crop the lower half would be ~R0 away: the uncropped accuracy is far larger
+    assert mt.accuracy(mt.sample_surface(half, 50000), mt.sample_surface(rec, 50000)) * 100 > 3 * out[0][0]
+
+
+def test_calc_3d_metric_with_the_box_elsewhere_is_none(mt, dev, capsys):
+    rec, far = _sphere_mesh(R0), _sphere_mesh(R0)
+    far.apply_translation([10.0, 0.0, 0.0])
+    assert mt.calc_3d_metric(rec, far, N=1000) is None
+    assert "no mesh found" in capsys.readouterr().out
+
+
+# ---- the command line ----------------------------------------------------------------------------------------------------
+def _write_quad_ply(path, v, quads):
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v), "property float x", "property float y",
+            "property float z", "property uchar red", "property uchar green", "property uchar blue",
+            "element face %d" % len(quads), "property list uchar int vertex_indices", "property int object_id", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode())
+        for p in v:
+            f.write(struct.pack("<3f3B", *p, 200, 100, 50))
+        for q in quads:
+            f.write(struct.pack("<B4ii", 4, *q, 3))
+
+
+def _cube(lo, hi, n=8):
+    """the surface of a box as an n x n grid of quads per face"""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    verts, quads = [], []
+    t = np.linspace(0, 1, n + 1)
+    for ax in range(3):
+        for side in (0, 1):
+            a, b = [k for k in range(3) if k != ax]
+            base = len(verts)
+            for i in range(n + 1):
+                for j in range(n + 1):
+                    p = np.empty(3)
+                    p[ax] = (lo if side == 0 else hi)[ax]
+                    p[a] = lo[a] + t[i] * (hi[a] - lo[a])
+                    p[b] = lo[b] + t[j] * (hi[b] - lo[b])
+                    verts.append(p)
+            for i in range(n):
+                for j in range(n):
+                    k = base + i * (n + 1) + j
+                    quads.append([k, k + n + 1, k + n + 2, k + 1])
+    return np.array(verts), np.array(quads)
+
+
+def test_eval_3d_obj_cli_on_a_replica_tree(dev, tmp_path):
+    from cnr_amd import vis
+    data = tmp_path / "Replica"
+    hab = data / "room_0" / "habitat"
+    hab.mkdir(parents=True)
+    boxes = {1: ([0.0, 0.0, 0.0], [0.5, 0.4, 0.3]), 2: ([1.0, 1.0, 0.0], [1.3, 1.6, 0.8])}
+    (hab / "info_semantic.json").write_text(json.dumps({"objects": [{"id": 1, "class_id": 7}, {"id": 2, "class_id": 40}]}))
+    logs = tmp_path / "logs"
+    mdir = logs / "room_0" / "scene_mesh"
+    mdir.mkdir(parents=True)
+    for k, (lo, hi) in boxes.items():
+        v, q = _cube(lo, hi)
+        _write_quad_ply(str(hab / ("mesh_semantic.ply_%d.ply" % k)), v, q)
+        rv, rq = _cube(np.array(lo) + 0.01, np.array(hi) - 0.01, 6)        # a reconstruction 1 cm in on every side
+        tris = np.concatenate([rq[:, [0, 1, 2]], rq[:, [0, 2, 3]]])
+        vis.Mesh(rv, tris).export(str(mdir / ("iteration_10000_obj%d.obj" % k)))
+    vis.Mesh(*_cube([0, 0, 0], [1, 1, 1])[:1], np.zeros((0, 3), np.int64)).export(str(mdir / "iteration_500_obj3.obj"))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "eval_3d_obj.py"), "--data_dir", str(data),
+                        "--log_dir", str(logs)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = logs / "room_0" / "eval_mesh"
+    per = {k: np.load(out / ("metric_obj%d.npy" % k)) for k in boxes}
+    allm = np.load(out / "metrics_3D_obj.npy")
+    assert allm.shape == (3, 2, 1) and not (out / "metric_obj3.npy").exists()
+    for k, m in per.items():
+        assert m.shape == (3, 1)
+        acc, comp, ratio = m[:, 0]
+        # 1 cm offset surfaces, 10k samples: about 1 cm each way (plus the sampling's spread), all within 5 cm
+        assert 0.5 < acc < 2.0 and 0.5 < comp < 2.0 and ratio == 100.0, (k, m)
+    np.testing.assert_array_equal(allm[:, 0], per[1])
+    assert "Acc | Comp | Comp Ratio 5cm" in r.stdout

@@ -1,0 +1,139 @@
+"""3-D metrics of the reconstructed meshes (metric/eval_3D_obj.py's command line and output files), on cnr_amd.metrics:
+
+    python tools/eval_3d_obj.py --data_dir Datasets/Replica --log_dir logs/Replica [--log_dir_ref DIR] [--iteration 10000]
+
+For every scene of the dataset (the last component of --data_dir: Replica or ScanNet) whose <log_dir>/<scene>/scene_mesh exists,
+every object mesh iteration_<it>_obj<id>.obj written by train.py is scored against its ground-truth mesh in
+<data_dir>/<scene>/habitat (Replica: mesh_semantic.ply_<id>.ply; ScanNet: <scene>_vh_clean_2.ply_<id>.ply): accuracy and
+completion in cm, completion ratio at 5 cm in %.  Written: <log_dir>/<scene>/eval_mesh/metric_obj<id>.npy ((3,1)) and
+metrics_3D_obj.npy ((3, objects, 1)).  N = 10 000 samples per object, 200 000 for the background (id 0, whose ground truth is
+the union of the background classes' meshes) -- as in the reference, id 0 is left out where the ids are parsed from the file
+names.  A --log_dir_ref mesh it_<it>_obj<id>.obj, where present, sets the crop box instead of the ground truth.
+Differences from the reference: only the meshes of --iteration are listed (the reference lists every .obj and then opens
+the --iteration one), scenes without a scene_mesh directory are skipped, and the samples are seeded (cnr_amd.metrics)."""
+import argparse
+import csv
+import json
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+REPLICA_BG = [5, 12, 30, 31, 40, 60, 92, 93, 95, 97, 98, 79]
+REPLICA_SCENES = ["room_0", "room_1", "room_2", "office_0", "office_1", "office_2", "office_3", "office_4"]
+SCANNET_BG = [-1, 0, 1, 3, 16, 41, 232, 21, 161, 128, 21]
+SCANNET_SCENES = ["scene0013_02", "scene0059_00", "scene0066_00", "scene0281_00"]
+
+
+def concatenate(meshes):
+    from cnr_amd.vis import Mesh
+    v, f, n = [], [], 0
+    for m in meshes:
+        v.append(m.vertices)
+        f.append(m.faces + n)
+        n += len(m.vertices)
+    return Mesh(np.concatenate(v) if v else np.zeros((0, 3)), np.concatenate(f) if f else np.zeros((0, 3), np.int64))
+
+
+def get_gt_bg_mesh(gt_dir, background_cls_list):
+    from cnr_amd.vis import load_mesh
+    with open(os.path.join(gt_dir, "info_semantic.json")) as f:
+        objects = json.load(f)["objects"]
+    return concatenate([load_mesh(os.path.join(gt_dir, "mesh_semantic.ply_%d.ply" % int(o["id"])))
+                        for o in objects if int(o["class_id"]) in background_cls_list])
+
+
+def read_label_mapping(filename, label_from="raw_category", label_to="id"):
+    mapping = {}
+    with open(filename) as f:
+        for row in csv.DictReader(f, delimiter="\t"):
+            mapping[row[label_from]] = int(row[label_to])
+    try:
+        return {int(k): v for k, v in mapping.items()}
+    except ValueError:
+        return mapping
+
+
+def get_gt_bg_mesh_scannet(gt_dir, exp, background_cls_list, label_map_file):
+    from cnr_amd.vis import load_mesh
+    label_map = read_label_mapping(label_map_file)
+    with open(os.path.join(gt_dir, exp + ".aggregation.json")) as f:
+        groups = json.load(f)["segGroups"]
+    meshes = [load_mesh(os.path.join(gt_dir, "%s_vh_clean_2.ply_%d.ply" % (exp, int(g["id"]) + 2)))
+              for g in groups if label_map[g["label"]] in background_cls_list]
+    # the label table has no row for "unknown" (instance 0): always part of the background
+    meshes.append(load_mesh(os.path.join(gt_dir, exp + "_vh_clean_2.ply_0.ply")))
+    return concatenate(meshes)
+
+
+def get_obj_ids(obj_dir, iteration):
+    ids = set()
+    for name in os.listdir(obj_dir):
+        m = re.fullmatch(r"iteration_%d_obj(\d+)\.obj" % iteration, name)
+        if m and int(m.group(1)) != 0:
+            ids.add(int(m.group(1)))
+    return sorted(ids)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--data_dir", default="Datasets/Replica", type=str)
+    ap.add_argument("--log_dir", default="logs/Replica", type=str)
+    ap.add_argument("--log_dir_ref", default="", type=str)
+    ap.add_argument("--iteration", default=10000, type=int)
+    args = ap.parse_args(argv)
+    from cnr_amd.metrics import calc_3d_metric
+    from cnr_amd.vis import load_mesh
+
+    dataset = os.path.basename(os.path.normpath(args.data_dir))
+    if dataset == "Replica":
+        bg_cls, scenes = REPLICA_BG, REPLICA_SCENES
+    elif dataset == "ScanNet":
+        bg_cls, scenes = SCANNET_BG, SCANNET_SCENES
+        label_map_file = os.path.join(args.data_dir, "scannetv2-labels.combined.tsv")
+    else:
+        raise SystemExit(f"Dataset {dataset} is not supported (Replica, ScanNet)")
+
+    for exp in scenes:
+        gt_dir = os.path.join(args.data_dir, exp, "habitat")
+        exp_dir = os.path.join(args.log_dir, exp)
+        mesh_dir = os.path.join(exp_dir, "scene_mesh")
+        mesh_dir_ref = os.path.join(args.log_dir_ref, exp, "scene_mesh")
+        if not os.path.isdir(mesh_dir):
+            print(f"skip {exp}: no {mesh_dir}")
+            continue
+        output_path = os.path.join(exp_dir, "eval_mesh")
+        os.makedirs(output_path, exist_ok=True)
+        metrics_3D = [[] for _ in range(3)]
+        for obj_id in get_obj_ids(mesh_dir, args.iteration):
+            if obj_id == 0:
+                N = 200000
+                mesh_gt = (get_gt_bg_mesh(gt_dir, bg_cls) if dataset == "Replica"
+                           else get_gt_bg_mesh_scannet(gt_dir, exp, bg_cls, label_map_file))
+            else:
+                N = 10000
+                mesh_gt = load_mesh(os.path.join(gt_dir, "mesh_semantic.ply_%d.ply" % obj_id) if dataset == "Replica"
+                                    else os.path.join(gt_dir, "%s_vh_clean_2.ply_%d.ply" % (exp, obj_id)))
+            mesh_rec = load_mesh(os.path.join(mesh_dir, "iteration_%d_obj%d.obj" % (args.iteration, obj_id)))
+            ref_file = os.path.join(mesh_dir_ref, "it_%d_obj%d.obj" % (args.iteration, obj_id))
+            mesh_ref = load_mesh(ref_file) if os.path.exists(ref_file) else mesh_gt
+            metrics = calc_3d_metric(mesh_rec, mesh_ref, N=N, mesh_gt=mesh_gt)
+            if metrics is None:
+                continue
+            np.save(os.path.join(output_path, "metric_obj%d.npy" % obj_id), np.array(metrics))
+            for k in range(3):
+                metrics_3D[k].append(metrics[k])
+        metrics_3D = np.array(metrics_3D)
+        np.save(os.path.join(output_path, "metrics_3D_obj.npy"), metrics_3D)
+        print("metrics 3D obj \n Acc | Comp | Comp Ratio 5cm \n", metrics_3D.mean(axis=1) if metrics_3D.size else metrics_3D)
+        print("-----------------------------------------")
+        print("finish exp ", exp)
+
+
+if __name__ == "__main__":
+    main()
