@@ -97,6 +97,12 @@ SIGNATURES = {
     "cnr_clip_box_workspace_bytes": [_i64],
     "cnr_clip_box_count": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "cnr_clip_box_emit": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "cnr_frame_instances_workspace_bytes": [_i, _i],
+    "cnr_frame_instances_count": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "cnr_frame_instances_emit": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "cnr_frame_finish": [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp],
+    "cnr_resize_linear_u8c3": [_vp, _i, _i, _i, _vp, _i, _i, _vp],
+    "cnr_resize_nearest": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
@@ -158,7 +164,7 @@ def struct_type(name):
 _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_bytes", "cnr_render_loss_workspace_bytes",
               "cnr_dense_bwd_workspace_bytes", "cnr_field_fwd_render_workspace_bytes", "cnr_field_train_workspace_bytes", "cnr_pack_fp8_bytes", "cnr_bg_pack_bytes", "cnr_bg_backward_render_workspace_bytes",
               "cnr_mc_workspace_bytes", "cnr_nn_workspace_bytes", "cnr_dist_stats_workspace_bytes",
-              "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes"}
+              "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes"}
 
 _lib = None
 _double = None

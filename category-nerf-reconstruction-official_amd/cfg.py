@@ -1,7 +1,9 @@
-"""Config reader for the keys the hot path consumes, same attribute names as the reference's
-``cfg.Config`` (src/cfg.py:6-97); dataset / registration keys are read when present and otherwise
-ignored (those subsystems are out of scope)."""
+"""Config reader, same attribute names as the reference's ``cfg.Config`` (src/cfg.py:6-97).  The dataset, distortion and
+registration keys are read when present (the dataset loaders use them); a JSON without them gives the hot path's keys only."""
 import json
+import os
+
+import numpy as np
 
 
 class Config:
@@ -20,6 +22,30 @@ class Config:
         if "fx" in cam:
             self.fx, self.fy = cam["fx"], cam["fy"]
             self.cx, self.cy = cam["cx"] - self.mw, cam["cy"] - self.mh
+        ds = config.get("dataset", {})
+        if "format" in ds:
+            self.dataset_format = ds["format"]
+        if "path" in ds:
+            self.dataset_dir = ds["path"]
+            intrinsic_file = os.path.join(self.dataset_dir, "intrinsic/intrinsic_depth.txt")
+            if "fx" not in cam and os.path.exists(intrinsic_file):     # ScanNet (src/cfg.py:38-43)
+                from .utils import load_matrix_from_txt
+                intrinsic = load_matrix_from_txt(intrinsic_file)
+                self.fx, self.fy = intrinsic[0, 0], intrinsic[1, 1]
+                self.cx, self.cy = intrinsic[0, 2] - self.mw, intrinsic[1, 2] - self.mh
+        if "distortion" in cam:
+            self.distortion_array = np.array(cam["distortion"])
+        elif "k1" in cam:
+            self.distortion_array = np.array([cam[k] for k in ("k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")])
+        else:
+            self.distortion_array = None
+        if getattr(self, "dataset_format", None) == "ScanNet" and "use_refined_mask" in ds:
+            self.use_refined_mask = ds["use_refined_mask"]
+            self.load_refined_mask = ds["load_refined_mask"] and self.use_refined_mask
+        reg = config.get("registration", {})
+        for key in ("load_registration_result", "load_pretrained", "weight_root", "multi_init_pose", "eta1", "eta2", "eta3"):
+            if key in reg:
+                setattr(self, key, reg[key])
         self.n_per_optim, self.n_per_optim_bg = rd["n_per_optim"], rd["n_per_optim_bg"]
         self.obj_scale, self.bg_scale = md["obj_scale"], md["bg_scale"]
         self.hidden_feature_size, self.hidden_feature_size_bg = md["hidden_feature_size"], md["hidden_feature_size_bg"]

@@ -85,3 +85,50 @@ def get_transform_from_tensor(inputs):
     RT[:, :3, :3] = quad2rotation(v[:, :4])
     RT[:, :3, 3] = v[:, 4:7]
     return RT[0] if single else RT
+
+
+# ---- dataset helpers (src/utils.py:16-22, :30-51, :69-78, :322-327) ---------------------------------------------------
+class BoundingBox():
+    """An oriented 3-D box as the registration result stores it (bbox3D of inst_dict.pkl): extent, R, center, points3d (8,3)."""
+
+    def __init__(self):
+        super(BoundingBox, self).__init__()
+        self.extent = None
+        self.R = None
+        self.center = None
+        self.points3d = None
+
+
+def enlarge_bbox(bbox, scale, w, h):
+    """[min_x, min_y, max_x, max_y] grown by int(0.5 * scale * size) per side, clipped to [0, w-1] x [0, h-1]; None when either
+    margin is 0.  Arithmetic is whatever the inputs carry: torch tensors (Replica) give float32 margins, ints give double."""
+    assert scale >= 0
+    import numpy as np
+    min_x, min_y, max_x, max_y = bbox
+    margin_x = int(0.5 * scale * (max_x - min_x))
+    margin_y = int(0.5 * scale * (max_y - min_y))
+    if margin_x == 0 or margin_y == 0:
+        return None
+    min_x, max_x = np.clip(min_x - margin_x, 0, w - 1), np.clip(max_x + margin_x, 0, w - 1)
+    min_y, max_y = np.clip(min_y - margin_y, 0, h - 1), np.clip(max_y + margin_y, 0, h - 1)
+    return [int(min_x), int(min_y), int(max_x), int(max_y)]
+
+
+def get_bbox2d_batch(img):
+    """(b, h, w) masks -> (rmins, rmaxs, cmins, cmaxs) int64: first row with a set pixel, one past the last, the same for
+    columns (0 and h / w for an empty mask, as torch.argmax gives)."""
+    b, h, w = img.shape[:3]
+    rows, cols = torch.any(img, axis=2).float(), torch.any(img, axis=1).float()
+    rmins = torch.argmax(rows, dim=1)
+    rmaxs = h - torch.argmax(rows.flip(dims=[1]), dim=1)
+    cmins = torch.argmax(cols, dim=1)
+    cmaxs = w - torch.argmax(cols.flip(dims=[1]), dim=1)
+    return rmins, rmaxs, cmins, cmaxs
+
+
+def load_matrix_from_txt(path, shape=(4, 4)):
+    """whitespace-separated floats of a text file -> float64 array of `shape`"""
+    import numpy as np
+    with open(path) as f:
+        values = [float(v) for v in f.read().split()]
+    return np.array(values).reshape(shape)

@@ -747,6 +747,38 @@ int cnr_mc_emit(const float* vol, int D, float level, int ascent, void* workspac
  * left to right, then + t; 2 <= D <= 512. */
 int cnr_grid_points(int D, float lo, float hi, const float* scale, const float* transform, float* out, void* stream);
 
+/* ---- Frame parsing: the dataset loaders' get_all_frames (src/dataset.py:96-186, :273-430), src/image_transforms.py.
+ * DESIGN.md §3.8.  Label frames: F frames stored (H + 2 edge) x (W + 2 edge), row-major as decoded, of int32 (label_i32 != 0)
+ * or uint16; the analysed region is their centre H x W (the reference's `mw` crop).  A stored value v is id v + id_shift
+ * (id_shift 0 or 1: ScanNet's raw masks); ids outside [0, id_bound) are skipped (the caller checks the bound), id_bound <=
+ * 65537.  Instance table in two steps so that the caller allocates exact outputs:
+ *   workspace >= cnr_frame_instances_workspace_bytes(F, id_bound) (CNR_E_SHAPE for a bad F or id_bound);
+ *   cnr_frame_instances_count writes offsets_out (F + 1) i64 (device): frame f's distinct ids are entries
+ *   [offsets[f], offsets[f + 1]) of a CSR table; the workspace keeps each frame's id bitmap and ranks;
+ *   cnr_frame_instances_emit, same frames and arguments and workspace after _count on the same stream, writes ids (N,) i32 in
+ *   ascending order per frame (np.unique's) and stats (N, CNR_FRAME_NSTAT) i32 per id: pixel count, min and max row, min and
+ *   max column (region coordinates), min and max of `cls` over the id's pixels (0, 0 when cls is NULL; cls has inst's layout).
+ * Integer atomics only: every run is bit-identical. */
+#define CNR_FRAME_NSTAT 7
+int64_t cnr_frame_instances_workspace_bytes(int F, int id_bound);
+int cnr_frame_instances_count(const void* inst, int label_i32, int F, int H, int W, int edge, int id_shift, int id_bound,
+                              void* workspace, int64_t* offsets_out, void* stream);
+int cnr_frame_instances_emit(const void* inst, const void* cls, int label_i32, int F, int H, int W, int edge, int id_shift,
+                             int id_bound, const void* workspace, const int64_t* offsets, int32_t* ids, int32_t* stats, void* stream);
+/* The frame arrays of the reference's sample_dict, (W, H) after its transpose(1, 0), one thread per output pixel:
+ *   obj_mask (F, W, H) i32 = the pixel's id (label frames as above, crop label_edge) when keep[its table entry] != 0, else 0;
+ *   depth_out (F, W, H) f32 = depth (F, H + 2 edge, W + 2 edge) u16 * depth_scale in fp32, NaN -> 0, > max_depth -> 0;
+ *   image_out (F, W, H, 3) u8 = rgb (F, H + 2 edge, W + 2 edge, 3) u8.
+ * workspace and offsets: the table's, after cnr_frame_instances_count on the same label frames; keep (N,) u8. */
+int cnr_frame_finish(const void* inst, int label_i32, int label_edge, const uint16_t* depth, const uint8_t* rgb, int F, int H, int W,
+                     int edge, int id_shift, int id_bound, const void* workspace, const int64_t* offsets, const uint8_t* keep,
+                     float depth_scale, float max_depth, int32_t* obj_mask, float* depth_out, uint8_t* image_out, void* stream);
+/* cv2.resize(src, (dw, dh), INTER_LINEAR) on (F, sh, sw, 3) u8 -> (F, dh, dw, 3) u8: OpenCV's coefficients (half-pixel centres,
+ * edge clamp, 11-bit fixed point) and the rounding of its vectorised vertical pass. */
+int cnr_resize_linear_u8c3(const uint8_t* src, int F, int sh, int sw, uint8_t* dst, int dh, int dw, void* stream);
+/* cv2.resize(src, (dw, dh), INTER_NEAREST) on (F, sh, sw) elements of elem_bytes 2 or 4 -> (F, dh, dw). */
+int cnr_resize_nearest(const void* src, int elem_bytes, int F, int sh, int sw, void* dst, int dh, int dw, void* stream);
+
 /* ---- Mesh evaluation: metric/metrics.py, metric/eval_3D_obj.py:10-39.  DESIGN.md §3.7.  Every call is bit-identical run to
  * run (no atomics; fixed reduction orders).  Points are (n,3) f32, C-contiguous.
  * Nearest-neighbour distance: dist_out[i] = min_j |q_i - p_j| (Euclidean, fp32: (q - p)^2 summed per component, the min of the
