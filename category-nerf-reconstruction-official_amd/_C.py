@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CNR_HIP_LIB") or os.path.join(_HERE, "libcnr_hip.so")
 
 _vp, _i, _i64, _u64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+_d = ctypes.c_double
 
 # name -> argtypes ; every function returns int.  Mirrors include/cnr_hip.h one to one.
 SIGNATURES = {
@@ -103,6 +104,20 @@ SIGNATURES = {
     "cnr_frame_finish": [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp],
     "cnr_resize_linear_u8c3": [_vp, _i, _i, _i, _vp, _i, _i, _vp],
     "cnr_resize_nearest": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    "cnr_unproject_workspace_bytes": [_i, _i],
+    "cnr_unproject_count": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
+    "cnr_unproject_emit": [_vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp],
+    "cnr_points_min_workspace_bytes": [_i64],
+    "cnr_points_min": [_vp, _i64, _vp, _vp, _vp],
+    "cnr_voxel_keys": [_vp, _i64, _vp, _d, _vp, _vp],
+    "cnr_voxel_segments_workspace_bytes": [_i64],
+    "cnr_voxel_segments_count": [_vp, _i64, _vp, _vp, _vp],
+    "cnr_voxel_segments_emit": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cnr_nn_index_workspace_bytes": [_i64, _i64],
+    "cnr_nn_index": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "cnr_icp_workspace_bytes": [_i64, _i64, _i],
+    "cnr_icp_step": [_vp, _i64, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cnr_icp_update": [_vp, _i64, _i, _i, _vp, _vp, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
@@ -164,7 +179,9 @@ def struct_type(name):
 _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_bytes", "cnr_render_loss_workspace_bytes",
               "cnr_dense_bwd_workspace_bytes", "cnr_field_fwd_render_workspace_bytes", "cnr_field_train_workspace_bytes", "cnr_pack_fp8_bytes", "cnr_bg_pack_bytes", "cnr_bg_backward_render_workspace_bytes",
               "cnr_mc_workspace_bytes", "cnr_nn_workspace_bytes", "cnr_dist_stats_workspace_bytes",
-              "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes"}
+              "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes",
+              "cnr_unproject_workspace_bytes", "cnr_points_min_workspace_bytes", "cnr_voxel_segments_workspace_bytes",
+              "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -4,9 +4,12 @@ samples per ray, UniDirsEmbed -> OccupancyMap -> sigmoid(10 sigma) -> non-batch 
 entropies -> the per-object count of rays below a threshold that ranks the objects of a class.
 
 Everything between the rays and the count runs on the device through the drop-in modules (cnr_pe_fwd, the dense
-kernels, cnr_composite_fwd's termination); the reference moves the occupancies to the host and finishes in numpy.  The
-rest of that file (point-cloud accumulation, TEASER++ / ICP alignment) is geometry pre-processing outside the hot path
- and is not here.
+kernels, cnr_composite_fwd's termination); the reference moves the occupancies to the host and finishes in numpy.
+
+The rest of that file for Replica sequences is below it: ``get_all_poses`` (point-cloud accumulation), ``align_poses`` (the
+reference's bookkeeping around a pluggable solver; TEASER++ is not rebuilt, the default is the multi-start GPU ICP
+``IcpSolver``) and ``register_dataset`` (the driver behind ``dataset.get_dataset(cfg, register=True)``), on the kernels of
+csrc/pointcloud.hip.  ScanNet registration is not here.
 """
 import math
 import os
@@ -120,3 +123,276 @@ def get_uncertainty_fields(inst_dict, bbox3d_dict, count_dict, pe_dict, fc_occ_m
         counts = torch.stack([(m < threshold).sum() for m in metrics]).cpu() if metrics else []   # ONE host sync per class
         for obj_id, n in zip(obj_ids, counts):
             count_dict[cls_id][obj_id] = int(n)
+
+
+# ---- point clouds, alignment, sub-categorisation (src/category_registration.py:18-56, :179-324) -------------------------
+# DESIGN.md §3.9.  Replica only; TEASER++ sits behind align_poses(..., solver=), the default solver is IcpSolver.
+def get_all_poses(inst_dict, sample_dict, intrinsic_open3d, name="replica", depth_scale=0.001, max_depth=8.0):
+    """:18-56, Replica branch.  Every instance of every class gets 'pcs': its pixels of all its frames as one cloud at 1 cm.
+    The background (class 0) gets 'pcs' too and 'bbox3D', the oriented box of that cloud with its true extents (no 10 cm
+    floor)."""
+    from . import metrics
+    from .utils import BoundingBox, accumulate_pointcloud
+    if name != "replica":
+        raise NotImplementedError("get_all_poses: ScanNet registration needs open3d's TSDF integration and "
+                                  "geometry_segmentation, which are not part of this package")
+    for cls_id, entries in inst_dict.items():
+        if cls_id != 0:
+            for inst_id, entry in entries.items():
+                entry["pcs"] = accumulate_pointcloud(int(inst_id), entry["frame_info"], sample_dict, intrinsic_open3d)
+            continue
+        cloud = accumulate_pointcloud(0, entries["frame_info"], sample_dict, intrinsic_open3d)
+        to_box, extents = metrics.oriented_bounds(cloud.points)
+        from_box = np.linalg.inv(to_box)
+        box = BoundingBox()
+        box.R, box.center, box.extent = from_box[:3, :3], from_box[:3, 3], extents
+        entries["bbox3D"], entries["pcs"] = box, cloud
+
+
+def _rigid_fit(a, b):
+    """(n,3) -> the rigid (4,4) T minimising |T a - b| (Kabsch, fp64, host) and the largest residual"""
+    ca, cb = a.mean(0), b.mean(0)
+    U, _, Vt = np.linalg.svd((a - ca).T @ (b - cb))
+    R = Vt.T @ np.diag([1.0, 1.0, np.sign(np.linalg.det(Vt.T @ U.T))]) @ U.T
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, cb - R @ ca
+    return T, float(np.abs(a @ R.T + T[:3, 3] - b).max())
+
+
+def icp_device(source, target, T0, max_corr, max_iteration=100):
+    """Point-to-point ICP of (n,3) f32 device `source` against (m,3) f32 device `target` from B starts T0 (B,4,4), all through
+    cnr_icp_step / cnr_icp_update together; open3d's convergence test (1e-6 on fitness and rmse), at most max_iteration
+    updates.  A converged start freezes on the device; the host reads the flags every 10 iterations.
+    -> (T (B,4,4) f64 numpy, state (B,4) numpy: fitness, rmse, flag, updates)"""
+    from . import _C
+    dev = source.device
+    T = torch.from_numpy(np.ascontiguousarray(np.asarray(T0, np.float64).reshape(-1, 4, 4))).to(dev)
+    B, n, m = len(T), len(source), len(target)
+    nbytes = int(_C.load().cnr_icp_workspace_bytes(n, m, B))
+    if nbytes < 0:
+        raise _C.CnrError(f"cnr_icp_step: workspace query failed with {nbytes}")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    state = torch.zeros(B, 4, device=dev, dtype=torch.float64)
+    sums = torch.zeros(B, 17, device=dev, dtype=torch.float64)
+    for it in range(int(max_iteration) + 1):
+        _C.call("cnr_icp_step", source, n, target, m, T, B, float(max_corr), state, ws, sums, None, None)
+        _C.call("cnr_icp_update", sums, n, B, int(max_iteration), T, state)
+        if it % 10 == 9 and bool((state[:, 2] != 0).all()):
+            break
+    return T.cpu().numpy(), state.cpu().numpy()
+
+
+class IcpSolver:
+    """The default solver of align_poses: both clouds down-sampled to `voxel_size`, one start per template that puts the source's
+    oriented box onto the template's, point-to-point ICP (pairs closer than `max_corr`) from every start together.
+
+    The templates must be rigid copies of the first, point for point (align_poses passes the representative rotated by the 24
+    box symmetries S_k, or the representative alone).  Template k's box frame is the first template's box moved by S_k with
+    its axes relabelled by inv(S_k): F_k = S_k F_0 inv(rot S_k).  The 24 starts are then the 24 ways of laying one box onto the
+    other, and all of them run against ONE target cloud in one batch.  Anything else raises a ValueError."""
+
+    FIT_POINTS = 512          # points of the rigid fit, taken with a stride over the whole template
+
+    def __init__(self, voxel_size=0.02, max_corr=0.10, max_iteration=100):
+        self.voxel_size, self.max_corr, self.max_iteration = voxel_size, max_corr, max_iteration
+
+    @staticmethod
+    def _box_frame(pc, what):
+        from .utils import get_bound
+        box = get_bound(pc)
+        if box is None:
+            raise ValueError(f"IcpSolver: the {what} cloud has no 3-D convex hull")
+        F = np.eye(4)
+        F[:3, :3], F[:3, 3] = box.R, box.center
+        return F
+
+    def _copies(self, tm):
+        """tm (B,m,3) -> [S_k] with tm[k] = S_k tm[0]: fitted on a strided subset, the residual checked on every point"""
+        pick = tm[0][::max(1, tm.shape[1] // self.FIT_POINTS)]
+        spread = np.linalg.svd(pick - pick.mean(0), compute_uv=False)
+        if len(pick) < 3 or not spread[1] > 1e-9 * max(spread[0], 1e-300):
+            raise ValueError("IcpSolver: the template is (nearly) a line; no rigid fit between its copies is unique")
+        tol = 1e-5 * (1.0 + float(np.abs(tm[0]).max()))
+        rel = [np.eye(4)]
+        for k in range(1, len(tm)):
+            S, _ = _rigid_fit(pick, tm[k][::max(1, tm.shape[1] // self.FIT_POINTS)])
+            res = float(np.abs(tm[0] @ S[:3, :3].T + S[:3, 3] - tm[k]).max())
+            if not res < tol:
+                raise ValueError(f"IcpSolver: template {k} is no rigid copy of template 0 (residual {res:.3g} m); pass another "
+                                 "solver to align_poses for such templates")
+            rel.append(S)
+        return rel
+
+    def __call__(self, source, templates):
+        from .utils import PointCloud
+        dev = source.device if torch.is_tensor(source) and source.is_cuda else None
+        as_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        src = as_np(source).astype(np.float64)[0].T
+        tm = as_np(templates).astype(np.float64).transpose(0, 2, 1)
+        rel = self._copies(tm)
+        src_ds = PointCloud(src, device=dev).voxel_down_sample(self.voxel_size)
+        tgt_ds = PointCloud(tm[0], device=dev).voxel_down_sample(self.voxel_size)
+        F_s, F_0 = self._box_frame(src_ds, "source"), self._box_frame(tgt_ds, "template")
+        starts = []
+        for S in rel:
+            Q = np.eye(4)
+            Q[:3, :3] = S[:3, :3].T
+            starts.append(F_0 @ Q @ np.linalg.inv(F_s))          # = inv(S) F_k inv(F_s)
+        T, self.last_state = icp_device(src_ds.points_device, tgt_ds.points_device, np.stack(starts), self.max_corr,
+                                        self.max_iteration)
+        T = np.stack([S @ Tk for S, Tk in zip(rel, T)])
+        return torch.from_numpy(T[:, :3, :3].copy()), torch.from_numpy(T[:, :3, 3:].copy())
+
+
+def _mean_nn_distance(points_from, points_to):
+    """mean distance of the points of one device tensor / host array to the nearest point of another (cnr_nn_dist +
+    cnr_dist_stats)"""
+    from . import metrics
+    d = metrics.nn_dist(points_from, points_to)
+    return metrics.dist_stats(d)[0] / len(d)
+
+
+def _unit_scale(T):
+    """(4,4) similarity -> (the same with a pure rotation, its scale)"""
+    out = np.array(T, dtype=np.float64)
+    scale = np.cbrt(np.linalg.det(out[:3, :3]))
+    out[:3, :3] /= scale
+    return out, scale
+
+
+def _best_candidate(source_pts, template_dev, symmetries, R_all, t_all, dev):
+    """the solver's answers (source -> template k) undone by the symmetries, each scored by the mean distance of the moved
+    source to the template -> (T_rel of the lowest score, that score in metres)"""
+    from .utils import transform_pointcloud
+    best = None
+    for S, R, t in zip(symmetries, R_all, t_all):
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = R, np.reshape(t, 3)
+        T = np.linalg.inv(S) @ T
+        moved = torch.from_numpy(transform_pointcloud(source_pts, T)).to(dev)
+        score = _mean_nn_distance(moved, template_dev)
+        if best is None or score < best[1]:          # the first of equal scores, as argmin picks
+            best = (T, score)
+    return best
+
+
+def align_poses(inst_dict, bbox3d_dict, count_dict, pe_dict, fc_occ_map_dict, name="replica", multi_init_pose=True, eta1=0.06,
+                eta2=0.15, eta3=0.12, device="cuda:0", solver=None):
+    """:179-324, the reference's decisions in this package's words.  Classes are taken from bbox3d_dict until it is empty.  Per
+    class the instance with the highest count is the representative: T_obj and bbox3D from its own oriented box.  Every other
+    instance is aligned to it by ``solver(source (1,3,n), templates (B,3,m)) -> (R (B,3,3), t (B,3,1))`` (the signature of
+    TEASER_FPFH_ICP(source).forward(template); default IcpSolver()), where the templates are the representative under the 24
+    box symmetries (one template without multi_init_pose).  The candidate whose moved source lies closest to the template wins;
+    that distance over the source's half extent is the chamfer value c.  c < eta1 accepts, c > eta2 rejects, and in between
+    the opposite distance (template to moved source, over the representative's scale) decides against eta3.  An accepted
+    instance gets T_obj = inv(T_rel) T_obj_representative and its box from get_obb; a rejected one moves, with its entries in
+    all five dicts, to class cls_id + 100 (10000 for ScanNet ids), which is registered like a class on a later pass.
+    -> {"chamfer", "chamfer_opposite", "representative"}: what each decision saw."""
+    from .utils import get_obb, get_pose_from_pointcloud, get_possible_transform_from_bbox, transform_pointcloud
+    solver = IcpSolver() if solver is None else solver
+    dev = torch.device(device)
+    sub_offset = 100 if name == "replica" else 10000
+    per_class = (inst_dict, count_dict, bbox3d_dict, pe_dict, fc_occ_map_dict)
+    symmetries = get_possible_transform_from_bbox() if multi_init_pose else [np.eye(4)]
+    seen = {"chamfer": {}, "chamfer_opposite": {}, "representative": {}}
+    while bbox3d_dict:
+        for cls_id in list(bbox3d_dict.keys()):
+            members = list(bbox3d_dict[cls_id].keys())
+            counts = list(count_dict[cls_id].values())
+            rep_at = int(np.argmax(counts)) if len(counts) > 1 else 0
+            rep_id = members[rep_at]
+            rep = inst_dict[cls_id][rep_id]
+            rep["T_obj"], rep["bbox3D"] = get_pose_from_pointcloud(rep["pcs"], inst_id=rep_id)
+            seen["representative"][cls_id] = rep_id
+            seen["chamfer"][cls_id], seen["chamfer_opposite"][cls_id] = {}, {}
+            others = members[:rep_at] + members[rep_at + 1:]
+            if others:
+                rep_frame, rep_scale = _unit_scale(rep["T_obj"])
+                rep_pts = np.array(rep["pcs"].points)
+                rep_dev = torch.from_numpy(rep_pts).to(dev)
+                templates = torch.from_numpy(np.stack([transform_pointcloud(rep_pts, S).T for S in symmetries])).to(dev)
+            for obj_id in others:
+                src_pts = np.array(inst_dict[cls_id][obj_id]["pcs"].points)
+                half_extent = float((src_pts.max(axis=0) - src_pts.min(axis=0)).max()) / 2
+                R_all, t_all = solver(torch.from_numpy(src_pts.T[None].copy()).to(dev), templates)
+                T_rel, dist = _best_candidate(src_pts, rep_dev, symmetries, R_all.detach().cpu().numpy(),
+                                              t_all.detach().cpu().numpy(), dev)
+                chamfer = dist / half_extent
+                seen["chamfer"][cls_id][obj_id] = chamfer
+                if eta1 <= chamfer <= eta2:
+                    moved = torch.from_numpy(transform_pointcloud(src_pts, T_rel)).to(dev)
+                    opposite = _mean_nn_distance(rep_dev, moved) / rep_scale
+                    seen["chamfer_opposite"][cls_id][obj_id] = opposite
+                    rejected = bool(opposite > eta3)
+                else:
+                    rejected = bool(chamfer > eta2)
+                if rejected:
+                    for d in per_class:
+                        d.setdefault(cls_id + sub_offset, {})[obj_id] = d[cls_id].pop(obj_id)
+                else:
+                    entry = inst_dict[cls_id][obj_id]
+                    entry["T_obj"] = np.linalg.inv(T_rel) @ rep_frame
+                    get_obb(entry)
+            del bbox3d_dict[cls_id]
+    return seen
+
+
+class _RegistrationPickler:
+    """pickle.dump with utils.BoundingBox written under the reference's global name ``utils.BoundingBox``, so that the
+    reference -- and dataset.load_registration_result -- can read the file"""
+
+    @staticmethod
+    def dump(obj, f):
+        import pickle
+        import sys
+        import types
+        from .utils import BoundingBox
+        proxy = type("BoundingBox", (), {"__module__": "utils", "__qualname__": "BoundingBox"})
+        mod = types.ModuleType("utils")
+        mod.BoundingBox = proxy
+
+        class P(pickle.Pickler):
+            def reducer_override(self, o):
+                if type(o) is BoundingBox:
+                    return proxy, (), dict(o.__dict__)
+                return NotImplemented
+
+        saved = sys.modules.get("utils")
+        sys.modules["utils"] = mod
+        try:
+            P(f, protocol=pickle.DEFAULT_PROTOCOL).dump(obj)
+        finally:
+            if saved is None:
+                del sys.modules["utils"]
+            else:
+                sys.modules["utils"] = saved
+
+
+def write_registration_result(inst_dict, path):
+    """the cache file <dataset_dir>/inst_dict.pkl (src/dataset.py:87-88)"""
+    with open(path, "wb") as f:
+        _RegistrationPickler.dump(inst_dict, f)
+
+
+def register_dataset(dataset, cfg, solver=None):
+    """src/dataset.py:72-88 for a Replica dataset whose frames are loaded: get_all_poses -> get_uncertainty_fields ->
+    align_poses, the 'pcs' entries deleted, the result written to <root_dir>/inst_dict.pkl."""
+    if dataset.name != "replica":
+        raise NotImplementedError("registration of ScanNet sequences needs open3d's TSDF integration and "
+                                  "geometry_segmentation, which are not part of this package")
+    if not getattr(cfg, "load_pretrained", False):
+        raise NotImplementedError("get_uncertainty_fields: registration.load_pretrained is false; only per-object checkpoints "
+                                  "under registration.weight_root give the fields that rank a class's instances (the "
+                                  "reference registers nothing in this case, without saying so)")
+    inst_dict = dataset.inst_dict
+    boxes, counts, encoders, fields = {}, {}, {}, {}
+    get_all_poses(inst_dict, dataset.sample_dict, dataset.intrinsic_open3d, name=dataset.name, depth_scale=cfg.depth_scale,
+                  max_depth=cfg.max_depth)
+    get_uncertainty_fields(inst_dict, boxes, counts, encoders, fields, cfg, name=dataset.name, load_pretrained=True)
+    etas = {k: getattr(cfg, k) for k in ("eta1", "eta2", "eta3") if hasattr(cfg, k)}
+    align_poses(inst_dict, boxes, counts, encoders, fields, name=dataset.name,
+                multi_init_pose=getattr(cfg, "multi_init_pose", True), device=dataset._parse_device(), solver=solver, **etas)
+    for cls_id, entries in inst_dict.items():          # the clouds are intermediate results: not part of the cache
+        for entry in ([entries] if cls_id == 0 else entries.values()):
+            del entry["pcs"]
+    write_registration_result(inst_dict, os.path.join(dataset.root_dir, "inst_dict.pkl"))

@@ -4,8 +4,9 @@
 Images are decoded with PIL in a thread pool, uploaded in pinned batches and parsed on the device (csrc/frames.hip): one
 instance table per label frame (ids in np.unique order, pixel count, bounds, class range), then one pass that writes the frame
 arrays in the reference's (W, H) layout.  The per-instance decisions are host logic on the small table, in the reference's
-order and dtypes, quirks included.  Registration is not part of this package: the loaders need the cached
-result ``<dataset_dir>/inst_dict.pkl`` (``registration.load_registration_result``), read with a restricted unpickler."""
+order and dtypes, quirks included.  The loaders read the cached registration result
+``<dataset_dir>/inst_dict.pkl`` (``registration.load_registration_result``) with a restricted unpickler; without one,
+``get_dataset(cfg, register=True)`` runs category registration for Replica (category_registration.py)."""
 import glob
 import io
 import os
@@ -24,11 +25,13 @@ BATCH = 16                  # frames per upload
 DECODE_WORKERS = 16
 
 
-def get_dataset(cfg):
+def get_dataset(cfg, register=False):
+    """register=True: a Replica dataset without a usable cache runs category registration (category_registration.
+    register_dataset) and writes <dataset_dir>/inst_dict.pkl; the default raises NotImplementedError there, as before."""
     if cfg.dataset_format == "Replica":
-        return Replica(cfg)
+        return Replica(cfg, register=register)
     if cfg.dataset_format == "ScanNet":
-        return ScanNet(cfg)
+        return ScanNet(cfg, register=register)
     raise ValueError("Dataset format {} not found".format(cfg.dataset_format))
 
 
@@ -87,14 +90,25 @@ def load_registration_result(path):
 
 
 def _load_inst_dict(dataset, cfg):
+    register = getattr(dataset, "register", False)
     result_file = os.path.join(dataset.root_dir, "inst_dict.pkl")
     if getattr(cfg, "load_registration_result", False) and os.path.exists(result_file):
         dataset.inst_dict = load_registration_result(result_file)
         return
+    if register and dataset.name == "replica":
+        from . import category_registration
+        category_registration.register_dataset(dataset, cfg)
+        return
+    if dataset.name == "replica":
+        raise NotImplementedError(
+            f"{result_file}: no cached registration result (registration.load_registration_result = "
+            f"{getattr(cfg, 'load_registration_result', None)}).  Category-level registration (get_all_poses, "
+            "get_uncertainty_fields, align_poses) runs only on request: get_dataset(cfg, register=True)")
     raise NotImplementedError(
         f"{result_file}: no cached registration result (registration.load_registration_result = "
-        f"{getattr(cfg, 'load_registration_result', None)}).  Category-level registration (get_all_poses, "
-        "get_uncertainty_fields, align_poses with TEASER++) is not part of this package; run it with the reference once")
+        f"{getattr(cfg, 'load_registration_result', None)}).  Category-level registration of ScanNet sequences (open3d's TSDF "
+        "integration and geometry_segmentation, align_poses with TEASER++) is not part of this package; run it with the "
+        "reference once")
 
 
 # ---- decoding ----------------------------------------------------------------------------------------------------------
@@ -226,8 +240,9 @@ class _Base:
 
 
 class Replica(_Base):
-    def __init__(self, cfg):
+    def __init__(self, cfg, register=False):
         self.name = "replica"
+        self.register = register
         self.device = cfg.data_device
         self.root_dir = cfg.dataset_dir
         self.Twc = np.loadtxt(os.path.join(self.root_dir, "traj_w_c.txt"), delimiter=" ").reshape([-1, 4, 4])
@@ -301,8 +316,9 @@ def _sorted_by_stem(pattern):
 
 
 class ScanNet(_Base):
-    def __init__(self, cfg):
+    def __init__(self, cfg, register=False):
         self.name = "scannet"
+        self.register = register
         self.device = cfg.data_device
         self.root_dir = cfg.dataset_dir
         j = lambda *p: os.path.join(self.root_dir, *p)

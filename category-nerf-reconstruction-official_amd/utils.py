@@ -5,6 +5,7 @@ registers them as a new param group, and returns ``(fmodel, params, buffers)`` s
 ``functorch.vmap(fmodel)(params, buffers, *stacked_inputs)`` -- the exact call at train.py:154-155 --
 lands in the class-batched HIP kernels through the Functions' ``vmap`` rules (ops.py).
 """
+import numpy as np
 import torch
 from torch.func import functional_call, stack_module_state
 
@@ -132,3 +133,233 @@ def load_matrix_from_txt(path, shape=(4, 4)):
     with open(path) as f:
         values = [float(v) for v in f.read().split()]
     return np.array(values).reshape(shape)
+
+
+# ---- point clouds for category registration (src/utils.py:189-366) -----------------------------------------------------
+# DESIGN.md §3.9.  The reference builds these on open3d / trimesh; here the clouds live on the device and the unprojection,
+# voxel down-sample and nearest-neighbour work are kernels of csrc/pointcloud.hip.
+def _cuda_device(device=None):
+    if device is not None and torch.device(device).type == "cuda":
+        return torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _workspace(nbytes, dev, what):
+    from . import _C
+    nbytes = int(nbytes)
+    if nbytes < 0:
+        raise _C.CnrError(f"{what}: workspace query failed with {nbytes}")
+    return torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+
+
+def voxel_down_sample_device(points, colors, voxel_size):
+    """open3d's voxel_down_sample on (n,3) f32 device points (colors (n,3) f32 or None): voxel index floor((p - (min - v / 2)) / v)
+    per axis in fp64, the mean of each voxel's points and colours in fp64, summed in input order.
+    -> (points (m,3) f64, colors (m,3) f64 or None, keys (m,) i64, counts (m,) i64), voxels in ascending (ix, iy, iz)."""
+    from . import _C
+    lib = _C.load()
+    points = points.contiguous()
+    n, dev = len(points), points.device
+    if n == 0:
+        raise ValueError("voxel_down_sample of an empty point cloud")
+    if not voxel_size > 0:
+        raise ValueError("voxel_size must be positive")
+    mn = torch.empty(3, device=dev, dtype=torch.float32)
+    _C.call("cnr_points_min", points, n, _workspace(lib.cnr_points_min_workspace_bytes(n), dev, "cnr_points_min"), mn)
+    keys = torch.empty(n, device=dev, dtype=torch.int64)
+    _C.call("cnr_voxel_keys", points, n, mn, float(voxel_size), keys)
+    skeys, perm = torch.sort(keys, stable=True)
+    ws = _workspace(lib.cnr_voxel_segments_workspace_bytes(n), dev, "cnr_voxel_segments")
+    cnt = torch.empty(2, device=dev, dtype=torch.int64)
+    _C.call("cnr_voxel_segments_count", skeys, n, ws, cnt[:1])
+    cnt[1] = skeys[0]
+    m, first = (int(v) for v in cnt.cpu())
+    if first < 0:
+        raise ValueError("voxel_down_sample: non-finite points, or more than 2^21 voxels along an axis")
+    out_p = torch.empty(m, 3, device=dev, dtype=torch.float64)
+    out_c = torch.empty(m, 3, device=dev, dtype=torch.float64) if colors is not None else None
+    out_k = torch.empty(m, device=dev, dtype=torch.int64)
+    out_n = torch.empty(m, device=dev, dtype=torch.int64)
+    _C.call("cnr_voxel_segments_emit", skeys, perm, points, colors.contiguous() if colors is not None else None, n, ws,
+            out_p, out_c, out_k, out_n)
+    return out_p, out_c, out_k, out_n
+
+
+class PointCloud:
+    """The part of open3d.geometry.PointCloud that registration uses, on the device: ``points`` / ``colors`` (numpy float64
+    views of the fp32 device arrays, as np.asarray(pcd.points) gives), ``+=``, ``voxel_down_sample`` and
+    ``compute_point_cloud_distance``."""
+
+    def __init__(self, points=None, colors=None, device=None):
+        dev = points.device if torch.is_tensor(points) and points.is_cuda else _cuda_device(device)
+        as_dev = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(
+            device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        self.points_device = as_dev(points) if points is not None else torch.zeros(0, 3, device=dev)
+        self.colors_device = as_dev(colors) if colors is not None else None
+        if self.colors_device is not None and len(self.colors_device) != len(self.points_device):
+            raise ValueError("a colour per point")
+
+    def __len__(self):
+        return len(self.points_device)
+
+    @property
+    def points(self):
+        return self.points_device.double().cpu().numpy()
+
+    @property
+    def colors(self):
+        return self.colors_device.double().cpu().numpy() if self.colors_device is not None else np.zeros((0, 3))
+
+    def __iadd__(self, other):
+        both = self.colors_device is not None and other.colors_device is not None and len(self) and len(other)
+        if len(self) == 0:
+            self.points_device, self.colors_device = other.points_device, other.colors_device
+            return self
+        if len(other) == 0:
+            return self
+        self.colors_device = torch.cat([self.colors_device, other.colors_device.to(self.points_device.device)]) if both else None
+        self.points_device = torch.cat([self.points_device, other.points_device.to(self.points_device.device)])
+        return self
+
+    def voxel_down_sample(self, voxel_size):
+        p, c, _, _ = voxel_down_sample_device(self.points_device, self.colors_device, voxel_size)
+        return PointCloud(p.float(), c.float() if c is not None else None)
+
+    def compute_point_cloud_distance(self, other):
+        """per point of this cloud the distance to the nearest point of `other` -> (n,) f32 device tensor"""
+        from . import metrics
+        return metrics.nn_dist(self.points_device, other.points_device)
+
+
+def _intrinsics(intrinsic):
+    if hasattr(intrinsic, "fx"):
+        return float(intrinsic.fx), float(intrinsic.fy), float(intrinsic.cx), float(intrinsic.cy)
+    K = np.asarray(intrinsic.intrinsic_matrix if hasattr(intrinsic, "intrinsic_matrix") else intrinsic, np.float64)
+    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+
+def _unproject_frames(frames, inst_ids, intrinsic, dev):
+    """frames: [(image (W,H,3) u8, depth (W,H) f32, obj_mask (W,H) i32, T_WC (4,4))], one instance id each -> PointCloud of all
+    frames' kept pixels in frame order.  One read-back (the counts) for all frames."""
+    from . import _C
+    lib = _C.load()
+    fx, fy, cx, cy = _intrinsics(intrinsic)
+    up = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
+    staged, counts = [], torch.zeros(max(len(frames), 1), device=dev, dtype=torch.int64)
+    for k, ((image, depth, mask, T_WC), inst_id) in enumerate(zip(frames, inst_ids)):
+        d, m, im = up(depth, torch.float32), up(mask, torch.int32), up(image, torch.uint8)
+        W, H = d.shape
+        if m.shape != (W, H) or im.shape != (W, H, 3):
+            raise ValueError("depth (W,H), obj_mask (W,H) and image (W,H,3) of one frame")
+        ws = _workspace(lib.cnr_unproject_workspace_bytes(W, H), dev, "cnr_unproject")
+        _C.call("cnr_unproject_count", d, m, W, H, int(inst_id), ws, counts[k:k + 1])
+        T = torch.from_numpy(np.ascontiguousarray(np.asarray(T_WC, np.float64).reshape(4, 4))).to(dev)
+        staged.append((d, m, im, W, H, int(inst_id), T, ws))
+    counts = counts.cpu().numpy()[:len(frames)]
+    total = int(counts.sum())
+    points = torch.empty(total, 3, device=dev, dtype=torch.float32)
+    colors = torch.empty(total, 3, device=dev, dtype=torch.float32)
+    o = 0
+    for (d, m, im, W, H, inst_id, T, ws), c in zip(staged, counts):
+        if c:
+            _C.call("cnr_unproject_emit", d, m, im, W, H, inst_id, fx, fy, cx, cy, T, ws, points[o:o + c], colors[o:o + c])
+        o += int(c)
+    return PointCloud(points, colors)
+
+
+def unproject_colored_pointcloud(rgb, depth, intrinsic_open3d, T_CW, device=None):
+    """src/utils.py:341-351: the pixels with 0 < depth <= 8.0 (depth_trunc) of one (W,H) frame as a coloured cloud in the world
+    frame, inv(T_CW) . ((u - cx) z / fx, (v - cy) z / fy, z, 1).  Points come in the memory order of the (W,H) arrays (u major);
+    open3d walks its transposed image v major."""
+    depth = depth if torch.is_tensor(depth) else np.asarray(depth)
+    mask = torch.ones(tuple(depth.shape), dtype=torch.int32)
+    return _unproject_frames([(rgb, depth, mask, np.linalg.inv(np.asarray(T_CW, np.float64)))], [1], intrinsic_open3d,
+                             _cuda_device(device))
+
+
+def accumulate_pointcloud(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size=0.01, device=None):
+    """src/utils.py:189-210: the instance's pixels of every frame of inst_info_list, unprojected into one cloud (frame order,
+    then pixel order), then voxel_down_sample(voxel_size).  sample['T'] is the camera-to-world pose the kernel wants."""
+    frames = []
+    for entry in inst_info_list:
+        s = frame_samples[entry["frame"]]
+        if s["frame_id"] != entry["frame"]:
+            raise ValueError(f"frame {entry['frame']}: sample_dict holds frame {s['frame_id']} under that key")
+        frames.append((s["image"], s["depth"], s["obj_mask"], s["T"]))
+    cloud = _unproject_frames(frames, [inst_id] * len(frames), intrinsic_open3d, _cuda_device(device))
+    if len(cloud) == 0:
+        raise ValueError(f"instance {inst_id}: no pixel with a valid depth in its {len(frames)} frames")
+    return cloud.voxel_down_sample(voxel_size)
+
+
+def transform_pointcloud(cloud, T_rel):
+    """(n,3) points -> R p + t for the (4,4) transform T_rel, (n,3) (src/utils.py:361-366)"""
+    T = np.asarray(T_rel)
+    return np.asarray(cloud) @ T[:3, :3].T + T[:3, 3]
+
+
+MIN_BOX_EXTENT = 0.10       # a box is at least 10 cm along every edge (what the renderer samples)
+
+
+def _host_points(cloud):
+    return np.array(cloud.points if hasattr(cloud, "points") else cloud, dtype=np.float64).reshape(-1, 3)
+
+
+def get_bound(inst_pcs):
+    """src/utils.py:249-268: the oriented box of a cloud as a BoundingBox (R and center place the box in the world, extent >=
+    10 cm), from metrics.oriented_bounds where the reference calls trimesh's.  None, after a message, when the cloud spans no
+    volume (fewer than 4 points, or flat to rounding: where qhull refuses a 3-D hull)."""
+    from . import metrics
+    pts = _host_points(inst_pcs)
+    spread = np.linalg.svd(pts - pts.mean(0), compute_uv=False) if len(pts) >= 4 else np.zeros(3)
+    if not spread[2] > 1e-12 * max(spread[0], 1e-300):
+        print("fail to get initial pose from instance point cloud")
+        return None
+    to_box, extents = metrics.oriented_bounds(pts)
+    from_box = np.linalg.inv(to_box)
+    box = BoundingBox()
+    box.R, box.center = from_box[:3, :3], from_box[:3, 3]
+    box.extent = np.maximum(np.asarray(extents, np.float64), MIN_BOX_EXTENT)
+    return box
+
+
+def get_obb(inst_info):
+    """src/utils.py:270-284: inst_info['bbox3D'] = the box of inst_info['pcs'] in the frame of inst_info['T_obj'] with its
+    scale taken out: centred on that frame's origin, so each extent is twice the larger of the two reaches along its axis, at
+    least 10 cm.  T_obj's 3 x 3 part becomes that rotation times half the largest extent."""
+    pose = inst_info["T_obj"]
+    frame = np.array(pose, dtype=np.float64)
+    frame[:3, :3] /= np.cbrt(np.linalg.det(frame[:3, :3]))
+    local = transform_pointcloud(_host_points(inst_info["pcs"]), np.linalg.inv(frame))
+    reach = np.maximum(local.max(axis=0), -local.min(axis=0))
+    box = BoundingBox()
+    box.R, box.center = frame[:3, :3], frame[:3, 3]
+    box.extent = np.maximum(2.0 * reach, MIN_BOX_EXTENT)
+    pose[:3, :3] = frame[:3, :3] * (box.extent.max() / 2.0)
+    inst_info["bbox3D"] = box
+
+
+def get_pose_from_pointcloud(inst_pcs, inst_id=None):
+    """src/utils.py:286-296: (T_obj, bbox3D) of a cloud: its oriented box, and the similarity [R * max(extent) / 2 | center].
+    A cloud without a 3-D hull raises a ValueError naming the instance (the reference fails on None.extent)."""
+    box = get_bound(inst_pcs)
+    if box is None:
+        raise ValueError(f"instance {inst_id}: its point cloud has no 3-D convex hull, so no pose can be taken from it")
+    T_obj = np.eye(4)
+    T_obj[:3, :3] = box.R * (box.extent.max() / 2.0)
+    T_obj[:3, 3] = box.center
+    return T_obj, box
+
+
+def get_possible_transform_from_bbox():
+    """src/utils.py:298-320: the 24 proper rotations that map a box onto itself, as (4,4) transforms: for every ordered pair of
+    axes (x, y), the four sign choices (+,+), (-,+), (+,-), (-,-), z = x cross y."""
+    from itertools import permutations
+    transform_list = []
+    for ax, ay in permutations([0, 1, 2], 2):
+        for sx, sy in ((1, 1), (-1, 1), (1, -1), (-1, -1)):
+            x_axis, y_axis = sx * np.eye(3)[ax], sy * np.eye(3)[ay]
+            transform = np.eye(4)
+            transform[:3, :3] = np.vstack([x_axis, y_axis, np.cross(x_axis, y_axis)]).T
+            transform_list.append(transform)
+    return transform_list

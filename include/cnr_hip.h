@@ -811,6 +811,56 @@ int cnr_clip_box_count(const float* verts, const int* faces, int64_t F, const do
 int cnr_clip_box_emit(const float* verts, const int* faces, int64_t F, const double* planes, void* workspace, float* tris,
                       void* stream);
 
+/* ---- Category registration on point clouds: src/category_registration.py, src/utils.py:189-366.  DESIGN.md §3.9.  The
+ * contracts of the metric kernels hold: caller-allocated outputs, workspace queries, no float atomics, fixed reduction
+ * orders (bit-identical run to run).  Points and colours are (n,3) f32, C-contiguous.
+ * Unprojection of one frame as sample_dict stores it: depth (W,H) f32, obj_mask (W,H) i32, image (W,H,3) u8.  A pixel is kept
+ * when obj_mask == inst_id and 0 < depth <= 8.0; kept pixels are emitted in the arrays' memory order (i = u H + v: column by
+ * column of the image).  point = T_WC (4,4 row-major f64, device) . ((u - cx) z / fx, (v - cy) z / fy, z, 1) in fp64, rounded
+ * once; colour = u8 / 255.  cnr_unproject_count writes count_out (1,) i64 (device) and keeps per-workgroup offsets in
+ * workspace (>= cnr_unproject_workspace_bytes(W, H)); cnr_unproject_emit, with the same inputs and workspace after it on the
+ * same stream, writes count points and colours at the pointers given (the caller's cursor into a growing buffer). */
+int64_t cnr_unproject_workspace_bytes(int W, int H);
+int cnr_unproject_count(const float* depth, const int* obj_mask, int W, int H, int inst_id, void* workspace, int64_t* count_out,
+                        void* stream);
+int cnr_unproject_emit(const float* depth, const int* obj_mask, const uint8_t* image, int W, int H, int inst_id, double fx,
+                       double fy, double cx, double cy, const double* T_WC, void* workspace, float* points, float* colors,
+                       void* stream);
+/* open3d's voxel_down_sample in four steps.  cnr_points_min: min_out (3,) f32 = the per-axis minimum.  cnr_voxel_keys:
+ * keys[i] = (ix << 42) | (iy << 21) | iz with i* = floor((double(p) - (double(min) - voxel / 2)) / voxel), or -1 when an index
+ * is outside [0, 2^21) or not a number.  The caller sorts the keys (stable) and passes the sorted keys and the permutation:
+ * cnr_voxel_segments_count writes the number of distinct keys to count_out (1,) i64 (device); cnr_voxel_segments_emit writes
+ * per distinct key, in ascending key order = ascending (ix, iy, iz), the fp64 mean of its points (and colours, unless colors
+ * is NULL) summed in input order, the key and the number of points. */
+int64_t cnr_points_min_workspace_bytes(int64_t n);
+int cnr_points_min(const float* points, int64_t n, void* workspace, float* min_out, void* stream);
+int cnr_voxel_keys(const float* points, int64_t n, const float* min_xyz, double voxel, int64_t* keys, void* stream);
+int64_t cnr_voxel_segments_workspace_bytes(int64_t n);
+int cnr_voxel_segments_count(const int64_t* sorted_keys, int64_t n, void* workspace, int64_t* count_out, void* stream);
+int cnr_voxel_segments_emit(const int64_t* sorted_keys, const int64_t* perm, const float* points, const float* colors, int64_t n,
+                            void* workspace, double* out_points, double* out_colors, int64_t* out_keys, int64_t* out_counts,
+                            void* stream);
+/* cnr_nn_dist with the index: dist_out[i] = min_j |q_i - p_j| in cnr_nn_dist's arithmetic, index_out[i] = the lowest j that
+ * attains it.  nr < 2^31. */
+int64_t cnr_nn_index_workspace_bytes(int64_t nq, int64_t nr);
+int cnr_nn_index(const float* q, int64_t nq, const float* p, int64_t nr, float* dist_out, int* index_out, void* workspace,
+                 void* stream);
+/* One point-to-point ICP evaluation for B candidate transforms T (B,4,4 row-major f64, device) of one source cloud against one
+ * target cloud.  Per candidate b: a_i = f32(T_b . src_i) (fp64 fused multiply-adds, rounded once), j = its exact nearest target
+ * (ties: lowest index), d = their fp32 distance; over the pairs with d < max_corr, in a fixed order and in fp64, sums (B,17) =
+ * [pairs, sum d^2, sum a (3), sum b (3), sum a b^T (9, row-major)].  dist_out / index_out (B, n_src), when not NULL, receive
+ * d and j of every source point.  state (B,4) f64 or NULL: candidates whose state[b][2] != 0 are skipped: their sums and
+ * their rows of dist_out / index_out are left as the caller's buffers held them.  workspace >= cnr_icp_workspace_bytes(n_src, n_tgt, B); B <= 65535.
+ * cnr_icp_update, per running candidate: fitness = pairs / n_src and rmse = sqrt(sum d^2 / pairs) go to state[b][0..1]; when
+ * both moved by less than 1e-6 since the last call (open3d's test) state[b][2] = 1; with fewer than 3 pairs state[b][2] = 2;
+ * otherwise T_b <- dT . T_b for the rigid dT = (R, t) that minimises sum |R a + t - b|^2 (R = V diag(1,1,det(V U^T)) U^T of
+ * sum (a - ca)(b - cb)^T = U S V^T, computed as Horn's quaternion), state[b][3] += 1, and state[b][2] = 3 once that reaches
+ * max_iter.  A fresh state is all zeros. */
+int64_t cnr_icp_workspace_bytes(int64_t n_src, int64_t n_tgt, int B);
+int cnr_icp_step(const float* src, int64_t n_src, const float* tgt, int64_t n_tgt, const double* T, int B, float max_corr,
+                 const double* state, void* workspace, double* sums, float* dist_out, int* index_out, void* stream);
+int cnr_icp_update(const double* sums, int64_t n_src, int B, int max_iter, double* T, double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
