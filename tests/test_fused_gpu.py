@@ -5,6 +5,7 @@ import torch
 
 from conftest import Golden, golden_names, rel_l2
 from oracle import ref_cpu as O
+from f16_emulation import _emulated_f16_step, _ste_half, _torch_loss, emulated_grads  # noqa: F401  (re-exported)
 
 pytestmark = pytest.mark.gpu
 NORTH_STAR_TOL = 1e-3
@@ -168,121 +169,132 @@ def _fused_step(cnr, g, dev, grad_scale, max_blocks=0, precise=False):
     return dict(loss=loss, trunk=trunk, lat=lat, B=B, shape=shape, tex=tex)
 
 
-def _ste_half(x):
-    """round to f16 in the forward, identity in the backward (what an f16 MFMA operand is)."""
-    return x + (x.half().float() - x).detach()
+def _kernel_grad_tensors(cnr, g, out):
+    """_fused_step's gradients under the reference's tensor names"""
+    got, off = {}, 0
+    for n, o, i in cnr.ops.TRUNK_LAYERS:
+        for kind, cnt, shp in (("weight", o * i, (g.C, o, i)), ("bias", o, (g.C, o))):
+            got[n + "." + kind] = out["trunk"].grad[:, off:off + cnt].reshape(shp)
+            off += cnt
+    for n in cnr.ops.LATENT_LAYERS:
+        got[n + ".weight"], got[n + ".bias"] = out["lat"][n][0].grad, out["lat"][n][1].grad
+    got["B"], got["shape_codes"], got["texture_codes"] = out["B"].grad, out["shape"].grad, out["tex"].grad
+    return got
 
 
-def _emulated_f16_step(cnr, g, dev):
-    """The fused kernels' arithmetic restated with torch ops: fp32 PE -> f16 operands (weights, PE features,
-    post-ReLU activations) -> fp32 accumulate, fp32 sigma head, latent layers folded into bias rows.
-    Its autograd gradient is what an exact-arithmetic backward of the f16 forward would return; it shares
-    the kernel's ReLU masks, which the fp32 reference does not (see test_fused_backward_vs_fp32_reference)."""
-    q = _ste_half
-    mlp = g.mlp()
-    C, n_obj = g.C, g.n_obj
-    P = {k: v.clone().requires_grad_() for k, v in mlp.items()}
-    B = g.t("B").clone().requires_grad_()
-    shape = g.t("shape_codes").clone().requires_grad_()
-    tex = g.t("texture_codes").clone().requires_grad_()
-    idx = g.t("indices")
-    W = lambda n: P[n + ".weight"]
-    b = lambda n: P[n + ".bias"][:, None, None, :]
-    lin = lambda n, x: torch.matmul(x, q(W(n)).transpose(-1, -2)[:, None])
-    # differentiable PE (oracle formula, on device)
-    t = g.t("pts") / g.scale
-    proj = torch.matmul(t, B.transpose(-1, -2)[:, None])
-    bands = 2.0 ** torch.arange(6, device=dev, dtype=torch.float32)
-    xb = (proj[..., None, :] * bands[:, None]).reshape(*proj.shape[:-1], -1)
-    e = torch.cat([t, torch.sin(xb * torch.pi)], dim=-1)
-    e1, e2 = q(e[..., :87]), q(e[..., 87:])
-    zrow = {}
-    for i, n in enumerate(cnr.ops.LATENT_LAYERS):
-        code = tex if i == 3 else shape
-        zrow[i] = torch.relu(torch.baddbmm(P[n + ".bias"][:, None, :], code, P[n + ".weight"].transpose(1, 2)))
-    gather = lambda zr: torch.stack([zr[c][idx[c]] for c in range(C)])[:, :, None, :]   # (C,R,1,32)
-    fold = lambda n, zr, cols=None: torch.matmul(gather(zr), (W(n) if cols is None else W(n)[:, :, :cols]).transpose(-1, -2)[:, None])
-    a0 = q(torch.relu(lin("encoding_xyz.0", e1) + b("encoding_xyz.0")))
-    a1 = q(torch.relu(lin("shape_layer_1.0", a0) + fold("shape_layer_1.0", zrow[0]) + b("shape_layer_1.0")))
-    Wc = q(W("cat_layer.0"))
-    pre2 = torch.matmul(a1, Wc[:, :, :32].transpose(-1, -2)[:, None]) + torch.matmul(e1, Wc[:, :, 32:].transpose(-1, -2)[:, None]) \
-        + fold("cat_layer.0", zrow[1], 32) + b("cat_layer.0")
-    a2 = q(torch.relu(pre2))
-    a3 = q(torch.relu(lin("shape_layer_2.0", a2) + fold("shape_layer_2.0", zrow[2]) + b("shape_layer_2.0")))
-    y4 = lin("encoding_shape", a3) + b("encoding_shape")
-    sig = (torch.matmul(y4, W("sigma.0").transpose(-1, -2)[:, None]) + b("sigma.0")).squeeze(-1) * 10.0
-    Wv = q(W("encoding_viewdir.0"))
-    a5 = q(torch.relu(torch.matmul(q(y4), Wv[:, :, :32].transpose(-1, -2)[:, None])
-                      + torch.matmul(e2, Wv[:, :, 32:].transpose(-1, -2)[:, None]) + b("encoding_viewdir.0")))
-    a6 = q(torch.relu(lin("texture_layer_1.0", a5) + fold("texture_layer_1.0", zrow[3]) + b("texture_layer_1.0")))
-    a7 = q(torch.relu(lin("rgb.0", a6) + b("rgb.0")))
-    rgb = torch.sigmoid(lin("rgb.2", a7) + b("rgb.2"))
-    return P, B, shape, tex, sig, rgb
+def _trunk_rel_l2(cnr, got, ref):
+    """relative L2 of the whole trunk gradient (the twenty tensors of TRUNK_LAYERS as one vector)"""
+    num = den = 0.0
+    for n, _, _ in cnr.ops.TRUNK_LAYERS:
+        for k in (n + ".weight", n + ".bias"):
+            num += float((got[k] - ref[k]).double().pow(2).sum()); den += float(ref[k].double().pow(2).sum())
+    return (num / den) ** 0.5
 
 
-def _torch_loss(sig, rgb, g):
-    """loss.py:18-74 with device tensors (plain torch; test-side restatement of the oracle's step_batch_loss)."""
-    mask_obj = g.t("labels") != 0
-    mask_sem = g.t("labels") != 2
-    md = g.t("depth_mask") & mask_obj
-    occ = torch.sigmoid(sig)
-    free = torch.cat([torch.ones_like(occ[..., :1]), (1.0 - occ + 1e-10)[..., :-1]], -1)
-    term = occ * torch.cumprod(free, -1)
-    z = g.t("z")
-    depth = (term * z).sum(-1)
-    var = (term * (z - depth[..., None]) ** 2).sum(-1).detach()
-    col = (term[..., None] * rgb).sum(-2)
-    opa = term.sum(-1)
+# the two emulations' trunk gradients must differ by this much (4 x the 5e-3 trunk bar) for a fixture to tell the kernel
+# variants apart: a kernel within 5e-3 of its own emulation is then >= 1.5e-2 from the other one, hence the factor 3
+DISCRIMINATION_MIN, DISCRIMINATION_FACTOR = 2e-2, 3.0
 
-    def red(l, m, v=None):
-        if (m.sum(-1) == 0).any():
-            return torch.zeros(l.shape[0], device=l.device)
-        if v is not None:
-            l = l / (torch.sqrt(v) + 1e-4)
-        return l.sum(-1) / (m.sum(-1) + 1e-10)
-    ld = red((depth - g.t("gt_depth")).abs() * md, md, var)
-    lc = red((col - g.t("gt_rgb")).abs().sum(-1) * mask_obj, mask_obj)
-    lo = red((opa - mask_obj.float()).abs() * mask_sem, mask_sem)
-    return (ld + 5.0 * lc + 10.0 * lo).sum()
+
+# test_fused_backward_vs_emulated_f16's named exceptions to the 3e-2 per-tensor bar: {(fixture, variant): {tensor: bar}}.  Each is ONE
+# near-zero ReLU unit of the colour branch (plain f16 in both variants) that takes one side of zero in the kernel's MFMA summation
+# order and the other in torch.matmul's; every entry of the second is a tensor MEASURED over 3e-2, at <= 1.5 x its own measured value,
+# and every other tensor of that case stays at 3e-2.
+#  * plain_f16, s1_c1_r64_s16_l256 (the exception this test has always had: 5e-2 on that fixture): a texture_layer_1.0 unit whose
+#    pre-activation is ~1e-6; 3.3e-2 on that layer's weight.  The precise kernel measures 2.6e-3 there and gets none.
+#  * precise_geometry, s0_c2_r64_s16_l32 (two classes x 64 rays, L = 32): rgb.0 unit 6 of class 0, ray 8, sample 0 has the
+#    pre-activation +1.9e-5 in the emulation (a sum of 32 products of f16 a6 entries, themselves re-rounded fp32 sums: one f16 ulp
+#    of one a6 entry moves it by more) and is off in the kernel.  Inverting that ONE mask in the emulation takes the worst tensor
+#    from 7.9e-2 to 2.1e-3.  Measured: texture_codes 7.91e-2, texture_latent_layer_1.0 weight 6.69e-2 / bias 6.17e-2,
+#    encoding_viewdir.0 weight 5.71e-2 / bias 5.24e-2, texture_layer_1.0 weight 4.10e-2 / bias 5.04e-2, B 3.52e-2 (through d e2),
+#    rgb.0.bias 3.20e-2; rgb.0.weight 2.32e-2 and the rest are under the bar.
+NAMED_EXCEPTIONS = {
+    ("s1_c1_r64_s16_l256", "plain_f16"): {None: 5e-2},                       # None: every tensor of the case
+    ("s0_c2_r64_s16_l32", "precise_geometry"): {
+        "texture_codes": 1.1e-1, "texture_latent_layer_1.0.weight": 9.4e-2, "texture_latent_layer_1.0.bias": 8.6e-2,
+        "encoding_viewdir.0.weight": 8.0e-2, "encoding_viewdir.0.bias": 7.3e-2, "texture_layer_1.0.weight": 5.7e-2,
+        "texture_layer_1.0.bias": 7.0e-2, "B": 4.9e-2, "rgb.0.bias": 4.5e-2},
+}
 
 
 @pytest.mark.parametrize("name", golden_names())
 def test_fused_backward_vs_emulated_f16(cnr, dev, name, bwd_variant):
-    """Kernel gradients == autograd of the torch emulation of the same f16 pipeline (same ReLU masks up to
-    fp32 summation order): 5e-3 relative L2 on the whole trunk gradient, 2e-2 per tensor (one unit whose
-    pre-activation is ~1e-6 can still flip between MFMA and torch.matmul summation order: 1.5e-2 on the
-    texture branch of the 120x10 fixture, tools/debug_fused_grads.py); the rest is f16 rounding of dPre."""
+    """Kernel gradients == autograd of the torch emulation of the SAME pipeline (tests/f16_emulation.py: plain f16 operands for
+    plain_f16; for precise_geometry the three-product geometry branch whose backward reads f16(W), f16(x) of that forward --
+    pinned on the CPU by tests/test_emulation_host.py), same ReLU masks up to fp32 summation order: loss 1e-4, 5e-3 relative L2 on
+    the whole trunk gradient, 3e-2 per tensor (one unit whose pre-activation is ~1e-6 can still flip between MFMA and torch.matmul
+    summation order); the rest is f16 rounding of dPre.  Both variants meet the same bars; each has one named fixture where such a
+    flip is measured over 3e-2 (NAMED_EXCEPTIONS above).
+    Where the two emulations' trunk gradients are more than 2e-2 apart (edge_empty_mask: 2.7e-2), the kernel must also be three
+    times closer to its own emulation than to the other one: the pairing of kernel variant and arithmetic is a tested fact.
+    Measured on MI355X ("[emu]" lines; trunk / worst tensor):
+                            plain_f16                                   precise_geometry
+      edge_empty_mask       7.0e-4 / B 1.8e-3                            6.7e-4 / B 2.3e-3
+      edge_invalid_depth    7.8e-4 / texture_codes 1.9e-3                7.8e-4 / texture_latent_layer_1.0.weight 2.1e-3
+      edge_single_obj_W     8.1e-4 / encoding_viewdir.0.weight 1.7e-3    7.5e-4 / B 2.1e-3
+      s0_c1_r120_s10_l256   1.2e-3 / texture_latent_layer_1.0.bias 3.1e-3  1.2e-3 / texture_latent_layer_1.0.bias 2.4e-3
+      s0_c1_r512_s32_l256   2.8e-4 / encoding_viewdir.0.weight 1.6e-3    3.0e-4 / encoding_xyz.0.weight 1.8e-3
+      s0_c1_r64_s16_l256    8.6e-4 / B 2.0e-3                            8.5e-4 / B 2.0e-3
+      s0_c2_r64_s16_l32     9.2e-4 / B 2.1e-3                            1.6e-3 / texture_codes 7.9e-2 (named exception)
+      s1_c1_r64_s16_l256    2.0e-3 / texture_layer_1.0.weight 3.3e-2 (named exception)  7.2e-4 / rgb.2.weight 2.6e-3
+      s2_c1_r64_s16_l256    7.4e-4 / encoding_viewdir.0.bias 2.2e-3      7.4e-4 / encoding_viewdir.0.bias 2.3e-3
+    loss: plain_f16 <= 6.0e-6, precise_geometry <= 4.3e-7.  edge_empty_mask: the emulations are 2.65e-2 apart and either kernel is
+    2.65e-2 from the OTHER one, 40 x its distance from its own."""
     g = Golden(name, dev)
-    if bwd_variant == "precise_geometry":
-        pytest.skip("the emulation restates the PLAIN f16 pipeline; the precise recompute is pinned against the fp32 reference below "
-                    "and against the one-launch step (tests/test_trainer_gpu.py)")
-    out = _fused_step(cnr, g, dev, grad_scale=float(2 ** 10))
-    P, B, shape, tex, sig, rgb = _emulated_f16_step(cnr, g, dev)
+    precise = bwd_variant == "precise_geometry"
+    out = _fused_step(cnr, g, dev, grad_scale=float(2 ** 10), precise=precise)
+    P, B, shape, tex, sig, rgb = _emulated_f16_step(cnr, g, dev, precise=precise)
     loss = _torch_loss(sig, rgb, g)
     if g.n_obj > 1:
         loss = loss + 0.0005 * sum(torch.norm(shape[c], dim=-1).sum() + torch.norm(tex[c], dim=-1).sum() for c in range(g.C))
     loss.backward()
-    assert rel_l2(out["loss"], loss) < 1e-4
-    # per tensor on 64-ray fixtures: a unit whose pre-activation is ~1e-6 can flip between MFMA and torch.matmul summation order
-    # (measured, round 4: 3.3e-2 on texture_layer_1.0.weight of s1_c1_r64_s16_l256 -- the one named exception --, 2.3e-2 on
-    # encoding_viewdir.0.weight elsewhere, 1.5e-2 on the texture branch of the 120 x 10 fixture); the whole-trunk bar (5e-3) is the tight one
-    TOL = 5e-2 if name == "s1_c1_r64_s16_l256" else 3e-2
     zg = lambda p: torch.zeros_like(p) if p.grad is None else p.grad
+    own = {k: zg(v) for k, v in P.items()}                              # the emulation of this variant, by tensor name
+    own["B"], own["shape_codes"], own["texture_codes"] = zg(B), zg(shape), zg(tex)
+    _, other = emulated_grads(cnr, g, dev, precise=not precise, regulariser=g.n_obj > 1)
+    kernel = _kernel_grad_tensors(cnr, g, out)
+    errs = {k: rel_l2(kernel[k], own[k]) for k in kernel}
+    trunk, trunk_other = _trunk_rel_l2(cnr, kernel, own), _trunk_rel_l2(cnr, kernel, other)
+    apart = _trunk_rel_l2(cnr, own, other) if precise else _trunk_rel_l2(cnr, other, own)      # precise against plain
+    worst = max(errs, key=errs.get)
+    print(f"[emu] {name} {bwd_variant} trunk={trunk:.2e} worst={worst} {errs[worst]:.2e} loss={rel_l2(out['loss'], loss):.1e} "
+          f"| emulations apart {apart:.2e}, kernel vs the other emulation {trunk_other:.2e}")
+    print("[emu]    over 1e-2: " + " ".join(f"{k}={e:.2e}" for k, e in errs.items() if e > 1e-2))
+    assert rel_l2(out["loss"], loss) < 1e-4
+    # per tensor: 3e-2, but for the tensors NAMED_EXCEPTIONS lists for this case; the whole-trunk bar (5e-3) is the tight one
+    named = NAMED_EXCEPTIONS.get((name, bwd_variant), {})
+    TOL = lambda k: named.get(k, named.get(None, 3e-2))
     off, num, den = 0, 0.0, 0.0
     for n, o, i in cnr.ops.TRUNK_LAYERS:
         for kind, cnt, shp in (("weight", o * i, (g.C, o, i)), ("bias", o, (g.C, o))):
             got = out["trunk"].grad[:, off:off + cnt].reshape(shp)
             ref = zg(P[n + "." + kind])
-            assert rel_l2(got, ref) < TOL, (n, kind, rel_l2(got, ref))
+            assert rel_l2(got, ref) < TOL(n + "." + kind), (n, kind, rel_l2(got, ref))
             num += float((got - ref).double().pow(2).sum()); den += float(ref.double().pow(2).sum())
             off += cnt
     assert (num / den) ** 0.5 < 5e-3
     for n in cnr.ops.LATENT_LAYERS:
-        assert rel_l2(out["lat"][n][0].grad, zg(P[n + ".weight"])) < TOL, n
-        assert rel_l2(out["lat"][n][1].grad, zg(P[n + ".bias"])) < TOL, n
-    assert rel_l2(out["B"].grad, zg(B)) < TOL
-    assert rel_l2(out["shape"].grad, zg(shape)) < TOL
-    assert rel_l2(out["tex"].grad, zg(tex)) < TOL
+        assert rel_l2(out["lat"][n][0].grad, zg(P[n + ".weight"])) < TOL(n + ".weight"), n
+        assert rel_l2(out["lat"][n][1].grad, zg(P[n + ".bias"])) < TOL(n + ".bias"), n
+    assert rel_l2(out["B"].grad, zg(B)) < TOL("B")
+    assert rel_l2(out["shape"].grad, zg(shape)) < TOL("shape_codes")
+    assert rel_l2(out["tex"].grad, zg(tex)) < TOL("texture_codes")
+    assert set(named) - {None} <= set(errs)
+    if apart > DISCRIMINATION_MIN:
+        assert DISCRIMINATION_FACTOR * trunk <= trunk_other, (trunk, trunk_other)
+
+
+def test_a_fixture_tells_the_two_pipelines_apart(cnr, dev):
+    """the discrimination assertion of test_fused_backward_vs_emulated_f16 is not vacuous: at least one fixture's two emulated
+    trunk gradients are more than 2e-2 apart (on the CPU: edge_empty_mask, 2.7e-2)"""
+    selected = []
+    for name in golden_names():
+        g = Golden(name, dev)
+        grads = [emulated_grads(cnr, g, dev, precise=p, regulariser=g.n_obj > 1)[1] for p in (True, False)]
+        if _trunk_rel_l2(cnr, grads[0], grads[1]) > DISCRIMINATION_MIN:
+            selected.append(name)
+    print("[emu] fixtures that discriminate:", selected)
+    assert selected
 
 
 @pytest.mark.parametrize("name", golden_names())
