@@ -118,6 +118,9 @@ SIGNATURES = {
     "cnr_icp_workspace_bytes": [_i64, _i64, _i],
     "cnr_icp_step": [_vp, _i64, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "cnr_icp_update": [_vp, _i64, _i, _i, _vp, _vp, _vp],
+    "cnr_teaser_graph": [_vp, _vp, _i, _f, _vp, _vp, _vp],
+    "cnr_clique_workspace_bytes": [_i, _i],
+    "cnr_clique_search": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
@@ -181,7 +184,7 @@ _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_by
               "cnr_mc_workspace_bytes", "cnr_nn_workspace_bytes", "cnr_dist_stats_workspace_bytes",
               "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes",
               "cnr_unproject_workspace_bytes", "cnr_points_min_workspace_bytes", "cnr_voxel_segments_workspace_bytes",
-              "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes"}
+              "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes", "cnr_clique_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -7,8 +7,8 @@ Everything between the rays and the count runs on the device through the drop-in
 kernels, cnr_composite_fwd's termination); the reference moves the occupancies to the host and finishes in numpy.
 
 The rest of that file for Replica sequences is below it: ``get_all_poses`` (point-cloud accumulation), ``align_poses`` (the
-reference's bookkeeping around a pluggable solver; TEASER++ is not rebuilt, the default is the multi-start GPU ICP
-``IcpSolver``) and ``register_dataset`` (the driver behind ``dataset.get_dataset(cfg, register=True)``), on the kernels of
+reference's bookkeeping around a pluggable solver: the default is the multi-start GPU ICP ``IcpSolver``, and ``TeaserSolver``
+is a TEASER-style global solver on the kernels of csrc/teaser.hip) and ``register_dataset`` (the driver behind ``dataset.get_dataset(cfg, register=True)``), on the kernels of
 csrc/pointcloud.hip.  ScanNet registration is not here.
 """
 import math
@@ -126,7 +126,7 @@ def get_uncertainty_fields(inst_dict, bbox3d_dict, count_dict, pe_dict, fc_occ_m
 
 
 # ---- point clouds, alignment, sub-categorisation (src/category_registration.py:18-56, :179-324) -------------------------
-# DESIGN.md §3.9.  Replica only; TEASER++ sits behind align_poses(..., solver=), the default solver is IcpSolver.
+# DESIGN.md §3.9.  Replica only; align_poses(..., solver=) takes IcpSolver (the default) or TeaserSolver.
 def get_all_poses(inst_dict, sample_dict, intrinsic_open3d, name="replica", depth_scale=0.001, max_depth=8.0):
     """:18-56, Replica branch.  Every instance of every class gets 'pcs': its pixels of all its frames as one cloud at 1 cm.
     The background (class 0) gets 'pcs' too and 'bbox3D', the oriented box of that cloud with its true extents (no 10 cm
@@ -242,6 +242,221 @@ class IcpSolver:
                                         self.max_iteration)
         T = np.stack([S @ Tk for S, Tk in zip(rel, T)])
         return torch.from_numpy(T[:, :3, :3].copy()), torch.from_numpy(T[:, :3, 3:].copy())
+
+
+# ---- TEASER-style global registration -------------------------------------------------------------------
+# The stages of Yang, Shi, Carlone, "TEASER: Fast and Certifiable Point Cloud Registration" (arXiv 2001.07715) with the
+# parameters of the reference's get_teaser_solver, in its "simultaneous pose and correspondence" use: all-to-all
+# correspondences, compatibility graph, maximum clique, GNC-TLS rotation, voted translation, ICP.  The graph and the clique
+# are HIP (csrc/teaser.hip); rotation and translation work on a few hundred 3-vectors and run on the host in fp64.
+TEASER_MAX_N = 16384          # CNR_TEASER_MAX_N
+
+
+def teaser_correspondences(source, template, voxel_size=0.1, max_correspondences=10000, rng=None, device=None):
+    """Stage 1.  Both clouds ((n,3) arrays or PointClouds) down-sampled to voxel_size, all n_s n_t pairs, and when there are more
+    than max_correspondences that many of them drawn without replacement from `rng` (a numpy Generator; default seed 0), kept
+    in ascending pair order.  -> (A (N,3), B (N,3) f32 device tensors with A[i] <-> B[i], the two down-sampled PointClouds,
+    pairs (N,2) int64 host: indices into them)"""
+    from .utils import PointCloud
+    as_cloud = lambda c: c if isinstance(c, PointCloud) else PointCloud(np.asarray(c, np.float64), device=device)
+    src_ds, tgt_ds = as_cloud(source).voxel_down_sample(voxel_size), as_cloud(template).voxel_down_sample(voxel_size)
+    n_s, n_t = len(src_ds), len(tgt_ds)
+    total = n_s * n_t
+    if int(max_correspondences) < 1 or int(max_correspondences) > TEASER_MAX_N:
+        raise ValueError(f"max_correspondences must lie in [1, {TEASER_MAX_N}]")
+    if total > int(max_correspondences):
+        rng = np.random.default_rng(0) if rng is None else rng
+        flat = np.sort(rng.choice(total, int(max_correspondences), replace=False))
+    else:
+        flat = np.arange(total)
+    pairs = np.stack([flat // n_t, flat % n_t], 1).astype(np.int64)
+    dev = src_ds.points_device.device
+    A = src_ds.points_device[torch.from_numpy(pairs[:, 0]).to(dev)].contiguous()
+    B = tgt_ds.points_device.to(dev)[torch.from_numpy(pairs[:, 1]).to(dev)].contiguous()
+    return A, B, src_ds, tgt_ds, pairs
+
+
+def compatibility_threshold(noise_bound=0.01, cbar2=1.0):
+    """2 noise_bound sqrt(cbar2), rounded once to fp32: the bound of the graph's fp32 comparison"""
+    return float(np.float32(2.0 * float(noise_bound) * math.sqrt(float(cbar2))))
+
+
+def compatibility_graph(A, B, noise_bound=0.01, cbar2=1.0):
+    """Stage 2 (cnr_teaser_graph).  A, B (N,3) f32 device tensors -> (adj (N, ceil(N/64)) int64 device tensor: bit j & 63 of word
+    j >> 6 of row i says i ~ j, i.e. | |B_i - B_j| - |A_i - A_j| | <= 2 noise_bound sqrt(cbar2) in fp32; deg (N,) int32)"""
+    from . import _C
+    N = len(A)
+    if not 1 <= N <= TEASER_MAX_N or A.shape != (N, 3) or B.shape != (N, 3):
+        raise ValueError(f"compatibility_graph: (N,3) correspondences with 1 <= N <= {TEASER_MAX_N}")
+    if not (torch.is_tensor(A) and torch.is_tensor(B) and A.is_cuda and B.device == A.device):
+        raise ValueError("compatibility_graph: A and B are tensors on one GPU")
+    A, B = A.to(torch.float32).contiguous(), B.to(torch.float32).contiguous()
+    adj = torch.empty(N, (N + 63) // 64, device=A.device, dtype=torch.int64)
+    deg = torch.empty(N, device=A.device, dtype=torch.int32)
+    _C.call("cnr_teaser_graph", A, B, N, compatibility_threshold(noise_bound, cbar2), adj, deg)
+    return adj, deg
+
+
+DEFAULT_SEARCH_BUDGET = 1 << 20          # row ANDs one root vertex may spend
+
+
+def clique_order(deg):
+    """the fixed vertex order of the search: ascending degree, ties by index -> (N,) int32 device tensor"""
+    return torch.sort(deg.to(torch.int64), stable=True)[1].to(torch.int32).contiguous()
+
+
+def max_clique(adj, deg, search_budget=None):
+    """Stage 3 (cnr_clique_search).  -> (clique: int64 host array of vertices, ascending in clique_order(deg); info: size, exact,
+    steps, find_steps, max_root_steps, roots_out_of_budget, greedy_size, flags).  With exact the clique is the maximum clique
+    that is lexicographically smallest in positions of clique_order(deg); without, it is a clique and its size a lower bound."""
+    from . import _C
+    from .utils import _workspace
+    N, dev = len(deg), adj.device
+    if not (adj.is_cuda and deg.device == dev and adj.dtype == torch.int64 and adj.shape == (N, (N + 63) // 64)
+            and deg.dtype == torch.int32 and deg.dim() == 1 and 1 <= N <= TEASER_MAX_N):
+        raise ValueError(f"max_clique: adj (N, ceil(N/64)) int64 and deg (N,) int32 on one GPU, 1 <= N <= {TEASER_MAX_N}")
+    adj, deg = adj.contiguous(), deg.contiguous()
+    budget = DEFAULT_SEARCH_BUDGET if search_budget is None else int(search_budget)
+    if budget < 1 or budget >= 1 << 31:
+        raise ValueError("search_budget must lie in [1, 2^31)")
+    order = clique_order(deg)
+    max_degree = int(deg.max())
+    ws = _workspace(_C.load().cnr_clique_workspace_bytes(N, max_degree), dev, "cnr_clique_search")
+    out = torch.zeros(max_degree + 1, device=dev, dtype=torch.int32)
+    info = torch.zeros(8, device=dev, dtype=torch.int64)
+    _C.call("cnr_clique_search", adj, order, N, max_degree, budget, ws, out, info)
+    v = [int(x) for x in info.cpu()]
+    keys = ("size", "exact", "steps", "find_steps", "max_root_steps", "roots_out_of_budget", "greedy_size", "flags")
+    res = dict(zip(keys, v))
+    res["exact"] = bool(res["exact"])
+    return out[:res["size"]].cpu().numpy().astype(np.int64), res
+
+
+def _weighted_rotation(a, b, w):
+    """the proper rotation minimising sum w |b - R a|^2 (no centring: the inputs are translation-free)"""
+    U, _, Vt = np.linalg.svd((a * w[:, None]).T @ b)
+    return Vt.T @ np.diag([1.0, 1.0, np.linalg.det(Vt.T @ U.T)]) @ U.T
+
+
+def gnc_tls_rotation(a, b, bound, gnc_factor=1.4, max_iterations=100, cost_threshold=1e-12):
+    """Stage 4.  Graduated non-convexity on the truncated least squares cost sum min(|b_k - R a_k|^2, bound) over (K,3) fp64
+    measurement pairs.  Per iteration: the weighted SVD fit; with r = the squared residuals, on the first iteration mu = 1 /
+    (2 max r / bound - 1) (mu <= 0: every residual is inside the bound, done); weights 1 below mu/(mu+1) bound, 0 above
+    (mu+1)/mu bound, sqrt(bound mu (mu+1) / r) - mu between; mu *= gnc_factor; stop when the weighted cost moves by less than
+    cost_threshold.  -> (R (3,3), iterations, weights (K,))"""
+    a, b = np.asarray(a, np.float64).reshape(-1, 3), np.asarray(b, np.float64).reshape(-1, 3)
+    w = np.ones(len(a))
+    if len(a) == 0:
+        return np.eye(3), 0, w
+    R, mu, prev = np.eye(3), 1.0, math.inf
+    it = 0
+    for it in range(1, int(max_iterations) + 1):
+        R = _weighted_rotation(a, b, w)
+        r = ((b - a @ R.T) ** 2).sum(1)
+        if it == 1:
+            denom = 2.0 * r.max() / bound - 1.0
+            if denom <= 0:
+                break
+            mu = 1.0 / denom
+        cost = float((w * r).sum())
+        hi, lo = (mu + 1.0) / mu * bound, mu / (mu + 1.0) * bound
+        w = np.where(r >= hi, 0.0, np.where(r <= lo, 1.0, np.sqrt(bound * mu * (mu + 1.0) / np.maximum(r, 1e-300)) - mu))
+        mu *= gnc_factor
+        done = abs(cost - prev) < cost_threshold
+        prev = cost
+        if done:
+            break
+    return R, it, w
+
+
+def tls_scalar(x, bound, cbar2=1.0):
+    """TEASER's adaptive voting for one scalar: the minimiser of sum min((x_k - t)^2 / bound^2, cbar2).  Each measurement votes
+    for [x_k - bound cbar, x_k + bound cbar]; between two consecutive interval ends the consensus set is constant, its mean the
+    candidate, and the candidate of the lowest cost wins (the first of equals).  -> (t, consensus mask)"""
+    x = np.asarray(x, np.float64).reshape(-1)
+    half = bound * math.sqrt(cbar2)
+    ends = np.sort(np.concatenate([x - half, x + half]))
+    best = (math.inf, 0.0, np.zeros(len(x), bool))
+    for m in (ends[:-1] + ends[1:]) / 2:
+        inside = np.abs(x - m) <= half
+        if not inside.any():
+            continue
+        t = float(x[inside].mean())
+        cost = float(((x[inside] - t) ** 2).sum() / bound ** 2 + cbar2 * (len(x) - inside.sum()))
+        if cost < best[0]:
+            best = (cost, t, inside)
+    if not best[2].any():
+        best = (0.0, float(x.mean()) if len(x) else 0.0, np.ones(len(x), bool))
+    return best[1], best[2]
+
+
+def tls_translation(a, b, R, noise_bound=0.01, cbar2=1.0):
+    """Stage 5.  Component-wise adaptive voting on b_k - R a_k with bound noise_bound sqrt(cbar2) -> t (3,)"""
+    d = np.asarray(b, np.float64) - np.asarray(a, np.float64) @ np.asarray(R, np.float64).T
+    return np.array([tls_scalar(d[:, k], noise_bound, cbar2)[0] for k in range(3)])
+
+
+class TeaserSolver:
+    """A solver for align_poses(..., solver=): TEASER's stages with the reference's parameters as defaults (get_teaser_solver,
+    TEASER_FPFH_ICP with spc=True), see the stage functions above.  Templates that are rigid copies of the first (align_poses'
+    24 box symmetries) share one graph, one clique and one pose T.  The B starts S_k T are refined the way IcpSolver runs
+    its batch: against the ONE down-sampled first template, each start taken back by inv(S_k) -- where all B coincide, so one ICP
+    runs and its result is moved by each S_k.  That equals refining S_k T against a down-sampled template k only while
+    down-sampling commutes with S_k (every point alone in its voxel); on dense clouds the voxel centroids of a rotated
+    template differ, and so would that refinement, by an amount that is not measured.  Other templates are solved one by one.  last_info: per solved template group N, edges, clique_size, exact, gnc_iterations, icp_state, the
+    search's step counts, and graph_builds for the call."""
+
+    def __init__(self, voxel_size=0.1, noise_bound=0.01, max_correspondences=10000, cbar2=1.0, gnc_factor=1.4,
+                 rotation_max_iterations=100, rotation_cost_threshold=1e-12, icp_max_iteration=100, seed=0, search_budget=None,
+                 icp_max_corr=None):
+        self.voxel_size, self.noise_bound, self.max_correspondences, self.cbar2 = voxel_size, noise_bound, max_correspondences, cbar2
+        self.gnc_factor, self.rotation_max_iterations = gnc_factor, rotation_max_iterations
+        self.rotation_cost_threshold, self.icp_max_iteration, self.seed = rotation_cost_threshold, icp_max_iteration, seed
+        self.search_budget, self.icp_max_corr = search_budget, icp_max_corr
+        self.last_info = None
+
+    def solve_pose(self, A, B, clique):
+        """stages 4 and 5 on the clique's correspondences -> (T (4,4) source -> template, GNC iterations)"""
+        a, b = A[clique].double().cpu().numpy(), B[clique].double().cpu().numpy()
+        nxt = np.roll(np.arange(len(clique)), -1)                    # the chain: each member with the next, the last with the first
+        k = len(clique) if len(clique) > 2 else len(clique) - 1      # (two members: one measurement, one member: none)
+        R, its, _ = gnc_tls_rotation((a[nxt] - a)[:k], (b[nxt] - b)[:k], (2.0 * self.noise_bound) ** 2 * self.cbar2, self.gnc_factor,
+                                     self.rotation_max_iterations, self.rotation_cost_threshold)
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = R, tls_translation(a, b, R, self.noise_bound, self.cbar2)
+        return T, its
+
+    def solve_one(self, source, template, device=None):
+        """one source (n,3) against one template (m,3) -> (T (4,4) after ICP, info)"""
+        A, B, src_ds, tgt_ds, _ = teaser_correspondences(source, template, self.voxel_size, self.max_correspondences,
+                                                         np.random.default_rng(self.seed), device)
+        adj, deg = compatibility_graph(A, B, self.noise_bound, self.cbar2)
+        clique, found = max_clique(adj, deg, self.search_budget)
+        T0, its = self.solve_pose(A, B, torch.from_numpy(clique).to(A.device))
+        max_corr = self.noise_bound if self.icp_max_corr is None else self.icp_max_corr
+        T, state = icp_device(src_ds.points_device, tgt_ds.points_device, T0[None], max_corr, self.icp_max_iteration)
+        info = dict(N=len(A), edges=int(deg.sum(dtype=torch.int64)) // 2, clique_size=len(clique), exact=found["exact"],
+                    gnc_iterations=its, icp_state=state, T_before_icp=T0, clique=clique, search=found)
+        return T[0], info
+
+    def __call__(self, source, templates):
+        dev = source.device if torch.is_tensor(source) and source.is_cuda else None
+        as_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        src = as_np(source).astype(np.float64)[0].T
+        tm = as_np(templates).astype(np.float64).transpose(0, 2, 1)
+        try:
+            rel = IcpSolver()._copies(tm) if len(tm) > 1 else [np.eye(4)]
+        except ValueError:
+            rel = None
+        if rel is not None:
+            T, info = self.solve_one(src, tm[0], dev)
+            out, groups = np.stack([S @ T for S in rel]), [info]
+            info["icp_state"] = np.repeat(info["icp_state"], len(rel), axis=0)
+        else:
+            solved = [self.solve_one(src, t, dev) for t in tm]
+            out, groups = np.stack([T for T, _ in solved]), [i for _, i in solved]
+        self.last_info = dict(groups[0], graph_builds=len(groups), rigid_copies=rel is not None, groups=groups)
+        return torch.from_numpy(out[:, :3, :3].copy()), torch.from_numpy(out[:, :3, 3:].copy())
 
 
 def _mean_nn_distance(points_from, points_to):

@@ -861,6 +861,29 @@ int cnr_icp_step(const float* src, int64_t n_src, const float* tgt, int64_t n_tg
                  const double* state, void* workspace, double* sums, float* dist_out, int* index_out, void* stream);
 int cnr_icp_update(const double* sums, int64_t n_src, int B, int max_iter, double* T, double* state, void* stream);
 
+/* ---- TEASER-style global registration (category_registration.TeaserSolver): the two device stages.  The
+ * contracts above hold: caller-allocated outputs, a workspace query, explicit stream, integer work only beyond the fp32 test
+ * (no float atomics; results bit-identical run to run).
+ * cnr_teaser_graph: the compatibility graph of N correspondences a_i -> b_i (A, B (N,3) f32): i ~ j (i != j) iff
+ * fabsf(nb - na) <= threshold with na = sqrtf((dx dx + dy dy) + dz dz) of d = a_i - a_j and nb likewise of b_i - b_j, every
+ * operation a single correctly rounded fp32 operation in this order (no fused multiply-add).  adj (N, ceil(N / 64)) u64: bit
+ * (j & 63) of word j >> 6 of row i; bits at and beyond N are zero; deg (N,) i32 the row sums.  1 <= N <= CNR_TEASER_MAX_N. */
+#define CNR_TEASER_MAX_N 16384
+int cnr_teaser_graph(const float* A, const float* B, int N, float threshold, uint64_t* adj, int* deg, void* stream);
+/* The maximum clique of a symmetric bitset graph in cnr_teaser_graph's layout.  order (N,) i32: a permutation of the vertices,
+ * the fixed order of the search (the caller sorts by ascending degree, ties by index); max_degree >= the largest row sum.
+ * Exact depth-first search, one wave per root vertex over its later neighbours in that order, pruned by the best size so far;
+ * then the clique that is lexicographically smallest in positions of `order` among those of that size is rebuilt.  clique_out
+ * (>= max_degree + 1) i32: its vertices (the caller's labels) in ascending position.  info_out (8) i64: [size, exact,
+ * steps of the size pass, steps of the rebuilding pass, most steps of one root, roots that ran out of budget, the greedy
+ * pass's size, flags (1: a row held more than max_degree neighbours, 2: the greedy clique was returned)].  A step is one AND
+ * of the candidate set with an adjacency row; a root that has spent `budget` (>= 1) of them stops, and exact = 0 then: the
+ * clique returned is still a clique, its size a lower bound.  With exact = 1 the result does not depend on timing.
+ * workspace >= cnr_clique_workspace_bytes(N, max_degree). */
+int64_t cnr_clique_workspace_bytes(int N, int max_degree);
+int cnr_clique_search(const uint64_t* adj, const int* order, int N, int max_degree, int budget, void* workspace, int* clique_out,
+                      int64_t* info_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
