@@ -1,6 +1,9 @@
 """GPU: the TEASER-style solver (csrc/teaser.hip, category_registration.TeaserSolver) against the restatement
-tests/teaser_cpu.py: the graph bit for bit on the guarded cases, the clique on graphs small enough for Bron-Kerbosch and on the
-planted construction at N = 10 000, the budget, align_poses end to end, and rigid-copy templates."""
+tests/teaser_cpu.py: the graph bit for bit on the guarded cases and on unguarded ones (pairs exactly at the threshold, pairs a
+fused multiply-add flips), the clique on graphs small enough for Bron-Kerbosch -- among them dense ones that rebuild deep
+levels thousands of times and embedded or positioned ones for the two wider instantiations of the search -- and on the planted
+construction at N = 10 000, the budget at every scale, the max_degree and order guards by direct calls, align_poses end to
+end, and rigid-copy templates.  tests/test_teaser_host.py proves by the restatement alone that each case can fail for its reason."""
 import time
 
 import numpy as np
@@ -51,8 +54,8 @@ def test_graph_equals_the_restatement_bit_for_bit_gpu(dev, CR, name):
     assert torch.equal(adj, adj2) and torch.equal(deg, deg2)
 
 
-def _check_against_restatement(CR, dev, adj_bool):
-    want = TC.max_clique(adj_bool)
+def _check_against_restatement(CR, dev, adj_bool, want=None):
+    want = TC.max_clique(adj_bool) if want is None else want
     adj, deg = _dev_graph(adj_bool, dev)
     got, info = CR.max_clique(adj, deg)
     print("clique", len(got), "restatement", len(want), info)
@@ -105,6 +108,138 @@ def test_a_tiny_budget_ends_promptly_and_inexact_gpu(dev, CR):
     assert not info["exact"] and info["roots_out_of_budget"] > 0 and info["max_root_steps"] <= 2 + 2500
     assert len(got) >= 1 and TC.is_clique(adj_bool, got)
     assert seconds < 5.0
+
+
+# ---- deep levels, the wider instantiations, the budget and the guards ----------------------------------------------------------
+SENTINEL = -77
+
+
+def _print_steps(name, info):
+    print(name, "GPU steps", info["steps"], "find_steps", info["find_steps"], "max_root_steps", info["max_root_steps"],
+          "| search_trace (one root after the other)", TC.SEARCH_TRACE_RECORD[name])
+
+
+@pytest.mark.parametrize("name", ["dense_96", "dense_120"])
+def test_clique_on_dense_graphs_that_rebuild_deep_levels_gpu(dev, CR, name):
+    """levels far beyond KL = 8 with thousands of backtracks there (dfs_root's rebuild branch), several maximum cliques"""
+    got, info = _check_against_restatement(CR, dev, TC.dense_graph_cases()[name], TC.expected_cliques()[name])
+    _print_steps(name, info)
+    assert info["roots_out_of_budget"] == 0 and info["flags"] == 0
+    assert info["greedy_size"] == TC.SEARCH_TRACE_RECORD[name]["greedy_size"] < info["size"]          # the greedy pass has no timing
+
+
+@pytest.mark.parametrize("name", ["embedded_4200", "embedded_8300"])
+def test_clique_in_the_wide_instantiations_gpu(dev, CR, name):
+    """66 and 130 row words: two and four words per lane (KL = 8 and 4), with rebuilds, against the exact answer"""
+    got, info = _check_against_restatement(CR, dev, TC.embedded_case(*TC.EMBEDDED[name]), TC.expected_cliques()[name])
+    _print_steps(name, info)
+    assert info["roots_out_of_budget"] == 0 and info["flags"] == 0
+
+
+def _direct_search(dev, words, order, max_degree, budget, alloc_degree=None):
+    """cnr_clique_search itself -> (clique_out whole, info as max_clique names it); buffers sized for alloc_degree, clique_out
+    filled with SENTINEL"""
+    import cnr_amd
+    _C, N = cnr_amd._C, len(words)
+    alloc = max_degree if alloc_degree is None else alloc_degree
+    adj = torch.from_numpy(np.ascontiguousarray(words).view(np.int64)).to(dev).contiguous()
+    order = torch.from_numpy(np.asarray(order, np.int32)).to(dev)
+    ws = torch.zeros(int(_C.load().cnr_clique_workspace_bytes(N, alloc)), device=dev, dtype=torch.uint8)
+    out = torch.full((alloc + 1,), SENTINEL, device=dev, dtype=torch.int32)
+    info = torch.zeros(8, device=dev, dtype=torch.int64)
+    _C.call("cnr_clique_search", adj, order, N, int(max_degree), int(budget), ws, out, info)
+    keys = ("size", "exact", "steps", "find_steps", "max_root_steps", "roots_out_of_budget", "greedy_size", "flags")
+    return out.cpu().numpy().astype(np.int64), dict(zip(keys, (int(x) for x in info.cpu())))
+
+
+@pytest.mark.parametrize("name", ["positioned_4161", "positioned_8257", "positioned_16379"])
+def test_clique_members_across_word_boundaries_gpu(dev, CR, name):
+    """identity order: the members sit on bits 63/64, words 63/64, 127/128, 191/192 and the last bit of the last, partial word"""
+    c = TC.positioned_cases()[name]
+    K = len(c["members"])
+    out, info = _direct_search(dev, c["words"], np.arange(c["N"]), K - 1, CR.DEFAULT_SEARCH_BUDGET)
+    print(name, info, out)
+    assert info["size"] == K and info["exact"] == 1 and info["flags"] == 0 and info["roots_out_of_budget"] == 0
+    assert np.array_equal(out[:K], c["members"]) and (out[K:] == SENTINEL).all()
+    assert info["greedy_size"] == K
+
+
+def test_budget_sweep_never_reports_a_wrong_exact_answer_gpu(dev, CR):
+    """dense_96 at budgets from 1 to the default: always a clique between the greedy and the true size, a root's steps within
+    budget + cap, and whatever is called exact IS the restatement's clique.  (Inexact results may differ run to run: which
+    roots run out depends on when `best` arrives; so nothing is asserted about them between runs.)"""
+    adj_bool, want = TC.dense_graph_cases()["dense_96"], TC.expected_cliques()["dense_96"]
+    adj, deg = _dev_graph(adj_bool, dev)
+    cap = int(adj_bool.sum(1).max()) + 1
+    for budget in (1, 8, 64, 512, 4096, 32768, None):
+        got, info = CR.max_clique(adj, deg, search_budget=budget)
+        print("budget", budget, info)
+        b = CR.DEFAULT_SEARCH_BUDGET if budget is None else budget
+        assert TC.is_clique(adj_bool, got) and info["size"] == len(got)
+        assert info["greedy_size"] <= info["size"] <= len(want)
+        assert info["greedy_size"] == TC.SEARCH_TRACE_RECORD["dense_96"]["greedy_size"]
+        assert info["max_root_steps"] <= b + cap
+        if info["exact"]:
+            assert np.array_equal(got, want) and info["roots_out_of_budget"] == 0, budget
+        if budget == 1:
+            assert not info["exact"] and info["roots_out_of_budget"] > 0
+        if budget is None:
+            assert info["exact"] and info["roots_out_of_budget"] == 0
+
+
+def test_an_understated_max_degree_is_caught_gpu(dev, CR):
+    """A 40-clique laid over a sparse graph, searched with half the true maximum degree stated: fewer levels than the clique
+    has.  The buffers are sized for the TRUE degree, so a broken guard writes into owned memory and shows on the sentinel."""
+    adj_bool = TC.random_graph(5, 150, 0.1)
+    members = np.random.default_rng(50).permutation(150)[:40]
+    adj_bool[np.ix_(members, members)] = ~np.eye(40, dtype=bool)
+    true_max = int(adj_bool.sum(1).max())
+    stated = true_max // 2
+    assert stated + 1 < 40 <= true_max + 1
+    out, info = _direct_search(dev, TC.pack(adj_bool), TC.search_order(adj_bool), stated, CR.DEFAULT_SEARCH_BUDGET, alloc_degree=true_max)
+    print("true max degree", true_max, "stated", stated, info)
+    assert info["flags"] & 1 and info["exact"] == 0
+    assert 1 <= info["size"] <= stated + 1
+    assert (out[info["size"]:] == SENTINEL).all()
+    assert TC.is_clique(adj_bool, out[:info["size"]])
+
+
+def test_order_entries_outside_the_range_read_as_isolated_vertices_gpu(dev, CR):
+    """Two members of the maximum clique lose their entry of `order` (-1 and N): their positions have no edge, the answer is the
+    restatement's on the graph without those two vertices, in positions of the same order."""
+    adj_bool = TC.random_graph(2, 200, 0.3)
+    N, order, first = 200, TC.search_order(adj_bool), TC.max_clique(adj_bool)
+    gone = first[[0, -1]]
+    cleared = adj_bool.copy()
+    cleared[gone, :] = cleared[:, gone] = False
+    want = TC.max_clique(cleared, order=order)
+    assert len(want) > 1 and not set(want.tolist()) & set(gone.tolist())
+    broken = order.copy()
+    broken[np.flatnonzero(order == gone[0])], broken[np.flatnonzero(order == gone[1])] = -1, N
+    max_degree = int(adj_bool.sum(1).max())
+    out, info = _direct_search(dev, TC.pack(adj_bool), broken, max_degree, CR.DEFAULT_SEARCH_BUDGET)
+    print(info, out[:info["size"]], "restatement", want, "with every vertex", first)
+    assert info["size"] == len(want) and info["exact"] == 1 and info["flags"] == 0
+    assert np.array_equal(out[:len(want)], want) and (out[len(want):] == SENTINEL).all()
+
+
+@pytest.mark.parametrize("name", ["lattice", "contraction", "planted_4161"])
+def test_unguarded_graph_equals_the_restatement_bit_for_bit_gpu(dev, CR, name):
+    """No vertex dropped: pairs exactly at the threshold (<= against <), pairs that a fused multiply-add flips, and a natural
+    input of 66 row words.  The header promises single correctly rounded fp32 operations in a fixed order; that is compared."""
+    A, B, noise_bound = TC.threshold_cases()[name]
+    want = TC.graph(A, B, noise_bound)
+    adj, deg = CR.compatibility_graph(torch.from_numpy(A).to(dev), torch.from_numpy(B).to(dev), noise_bound=noise_bound)
+    got = _host_adj(adj, len(A))
+    if not np.array_equal(got, want):
+        thr = TC.threshold32(noise_bound)
+        na, nb, ca, cb = TC.pair_norms32(A), TC.pair_norms32(B), TC.pair_norms32_contracted(A), TC.pair_norms32_contracted(B)
+        ulps = lambda x, y: (np.float64(np.abs(np.float32(y - x))) - np.float64(thr)) / np.float64(np.spacing(thr))
+        for i, j in list(zip(*np.nonzero(np.triu(got != want))))[:20]:
+            print("pair", i, j, "GPU", got[i, j], "restatement", want[i, j], "| chain: |a|", na[i, j], "|b|", nb[i, j], "difference - thr",
+                  ulps(na[i, j], nb[i, j]), "ulp | contracted: |a|", ca[i, j], "|b|", cb[i, j], "difference - thr", ulps(ca[i, j], cb[i, j]), "ulp")
+    assert np.array_equal(adj.cpu().numpy().view(np.uint64), TC.pack(want))          # the padding bits too
+    assert np.array_equal(deg.cpu().numpy(), want.sum(1))
 
 
 def _solver(CR, **kw):

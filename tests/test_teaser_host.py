@@ -136,3 +136,83 @@ def test_abi_rows_of_the_new_symbols():
     assert lib.cnr_clique_search(None, None, 4, 3, 10, None, None, None, None) == -1
     assert lib.cnr_clique_workspace_bytes(0, 0) < 0 and lib.cnr_clique_workspace_bytes(cnr_amd.category_registration.TEASER_MAX_N + 1, 5) < 0
     assert lib.cnr_clique_workspace_bytes(1, 0) > 0 and lib.cnr_clique_workspace_bytes(10000, 1800) > 10000 * 157 * 8
+
+
+# ---- the cases of tests/test_teaser_gpu.py that pin the search's deep levels, its wider instantiations and the graph's threshold:
+# each can fail for the reason it exists, by the restatement alone (conditions, not measurements) ------------------------------
+def _budget(CR):
+    return CR.DEFAULT_SEARCH_BUDGET
+
+
+@pytest.mark.parametrize("name,min_rebuilds", [("dense_96", 1000), ("dense_120", 50)])
+def test_dense_cases_rebuild_deep_levels_and_outrun_the_greedy_pass(CR, name, min_rebuilds):
+    adj = TC.dense_graph_cases()[name]
+    KL = TC.KL_OF_WORDS((len(adj) + 63) // 64)
+    assert KL == 8
+    tr = TC.search_trace(adj, KL, _budget(CR))
+    print(name, tr)
+    assert tr == TC.SEARCH_TRACE_RECORD[name]
+    assert tr["rebuilds"] >= min_rebuilds and tr["deepest_level"] >= KL + 4 and tr["roots_out_of_budget"] == 0
+    assert tr["max_root_steps"] <= _budget(CR) // 4          # headroom for the GPU's later `best`
+    want = TC.max_clique(adj)
+    assert TC.is_clique(adj, want) and tr["greedy_size"] < tr["size"] == len(want)
+    assert np.array_equal(want, TC.expected_cliques()[name])          # the record the GPU test reads
+
+
+@pytest.mark.parametrize("name,words,KL", [("embedded_4200", range(65, 129), 8), ("embedded_8300", range(129, 257), 4)])
+def test_embedded_cases_reach_the_wide_instantiations_with_rebuilds(CR, name, words, KL):
+    adj = TC.embedded_cases()[name]
+    W = (len(adj) + 63) // 64
+    assert W in words and TC.KL_OF_WORDS(W) == KL and len(adj) % 64
+    tr = TC.search_trace(adj, KL, _budget(CR))
+    print(name, tr)
+    assert tr == TC.SEARCH_TRACE_RECORD[name]
+    assert tr["rebuilds"] >= 10 and tr["roots_out_of_budget"] == 0 and tr["max_root_steps"] <= _budget(CR) // 4
+    want = TC.max_clique(adj)
+    assert TC.is_clique(adj, want) and tr["size"] == len(want)
+    assert np.array_equal(want, TC.expected_cliques()[name])
+
+
+def test_positioned_cases_straddle_the_word_boundaries():
+    cases = TC.positioned_cases()
+    assert sorted(c["N"] for c in cases.values()) == [4161, 8257, 16379]
+    for name, c in cases.items():
+        N, m = c["N"], set(c["members"].tolist())
+        W = (N + 63) // 64
+        assert N % 64 and c["words"].shape == (N, W)
+        assert {63, 64} <= m                                                   # bit 63 of word 0, bit 0 of word 1
+        for w in (64, 128, 192):                                               # the lane's next word
+            if w < W - 1:
+                assert {64 * w - 1, 64 * w} <= m, (name, w)
+        assert N - 1 in m and (N - 1) >> 6 == W - 1 and N < 64 * W             # the last bit of the last, partial word
+        assert max(m) >> 12 == (W - 1) // 64                                   # a member in the lane's last word index
+        # the answer, by construction and by Bron-Kerbosch on the vertices that have an edge at all
+        live = np.flatnonzero(c["deg"] > 0)
+        assert set(live.tolist()) == m | set(c["decoy"].tolist())
+        sub = TC.unpack(c["words"][live], N)[:, live]
+        assert (sub == sub.T).all() and np.array_equal(sub.sum(1), c["deg"][live])
+        got = live[TC.max_clique(sub, order=np.arange(len(live)))]
+        assert np.array_equal(got, c["members"]) and len(c["decoy"]) == len(got) - 1
+        assert c["decoy"].max() < 64 and c["decoy"].min() < c["members"].min()          # what a search blind beyond word 0 finds first
+
+
+def test_lattice_case_has_pairs_exactly_at_the_threshold():
+    A, B = TC.lattice_case()
+    thr = TC.threshold32(TC.LATTICE_NOISE_BOUND)
+    assert float(thr) == 0.125 and len(A) == 1500
+    diff = np.abs(TC.pair_norms32(B) - TC.pair_norms32(A))
+    at = np.triu(diff == thr, 1)
+    print("pairs exactly at the threshold", int(at.sum()))
+    assert int(at.sum()) >= 16                                                 # <= and < differ on them
+    le = diff <= thr
+    np.fill_diagonal(le, False)
+    assert np.array_equal(le, TC.graph(A, B, TC.LATTICE_NOISE_BOUND))
+
+
+def test_contraction_case_tells_a_fused_multiply_add_from_the_promised_chain():
+    A, B = TC.contraction_case()
+    assert len(A) <= 2048
+    plain, fused = TC.graph(A, B), TC.graph_contracted(A, B)
+    differ = int(np.triu(plain != fused, 1).sum())
+    print("N", len(A), "edges", int(plain.sum()) // 2, "edges a contracted evaluation flips", differ)
+    assert differ >= 16
