@@ -3,6 +3,7 @@ the reference's metrics.py (tests/golden/metric/), calc_3d_metric end to end on 
 tiny Replica-style tree."""
 import glob
 import json
+import math
 import os
 import struct
 import subprocess
@@ -64,16 +65,47 @@ def test_nn_dist_duplicates_and_exact_hits(mt, dev):
 
 
 def test_dist_stats(mt, dev):
+    """The count is exact: the kernel compares float v < float th with th rounded to fp32 as ctypes rounds a c_float argument
+    (to nearest), which is np.float32(th), and numpy compares the same two fp32 numbers.  The sum: any order of n fp64
+    additions of non-negative terms is within (n - 1) 2^-53 of the exact sum (math.fsum), relatively."""
     g = torch.Generator(device=dev).manual_seed(5)
-    for n in (1, 255, 256, 257, 10000, 200001):
+    for n in (1, 255, 256, 257, 10000, 65536, 65537, 200001):
         d = torch.rand(n, device=dev, generator=g) * 0.2
         th = 0.05
         s, c = mt.dist_stats(d, th)
-        d64 = d.double()
-        assert s == pytest.approx(float(d64.sum()), rel=1e-10, abs=1e-300)
-        if not ((d64 - th).abs() < 1e-6).any():
-            assert c == int((d < th).sum())
+        dn = d.cpu().numpy()
+        assert s == pytest.approx(math.fsum(dn.astype(np.float64)), rel=n * 2.0 ** -53, abs=1e-300)
+        assert c == int((dn < np.float32(th)).sum())
         assert (s, c) == mt.dist_stats(d, th)
+
+
+def test_dist_stats_at_the_threshold_and_non_finite(mt, dev):
+    """strict <: th itself and the fp32 number above it are not counted, the one below is; inf and NaN are never counted, not
+    even under th = inf; a NaN makes the sum NaN, an inf without a NaN makes it inf"""
+    th = 0.05
+    t32 = np.float32(th)
+    up, down = np.nextafter(t32, np.float32(np.inf)), np.nextafter(t32, np.float32(-np.inf))
+    assert down < t32 < up
+    edge = np.array([t32, up, down, np.inf, 0.01, 0.2, down, t32], np.float32)
+    rng = np.random.default_rng(8)
+    body = (rng.random(70001) * 0.2).astype(np.float32)
+    at = rng.permutation(len(body))[:len(edge)]
+    body[at] = edge
+    for base in (edge, body):
+        for with_nan in (False, True):
+            d = np.append(base, np.float32(np.nan)) if with_nan else base
+            t = torch.from_numpy(d).to(dev)
+            s, c = mt.dist_stats(t, th)
+            assert c == int((d < t32).sum())
+            if base is edge:
+                assert c == 3                         # 0.01 and `down` twice, by hand; the NaN adds nothing
+            assert math.isnan(s) if with_nan else s == float("inf")
+            s2, c2 = mt.dist_stats(t, float("inf"))
+            assert c2 == int(np.isfinite(d).sum()) == int((d < np.float32(np.inf)).sum())
+            assert (c, c2) == (mt.dist_stats(t, th)[1], mt.dist_stats(t, float("inf"))[1])
+    fin = np.where(np.isfinite(body), body, np.float32(0.1))
+    s, c = mt.dist_stats(torch.from_numpy(fin).to(dev), th)
+    assert s == pytest.approx(math.fsum(fin.astype(np.float64)), rel=len(fin) * 2.0 ** -53) and c == int((fin < t32).sum())
 
 
 def _mc_mesh(D=48, r0=0.85, centre=(0.0, 0.0, 0.0), scale=1.0):
@@ -83,43 +115,62 @@ def _mc_mesh(D=48, r0=0.85, centre=(0.0, 0.0, 0.0), scale=1.0):
     return m
 
 
+def _soup_device(verts32, dev):
+    """a soup (F*3,3) f32 both ways the kernels read triangles: unindexed (faces = NULL) and indexed by 0, 1, 2, ..."""
+    v = torch.from_numpy(np.ascontiguousarray(verts32, np.float32)).to(dev)
+    F = len(v) // 3
+    return (v, None, F), (v, torch.arange(3 * F, device=dev, dtype=torch.int32).view(F, 3), F)
+
+
+def _sample_points(tri, cum, u, dev):
+    from cnr_amd import _C
+    out = torch.empty(len(u), 3, device=dev)
+    _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), out)
+    return out
+
+
 def test_sample_surface_matches_the_restatement(mt, dev):
-    rng = np.random.default_rng(4)
-    meshes = [_mc_mesh(33), _mc_mesh(64, 0.6, (0.2, 0.0, 0.1), 3.0)]
     from cnr_amd import vis
-    v = rng.normal(size=(300, 3)) * 2 + 4
-    meshes.append(vis.Mesh(v, rng.integers(0, 300, (500, 3))))
-    for m in meshes:
+    v, f, us = K.sampling_random_inputs()
+    meshes = [_mc_mesh(33), _mc_mesh(64, 0.6, (0.2, 0.0, 0.1), 3.0), vis.Mesh(v, f)]
+    for m, u in zip(meshes, us):
         tri = mt._mesh_device(m, dev)
         area, cum = mt._area_scan(tri)
         T = K.triangles(m.vertices, m.faces)
         np.testing.assert_allclose(area.cpu().numpy(), K.face_areas(T), rtol=1e-12, atol=0)
-        u = rng.random((20000, 3))
-        face, pts, cum_r = K.sample_surface(T, u)
+        face, pts, cum_r, near = K.sampling_near_boundaries(T, u)
         np.testing.assert_allclose(cum.cpu().numpy(), cum_r, rtol=1e-12)
-        out = torch.empty(len(u), 3, device=dev)
-        from cnr_amd import _C
-        _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), out)
+        out = _sample_points(tri, cum, u, dev)
         got = out.cpu().numpy()
-        # the same face wherever u0 * total is not within 1e-12 (relative) of a prefix boundary
-        target = u[:, 0] * cum_r[-1]
-        near = np.abs(cum_r[np.minimum(face, len(cum_r) - 1)] - target) < 1e-12 * cum_r[-1]
-        near |= np.abs(cum_r[np.maximum(face - 1, 0)] - target) < 1e-12 * cum_r[-1]
-        ok = ~near
-        np.testing.assert_allclose(got[ok], pts[ok], rtol=0, atol=1e-6 * (1 + np.abs(pts[ok]).max()))
-        a1 = torch.empty_like(out)
-        _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), a1)
-        assert torch.equal(out, a1)
+        # the same face wherever u0 * total is not within 1e-12 (relative) of a prefix boundary: that band is 2e-12 of the total
+        # per boundary, 4e-3 samples are expected in it, and none of this seed's draws is (test_metrics_host.py checks the same)
+        assert near.sum() == 0
+        np.testing.assert_allclose(got, pts, rtol=0, atol=1e-6 * (1 + np.abs(pts).max()))
+        assert torch.equal(out, _sample_points(tri, cum, u, dev))
 
 
-def _random_box(rng, centre, ext):
-    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-    q = q * np.sign(np.diag(r))
-    if np.linalg.det(q) < 0:
-        q[:, 0] *= -1
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = q, -q @ np.asarray(centre)
-    return T, np.asarray(ext, np.float64)
+@pytest.mark.parametrize("which", ["many", "single"])
+def test_sample_surface_is_exact_on_dyadic_input(mt, dev, which):
+    """Areas, prefixes, targets and points of K.dyadic_sampling_fixture are exact in fp64 however they are evaluated
+    (test_metrics_host.py proves it in rational arithmetic), so everything is compared bit for bit: u0 = 0, u0 on a prefix
+    boundary (the lower face; the first of equal prefixes), one ulp either side, zero-area faces, a + b == 1 and 1 + 2^-52."""
+    verts, u = K.dyadic_sampling_fixture() if which == "many" else K.dyadic_single_face()
+    T = K.triangles(verts)
+    face, pts, cum_r = K.sample_surface(T, u)
+    outs = []
+    for tri in _soup_device(verts, dev):
+        area, cum = mt._area_scan(tri)
+        assert np.array_equal(area.cpu().numpy(), K.face_areas(T)) and np.array_equal(cum.cpu().numpy(), cum_r)
+        out = _sample_points(tri, cum, u, dev)
+        got = out.cpu().numpy()
+        wrong = np.flatnonzero((got != pts).any(1))
+        assert len(wrong) == 0, (wrong[:5], u[wrong[:5]], got[wrong[:5]], pts[wrong[:5]], face[wrong[:5]])
+        assert torch.equal(out, _sample_points(tri, cum, u, dev))
+        outs.append(out)
+    assert torch.equal(outs[0], outs[1])
+
+
+_random_box = K.random_box
 
 
 def test_clip_matches_the_restatement(mt, dev):
@@ -146,6 +197,108 @@ def test_clip_matches_the_restatement(mt, dev):
     # outside everything: nothing
     T, ext = _random_box(rng, (10.0, 0.0, 0.0), (0.5, 0.5, 0.5))
     assert mt._clip(mt._mesh_device(_mc_mesh(33), dev), mt.box_planes(T, ext)) is None
+
+
+def _check_clip_rows(mt, tri_dev, tri64, planes, general=True):
+    """mt._clip against K.clip_box row for row: the same triangle count, (face, fan) order and corner order.  The kernel
+    evaluates each corner in fp64 and rounds once to fp32; its fp64 value differs from numpy's by a few units of 2^-53 (fused
+    multiply-adds; t = da / (da - db) is well conditioned, da and db have opposite signs), so each coordinate lies within one
+    fp32 spacing of float32(ref), and a rounding boundary between the two fp64 values has probability 2^-53 / 2^-24 = 2e-9:
+    at most 1 coordinate in 10^4 may differ from float32(ref) at all."""
+    ref, counts, closest = K.clip_box_info(tri64, planes)
+    if general:
+        assert closest >= 1e-9 * np.abs(tri64).max(), closest    # the kept / dropped decisions cannot differ (test_metrics_host.py)
+    out = mt._clip(tri_dev, planes)
+    assert out is not None and len(ref) and out[2] == len(ref) and out[0].shape == (3 * len(ref), 3)
+    got = out[0].cpu().numpy().reshape(-1, 3, 3)
+    ref32 = ref.astype(np.float32)
+    err = np.abs(got.astype(np.float64) - ref32.astype(np.float64))
+    bad = np.flatnonzero((err > np.spacing(np.abs(ref32)).astype(np.float64)).any((1, 2)))
+    face_of = np.repeat(np.arange(len(counts)), counts)
+    assert len(bad) == 0, (len(bad), len(ref), bad[:4], face_of[bad[:4]], got[bad[:2]], ref32[bad[:2]])
+    differ = int((got != ref32).sum())
+    print("clip: %d faces -> %d triangles, %d of %d coordinates off float32(ref), closest dist %.3g"
+          % (len(tri64), len(ref), differ, got.size, closest))
+    assert differ * 10 ** 4 <= got.size, (differ, got.size)
+    again = mt._clip(tri_dev, planes)
+    assert torch.equal(out[0], again[0])
+    return out
+
+
+@pytest.mark.parametrize("F,verts,T,ext", K.clip_soup_cases(), ids=["F%d" % c[0] for c in K.clip_soup_cases()])
+def test_clip_rows_of_random_soups(mt, dev, F, verts, T, ext):
+    planes = mt.box_planes(T, ext)
+    soup, indexed = _soup_device(verts, dev)
+    assert soup[2] == F
+    out = _check_clip_rows(mt, soup, K.triangles(verts), planes)
+    assert torch.equal(out[0], _check_clip_rows(mt, indexed, K.triangles(verts), planes)[0])
+
+
+def test_clip_rows_of_an_indexed_sphere(mt, dev):
+    m = _mc_mesh(48)
+    T, ext = K.random_box(np.random.default_rng(22), (0.1, 0.0, -0.2), (1.2, 0.9, 1.0))
+    out = _check_clip_rows(mt, mt._mesh_device(m, dev), K.triangles(m.vertices, m.faces), mt.box_planes(T, ext))
+    assert 1000 < out[2] < len(m.faces)
+
+
+def test_clip_rows_for_every_fan_count(mt, dev):
+    """faces that clip to 0, 1, ... 7 triangles (the 9-vertex polygon is constructed: K.hexagon_triangle), shuffled so that
+    every bit of the per-lane count is mixed within every wave"""
+    verts = K.fan_soup()
+    planes = mt.box_planes(*K.UNIT_BOX)
+    counts = K.clip_box_info(K.triangles(verts), planes)[1]
+    assert set(counts) == set(range(8))
+    for tri in _soup_device(verts, dev):
+        _check_clip_rows(mt, tri, K.triangles(verts), planes)
+
+
+def test_clip_rows_with_corners_exactly_on_the_planes(mt, dev):
+    """dist == 0 is inside (>=).  All dists and intersections of K.on_plane_soup are exact, so the decisions are the
+    restatement's; a face that only touches the box comes out as zero-area triangles, as the restatement emits them."""
+    verts, counts = K.on_plane_soup()
+    planes = mt.box_planes(*K.UNIT_BOX)
+    for tri in _soup_device(verts, dev):
+        out = _check_clip_rows(mt, tri, K.triangles(verts), planes, general=False)
+        assert out[2] == counts.sum()
+        got = out[0].double().cpu().numpy().reshape(-1, 3, 3)
+        assert np.array_equal(got, K.clip_box(K.triangles(verts), planes))       # exact input: exact output
+        first = np.cumsum(counts) - counts
+        assert (got[first[3]] == verts[9]).all()                                 # touched by one corner: that corner three times
+
+
+def test_clip_scan_with_more_than_1024_blocks(mt, dev):
+    """F > 262144 faces are more than 1024 blocks of 256: every thread of clip_scan_kernel owns a run of `per` = 2 block
+    counts.  Clipping is per face, so a verified soup tiled k times gives its verified output k times, bit for bit."""
+    F, verts, T, ext = K.clip_soup_cases()[-1]
+    planes = mt.box_planes(T, ext)
+    small = _check_clip_rows(mt, _soup_device(verts, dev)[0], K.triangles(verts), planes)
+    k = 263
+    assert F * k > 262144 and (F * k) % 256 != 0 and -(-F * k // 256) > 1024
+    for tri in _soup_device(np.tile(verts, (k, 1)), dev):
+        big = mt._clip(tri, planes)
+        assert big[2] == k * small[2]
+        assert torch.equal(big[0].view(k, -1), small[0].view(1, -1).expand(k, -1))
+        assert torch.equal(big[0], mt._clip(tri, planes)[0])
+
+
+def test_face_area_scan_with_more_than_1024_blocks(mt, dev):
+    """F > 1048576 faces are more than 1024 blocks of 1024: fa_blocks_scan_kernel's `per` = 2.  The areas are the small
+    soup's, tiled, bit for bit; the prefix against numpy's sequential fp64 cumsum at 1e-12 (sqrt(F) 2^-53 = 1e-13 is the
+    expected difference of two summation orders), and it never decreases."""
+    F, verts, _, _ = K.clip_soup_cases()[-1]
+    small_area, small_cum = mt._area_scan(_soup_device(verts, dev)[0])
+    ref = K.face_areas(K.triangles(verts))
+    np.testing.assert_allclose(small_area.cpu().numpy(), ref, rtol=1e-12, atol=0)
+    np.testing.assert_allclose(small_cum.cpu().numpy(), np.cumsum(ref), rtol=1e-12, atol=0)
+    k = 1049
+    assert F * k > 1048576 and (F * k) % 1024 != 0 and -(-F * k // 1024) > 1024
+    for tri in _soup_device(np.tile(verts, (k, 1)), dev):
+        area, cum = mt._area_scan(tri)
+        assert torch.equal(area.view(k, F), small_area.view(1, F).expand(k, F))
+        np.testing.assert_allclose(cum.cpu().numpy(), np.cumsum(area.cpu().numpy()), rtol=1e-12, atol=0)
+        assert bool((cum[1:] >= cum[:-1]).all())
+        area2, cum2 = mt._area_scan(tri)
+        assert torch.equal(area, area2) and torch.equal(cum, cum2)
 
 
 @pytest.mark.parametrize("path", METRIC_GOLDEN, ids=[os.path.basename(p)[:-4] for p in METRIC_GOLDEN])

@@ -242,6 +242,136 @@ def test_golden_metric_fixtures_exist_and_stay_small():
     assert any(a != b for a, b in sizes)
 
 
+# ---- the fixtures of test_metrics_gpu.py: each condition they rest on, from the restatement alone -----------------------------
+def _mc_mesh_cpu(D=48, r0=0.85, centre=(0.0, 0.0, 0.0), scale=1.0):
+    """test_metrics_gpu._mc_mesh with the numpy marching cubes (the two agree to 2e-6, test_meshing_gpu.py)"""
+    import mc_cpu as M
+    from cnr_amd import vis
+    v, n, f = M.marching_cubes(M.sphere(D, r0, 4.0, centre))
+    m = vis.Mesh(v, f, n)
+    m.apply_translation([-0.5, -0.5, -0.5]).apply_scale(2.0 * scale)
+    return m
+
+
+def _general_clip_cases():
+    from cnr_amd import metrics
+    for F, v, T, ext in K.clip_soup_cases():
+        yield "soup%d" % F, K.triangles(v), metrics.box_planes(T, ext)
+    m = _mc_mesh_cpu(48)
+    T, ext = K.random_box(np.random.default_rng(22), (0.1, 0.0, -0.2), (1.2, 0.9, 1.0))
+    yield "sphere", K.triangles(m.vertices, m.faces), metrics.box_planes(T, ext)
+    yield "fans", K.triangles(K.fan_soup()), metrics.box_planes(*K.UNIT_BOX)
+
+
+def test_general_clip_fixtures_decide_far_from_rounding():
+    """Every kept / dropped decision of the general-position cases is taken at |dist| >= 1e-9 S (S the largest coordinate),
+    seven orders above the 2^-53 S by which two fp64 evaluations of a dist can differ: the GPU takes the same decisions, so
+    its output can be compared row for row."""
+    for name, tri, planes in _general_clip_cases():
+        out, counts, closest = K.clip_box_info(tri, planes)
+        assert closest >= 1e-9 * np.abs(tri).max(), (name, closest)
+        assert len(out) == counts.sum() > 0 and len(counts) == len(tri), name
+        if name.startswith("soup") and len(tri) >= 63:
+            assert (counts == 0).any() and (counts >= 3).any(), name
+
+
+def test_fan_soup_has_every_triangle_count_mixed_within_a_wave():
+    from cnr_amd import metrics
+    tri = K.triangles(K.fan_soup())
+    _, counts, _ = K.clip_box_info(tri, metrics.box_planes(*K.UNIT_BOX))
+    hist = np.bincount(counts, minlength=8)
+    assert len(hist) == 8 and (hist > 0).all(), hist                   # 0 .. 7, and no face beyond 9 vertices
+    assert hist[7] >= 8                                                # the eight constructed hexagon cuts
+    # the construction itself, unperturbed: 9 vertices
+    _, c, closest = K.clip_box_info(K.hexagon_triangle()[None], metrics.box_planes(*K.UNIT_BOX))
+    assert c.tolist() == [7] and closest > 1e-3
+    # each of the three count bits is set in some lanes and clear in others of every full wave
+    full = counts[:len(counts) // 64 * 64].reshape(-1, 64)
+    for b in range(3):
+        bit = (full >> b) & 1
+        assert ((bit.sum(1) > 0) & (bit.sum(1) < 64)).all(), b
+    assert len(counts) % 256 != 0 and len(counts) > 256
+
+
+def test_on_plane_fixture_is_exact_and_touching_faces_survive_as_zero_area():
+    from cnr_amd import metrics
+    v, want = K.on_plane_soup()
+    tri = K.triangles(v)
+    planes = metrics.box_planes(*K.UNIT_BOX)
+    assert np.array_equal(np.abs(planes[:, :3]).sum(1), np.full(6, 0.5)) and np.array_equal(np.abs(planes[:, 3:]).sum(1), np.ones(6))
+    out, counts, closest = K.clip_box_info(tri, planes)
+    assert closest == 0.0 and counts.tolist() == want.tolist()
+    assert np.array_equal(out * 1024, np.round(out * 1024))            # dyadic: the same in any fp64 evaluation
+    area = K.face_areas(out)
+    first = np.cumsum(counts) - counts
+    assert area[first[3]] == 0.0 and (out[first[3]] == tri[3][0]).all()        # touched by one corner from outside
+    assert area[first[0]] == K.face_areas(tri)[0] and (area[first[1]:first[1] + 2] == 0).all()
+    assert (np.abs(out) <= 0.5).all()
+
+
+def _exact_sampling(verts, u):
+    """the sampling of a soup in rational arithmetic -> (face, points as floats): exact, or an AssertionError"""
+    from fractions import Fraction as Fr
+    tri = [[[Fr(float(x)) for x in p] for p in t] for t in np.asarray(verts, np.float64).reshape(-1, 3, 3)]
+    area = [abs((t[1][0] - t[0][0]) * (t[2][1] - t[0][1]) - (t[1][1] - t[0][1]) * (t[2][0] - t[0][0])) / 2 for t in tri]
+    cum = [sum(area[:k + 1]) for k in range(len(area))]
+    faces, pts = [], []
+    for u0, a, b in u:
+        target = Fr(float(u0)) * cum[-1]
+        f = next(k for k in range(len(cum)) if cum[k] >= target)
+        a, b = Fr(float(a)), Fr(float(b))
+        if a + b > 1:
+            a, b = abs(a - 1), abs(b - 1)
+        t = tri[f]
+        p = [(t[1][k] - t[0][k]) * a + (t[2][k] - t[0][k]) * b + t[0][k] for k in range(3)]
+        faces.append(f)
+        pts.append([float(x) for x in p])
+        assert all(Fr(x) == y for x, y in zip(pts[-1], p))             # the point is an fp64 number
+    return np.array(faces), np.array(pts), [float(c) for c in cum]
+
+
+@pytest.mark.parametrize("which", ["many", "single"])
+def test_dyadic_sampling_fixture_is_exact(which):
+    import math
+    verts, u = K.dyadic_sampling_fixture() if which == "many" else K.dyadic_single_face()
+    tri = K.triangles(verts)
+    area = K.face_areas(tri)
+    cum = np.cumsum(area)
+    assert cum.tolist() == [math.fsum(area[:k + 1]) for k in range(len(area))]
+    assert math.frexp(cum[-1])[0] == 0.5                               # a power of two: u0 * total is exact
+    face, pts, cum_r = K.sample_surface(tri, u)
+    want_face, want_pts, want_cum = _exact_sampling(verts, u)
+    assert cum_r.tolist() == want_cum and np.array_equal(face, want_face)
+    assert np.array_equal(pts, want_pts.astype(np.float32))
+    # what the draws cover
+    assert (u[:, 0] == 0).any() and (u[:, 0] == 1.0 - 2.0 ** -53).any()
+    s = u[:, 1] + u[:, 2]
+    assert (s == 1.0).any() and (s == 1.0 + 2.0 ** -52).any() and (s < 1).any() and (s > 1.25).any()
+    if which == "many":
+        assert area[0] == 0 and area[-1] == 0 and (area[1:-1] == 0).any() and len(np.unique(cum)) < len(cum)
+        target = u[:, 0] * cum[-1]
+        on = np.isin(target, cum)
+        assert set(target[on]) == set(cum) - {cum[-1]}                 # every boundary below the total is hit exactly ...
+        assert (cum[face[on]] == target[on]).all()                     # ... and belongs to the face that ends there:
+        assert (face[on] == np.searchsorted(cum, target[on], "left")).all()       # the first of equal prefixes
+        assert face.max() == len(cum) - 2 and face.min() == 0          # never the trailing zero-area face; u0 = 0 -> face 0
+        assert set(face) == {0} | set(np.flatnonzero(area))             # every face with an area, and no other but face 0
+    else:
+        assert len(tri) == 1 and (face == 0).all()
+
+
+def test_random_sampling_draws_stay_off_the_prefix_boundaries():
+    """The random comparison of test_metrics_gpu.py leaves out no sample: none of the committed seed's draws lies within
+    1e-12 of a prefix boundary (about 4e-3 are expected to).  The marching-cubes meshes here come from the numpy restatement,
+    whose vertices agree with the GPU's to 2e-6; the GPU test asserts the same on its own meshes."""
+    from cnr_amd import vis
+    v, f, us = K.sampling_random_inputs()
+    meshes = [_mc_mesh_cpu(33), _mc_mesh_cpu(64, 0.6, (0.2, 0.0, 0.1), 3.0), vis.Mesh(v, f)]
+    for m, u in zip(meshes, us):
+        _, _, _, near = K.sampling_near_boundaries(K.triangles(m.vertices, m.faces), u)
+        assert near.sum() == 0
+
+
 # ---- build and ABI -----------------------------------------------------------------------------------------------------
 def test_metric_build_is_warning_free():
     """csrc/metric.hip, compiled with the Makefile's own compiler and flags (into a temporary file), gives no warning"""

@@ -85,6 +85,39 @@ def test_unproject_depth_limits_and_order_gpu(dev, cnr):
     assert np.array_equal(pc.colors_device.cpu().numpy(), (rgb[[1, 3, 6], [2, 3, 1]].astype(np.float64) / 255.0).astype(np.float32))
 
 
+def test_unproject_with_more_than_1024_blocks_gpu(dev, cnr):
+    """1100 x 960 = 1 056 000 pixels are 1032 blocks of 1024: every thread of blocks_scan_kernel owns a run of `per` = 2 block
+    counts, as on a full Replica (1200 x 680) or ScanNet (1296 x 968) frame.  A third of the pixels carry the mask; depths in
+    (0, 8] with zeros, values above 8 and 8 itself.  The bounds are those of the Replica fixture above: the kept pixels and
+    their order equal, colours equal, coordinates (below 16 m) within 1e-5 m."""
+    W, H = 1100, 960
+    assert W * H > 1024 * 1024 + 1 and W * H < 1_100_000 and (W * H) % 1024 != 0
+    rng = np.random.default_rng(23)
+    depth = (rng.random((W, H)) * 9.0).astype(np.float32)
+    depth[rng.random((W, H)) < 0.05] = 0.0
+    depth[rng.random((W, H)) < 0.01] = 8.0
+    mask = rng.integers(0, 3, (W, H)).astype(np.int32)
+    image = rng.integers(0, 256, (W, H, 3)).astype(np.uint8)
+    ang = 0.3
+    T = np.eye(4)
+    T[:3, :3] = [[np.cos(ang), -np.sin(ang), 0.0], [np.sin(ang), np.cos(ang), 0.0], [0.0, 0.0, 1.0]]
+    T[:3, 3] = [0.5, -1.0, 2.0]
+    fx, fy, cx, cy = 600.0, 610.0, 549.5, 479.5
+    sample = {"image": image, "depth": depth, "obj_mask": mask, "T": T}
+    idx, want_p, want_c = RC.unproject(sample, 1, fx, fy, cx, cy)
+    assert 0.25 * W * H < len(idx) < 0.33 * W * H and np.abs(want_p).max() < 16.0
+    assert (depth.reshape(-1)[idx] == 8.0).any() and (depth[mask == 1] > 8.0).any() and (depth[mask == 1] == 0.0).any()
+    K = cnr.dataset.PinholeIntrinsics(W, H, fx, fy, cx, cy)
+    pc = cnr.utils._unproject_frames([(image, depth, mask, T)], [1], K, dev)
+    assert len(pc) == len(idx)
+    err = np.abs(pc.points - want_p).max()
+    print("points", len(pc), "max coordinate error %.3g m" % err)
+    assert err < 1e-5, err
+    assert np.array_equal(pc.colors_device.cpu().numpy(), want_c.astype(np.float32))
+    again = cnr.utils._unproject_frames([(image, depth, mask, T)], [1], K, dev)
+    assert torch.equal(pc.points_device, again.points_device) and torch.equal(pc.colors_device, again.colors_device)
+
+
 def _check_down_sample(cnr, dev, p32, c32, voxel):
     P, C = torch.from_numpy(p32).to(dev), (torch.from_numpy(c32).to(dev) if c32 is not None else None)
     out = cnr.utils.voxel_down_sample_device(P, C, voxel)
@@ -110,6 +143,18 @@ def test_voxel_down_sample_gpu(dev, cnr):
     out = _check_down_sample(cnr, dev, p, None, 0.2)
     assert out[1] is None and int(out[3].max()) > 100         # long runs: many points per voxel
     _check_down_sample(cnr, dev, p[:1], c[:1], 0.01)
+
+
+def test_voxel_down_sample_with_more_than_1024_blocks_gpu(dev, cnr):
+    """1 060 001 sorted keys are 1036 blocks of 1024: blocks_scan_kernel's `per` = 2 under the voxel segments.  A 1 m cube at
+    1 cm: about 650 000 occupied voxels, runs of 1 to 9 points."""
+    rng = np.random.default_rng(12)
+    n = 1_060_001
+    assert -(-n // 1024) > 1024 and n % 1024 != 0
+    p = (rng.random((n, 3)) + [3.0, -2.0, 0.7]).astype(np.float32)
+    c = rng.random((n, 3)).astype(np.float32)
+    out = _check_down_sample(cnr, dev, p, c, 0.01)
+    assert 600_000 < len(out[0]) < 700_000 and int(out[3].sum()) == n
 
 
 def test_voxel_down_sample_points_on_voxel_faces_gpu(dev, cnr):
