@@ -121,6 +121,15 @@ SIGNATURES = {
     "cnr_teaser_graph": [_vp, _vp, _i, _f, _vp, _vp, _vp],
     "cnr_clique_workspace_bytes": [_i, _i],
     "cnr_clique_search": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "cnr_tsdf_depth_image": [_vp, _vp, _i64, _i, _d, _d, _vp, _vp],
+    "cnr_tsdf_touch_slots": [_i, _i],
+    "cnr_tsdf_touch": [_vp, _i, _i, _d, _d, _d, _d, _vp, _d, _d, _i, _vp, _vp, _vp, _vp],
+    "cnr_tsdf_integrate": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp, _vp],
+    "cnr_tsdf_extract_workspace_bytes": [_i64],
+    "cnr_tsdf_extract_count": [_vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "cnr_tsdf_extract_emit": [_vp, _vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp, _vp],
+    "cnr_radius_cell_keys": [_vp, _i64, _d, _vp, _vp, _vp],
+    "cnr_radius_count": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _vp, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
@@ -184,7 +193,8 @@ _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_by
               "cnr_mc_workspace_bytes", "cnr_nn_workspace_bytes", "cnr_dist_stats_workspace_bytes",
               "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes",
               "cnr_unproject_workspace_bytes", "cnr_points_min_workspace_bytes", "cnr_voxel_segments_workspace_bytes",
-              "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes", "cnr_clique_workspace_bytes"}
+              "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes", "cnr_clique_workspace_bytes",
+              "cnr_tsdf_touch_slots", "cnr_tsdf_extract_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -9,7 +9,8 @@ kernels, cnr_composite_fwd's termination); the reference moves the occupancies t
 The rest of that file for Replica sequences is below it: ``get_all_poses`` (point-cloud accumulation), ``align_poses`` (the
 reference's bookkeeping around a pluggable solver: the default is the multi-start GPU ICP ``IcpSolver``, and ``TeaserSolver``
 is a TEASER-style global solver on the kernels of csrc/teaser.hip) and ``register_dataset`` (the driver behind ``dataset.get_dataset(cfg, register=True)``), on the kernels of
-csrc/pointcloud.hip.  ScanNet registration is not here.
+csrc/pointcloud.hip.  ScanNet sequences register on request (``tsdf=True``): their background cloud is a TSDF
+fusion on the kernels of csrc/tsdf.hip, their objects' clouds come from the loader.
 """
 import math
 import os
@@ -126,22 +127,35 @@ def get_uncertainty_fields(inst_dict, bbox3d_dict, count_dict, pe_dict, fc_occ_m
 
 
 # ---- point clouds, alignment, sub-categorisation (src/category_registration.py:18-56, :179-324) -------------------------
-# DESIGN.md §3.9.  Replica only; align_poses(..., solver=) takes IcpSolver (the default) or TeaserSolver.
-def get_all_poses(inst_dict, sample_dict, intrinsic_open3d, name="replica", depth_scale=0.001, max_depth=8.0):
-    """:18-56, Replica branch.  Every instance of every class gets 'pcs': its pixels of all its frames as one cloud at 1 cm.
-    The background (class 0) gets 'pcs' too and 'bbox3D', the oriented box of that cloud with its true extents (no 10 cm
-    floor)."""
+# DESIGN.md §3.9 and §3.10.  align_poses(..., solver=) takes IcpSolver (the default) or TeaserSolver.
+def get_all_poses(inst_dict, sample_dict, intrinsic_open3d, name="replica", depth_scale=0.001, max_depth=8.0, tsdf=False):
+    """:18-56.  Replica: every instance of every class gets 'pcs', its pixels of all its frames as one cloud at 1 cm.  ScanNet
+    (only with tsdf=True): an instance's 'pcs' is what the loader gathered frame by frame, down-sampled to 1 cm; an instance
+    without one (or with an empty one) gets T_obj = eye(4) and pcs = None.  The background (class 0) gets 'pcs' too -- for
+    ScanNet from a TSDF volume (utils.accumulate_pointcloud_tsdf) -- and 'bbox3D', the oriented box of that cloud with its true
+    extents (no 10 cm floor)."""
     from . import metrics
-    from .utils import BoundingBox, accumulate_pointcloud
-    if name != "replica":
-        raise NotImplementedError("get_all_poses: ScanNet registration needs open3d's TSDF integration and "
-                                  "geometry_segmentation, which are not part of this package")
+    from .utils import BoundingBox, accumulate_pointcloud, accumulate_pointcloud_tsdf
+    if name != "replica" and not tsdf:
+        raise NotImplementedError("get_all_poses: ScanNet registration fuses the background in a TSDF volume and takes the "
+                                  "objects' clouds from refined masks on disk (geometry_segmentation is not part of this "
+                                  "package); it runs only on request: tsdf=True")
     for cls_id, entries in inst_dict.items():
         if cls_id != 0:
             for inst_id, entry in entries.items():
-                entry["pcs"] = accumulate_pointcloud(int(inst_id), entry["frame_info"], sample_dict, intrinsic_open3d)
+                if name == "replica":
+                    entry["pcs"] = accumulate_pointcloud(int(inst_id), entry["frame_info"], sample_dict, intrinsic_open3d)
+                elif entry.get("pcs") is None or len(entry["pcs"]) == 0:
+                    print(f"{inst_id} is not detected from semantically refined geometry segmentations")
+                    entry["T_obj"], entry["pcs"] = np.eye(4), None
+                else:
+                    entry["pcs"] = entry["pcs"].voxel_down_sample(0.01)
             continue
-        cloud = accumulate_pointcloud(0, entries["frame_info"], sample_dict, intrinsic_open3d)
+        if name == "replica":
+            cloud = accumulate_pointcloud(0, entries["frame_info"], sample_dict, intrinsic_open3d)
+        else:
+            cloud = accumulate_pointcloud_tsdf(0, entries["frame_info"], sample_dict, intrinsic_open3d, depth_scale=depth_scale,
+                                               max_depth=max_depth)
         to_box, extents = metrics.oriented_bounds(cloud.points)
         from_box = np.linalg.inv(to_box)
         box = BoundingBox()
@@ -589,12 +603,16 @@ def write_registration_result(inst_dict, path):
         _RegistrationPickler.dump(inst_dict, f)
 
 
-def register_dataset(dataset, cfg, solver=None):
-    """src/dataset.py:72-88 for a Replica dataset whose frames are loaded: get_all_poses -> get_uncertainty_fields ->
-    align_poses, the 'pcs' entries deleted, the result written to <root_dir>/inst_dict.pkl."""
-    if dataset.name != "replica":
-        raise NotImplementedError("registration of ScanNet sequences needs open3d's TSDF integration and "
-                                  "geometry_segmentation, which are not part of this package")
+def register_dataset(dataset, cfg, solver=None, tsdf=False):
+    """src/dataset.py:72-88 for a dataset whose frames are loaded: get_all_poses -> get_uncertainty_fields -> align_poses, the
+    'pcs' entries deleted, the result written to <root_dir>/inst_dict.pkl.  A ScanNet dataset needs tsdf=True, here and when it
+    was loaded (get_dataset(cfg, register=True, tsdf=True): the loader gathers the objects' clouds only then)."""
+    if dataset.name != "replica" and not tsdf:
+        raise NotImplementedError("registration of ScanNet sequences (TSDF fusion of the background, objects from refined "
+                                  "masks on disk) runs only on request: tsdf=True")
+    if dataset.name != "replica" and not getattr(dataset, "_accumulate", False):
+        raise ValueError("register_dataset(tsdf=True): the ScanNet dataset was loaded without the objects' clouds; load it with "
+                         "get_dataset(cfg, register=True, tsdf=True)")
     if not getattr(cfg, "load_pretrained", False):
         raise NotImplementedError("get_uncertainty_fields: registration.load_pretrained is false; only per-object checkpoints "
                                   "under registration.weight_root give the fields that rank a class's instances (the "
@@ -602,12 +620,12 @@ def register_dataset(dataset, cfg, solver=None):
     inst_dict = dataset.inst_dict
     boxes, counts, encoders, fields = {}, {}, {}, {}
     get_all_poses(inst_dict, dataset.sample_dict, dataset.intrinsic_open3d, name=dataset.name, depth_scale=cfg.depth_scale,
-                  max_depth=cfg.max_depth)
+                  max_depth=cfg.max_depth, tsdf=tsdf)
     get_uncertainty_fields(inst_dict, boxes, counts, encoders, fields, cfg, name=dataset.name, load_pretrained=True)
     etas = {k: getattr(cfg, k) for k in ("eta1", "eta2", "eta3") if hasattr(cfg, k)}
     align_poses(inst_dict, boxes, counts, encoders, fields, name=dataset.name,
                 multi_init_pose=getattr(cfg, "multi_init_pose", True), device=dataset._parse_device(), solver=solver, **etas)
     for cls_id, entries in inst_dict.items():          # the clouds are intermediate results: not part of the cache
         for entry in ([entries] if cls_id == 0 else entries.values()):
-            del entry["pcs"]
+            entry.pop("pcs", None)
     write_registration_result(inst_dict, os.path.join(dataset.root_dir, "inst_dict.pkl"))

@@ -6,7 +6,8 @@ instance table per label frame (ids in np.unique order, pixel count, bounds, cla
 arrays in the reference's (W, H) layout.  The per-instance decisions are host logic on the small table, in the reference's
 order and dtypes, quirks included.  The loaders read the cached registration result
 ``<dataset_dir>/inst_dict.pkl`` (``registration.load_registration_result``) with a restricted unpickler; without one,
-``get_dataset(cfg, register=True)`` runs category registration for Replica (category_registration.py)."""
+``get_dataset(cfg, register=True)`` runs category registration for Replica (category_registration.py), and
+``get_dataset(cfg, register=True, tsdf=True)`` for ScanNet sequences whose refined masks are on disk."""
 import glob
 import io
 import os
@@ -25,13 +26,14 @@ BATCH = 16                  # frames per upload
 DECODE_WORKERS = 16
 
 
-def get_dataset(cfg, register=False):
+def get_dataset(cfg, register=False, tsdf=False):
     """register=True: a Replica dataset without a usable cache runs category registration (category_registration.
-    register_dataset) and writes <dataset_dir>/inst_dict.pkl; the default raises NotImplementedError there, as before."""
+    register_dataset) and writes <dataset_dir>/inst_dict.pkl; the default raises NotImplementedError there, as before.
+    A ScanNet dataset does so only with tsdf=True as well (its background cloud is a TSDF fusion)."""
     if cfg.dataset_format == "Replica":
         return Replica(cfg, register=register)
     if cfg.dataset_format == "ScanNet":
-        return ScanNet(cfg, register=register)
+        return ScanNet(cfg, register=register, tsdf=tsdf)
     raise ValueError("Dataset format {} not found".format(cfg.dataset_format))
 
 
@@ -89,15 +91,23 @@ def load_registration_result(path):
         return RegistrationUnpickler(f).load()
 
 
+def _has_cache(root_dir, cfg):
+    return bool(getattr(cfg, "load_registration_result", False)) and os.path.exists(os.path.join(root_dir, "inst_dict.pkl"))
+
+
 def _load_inst_dict(dataset, cfg):
     register = getattr(dataset, "register", False)
     result_file = os.path.join(dataset.root_dir, "inst_dict.pkl")
-    if getattr(cfg, "load_registration_result", False) and os.path.exists(result_file):
+    if _has_cache(dataset.root_dir, cfg):
         dataset.inst_dict = load_registration_result(result_file)
         return
     if register and dataset.name == "replica":
         from . import category_registration
         category_registration.register_dataset(dataset, cfg)
+        return
+    if register and getattr(dataset, "tsdf", False):
+        from . import category_registration
+        category_registration.register_dataset(dataset, cfg, tsdf=True)
         return
     if dataset.name == "replica":
         raise NotImplementedError(
@@ -107,8 +117,8 @@ def _load_inst_dict(dataset, cfg):
     raise NotImplementedError(
         f"{result_file}: no cached registration result (registration.load_registration_result = "
         f"{getattr(cfg, 'load_registration_result', None)}).  Category-level registration of ScanNet sequences (open3d's TSDF "
-        "integration and geometry_segmentation, align_poses with TEASER++) is not part of this package; run it with the "
-        "reference once")
+        "integration and geometry_segmentation, align_poses with TEASER++) runs only on request and only from refined masks "
+        "on disk: get_dataset(cfg, register=True, tsdf=True)")
 
 
 # ---- decoding ----------------------------------------------------------------------------------------------------------
@@ -316,9 +326,12 @@ def _sorted_by_stem(pattern):
 
 
 class ScanNet(_Base):
-    def __init__(self, cfg, register=False):
+    def __init__(self, cfg, register=False, tsdf=False):
         self.name = "scannet"
-        self.register = register
+        self.register, self.tsdf = register, tsdf
+        # the objects' clouds are gathered frame by frame (src/dataset.py:385-400) only when registration is going to run
+        self._accumulate = bool(register and tsdf) and not _has_cache(cfg.dataset_dir, cfg)
+        self._frame_objects = {}
         self.device = cfg.data_device
         self.root_dir = cfg.dataset_dir
         j = lambda *p: os.path.join(self.root_dir, *p)
@@ -423,6 +436,30 @@ class ScanNet(_Base):
         for f, index in enumerate(idxs):
             r = reduced[index]
             self.sample_dict[r] = {"image": img[f], "depth": dep[f], "obj_mask": obj_mask[f], "T": self.poses[index], "frame_id": r}
+            if self._accumulate:
+                self._accumulate_objects(r, dev)
+
+    def _accumulate_objects(self, frame, dev):
+        """src/dataset.py:385-400: every kept object's pixels of this frame, unprojected, added to its 'pcs'"""
+        from .utils import PointCloud, _unproject_frames
+        objects = self._frame_objects.pop(frame, [])
+        if not objects:
+            return
+        s = self.sample_dict[frame]
+        # one upload of the frame and one read-back for all its objects
+        entry = (torch.zeros(s["image"].shape, dtype=torch.uint8, device=dev), torch.from_numpy(s["depth"]).to(dev),
+                 torch.from_numpy(s["obj_mask"]).to(dev), s["T"])
+        cloud, counts = _unproject_frames([entry] * len(objects), [int(o) for _, o in objects], self.intrinsic_open3d, dev,
+                                          return_counts=True)
+        at = 0
+        for (sem_cls, obj_id), n in zip(objects, counts):
+            part = PointCloud(cloud.points_device[at:at + int(n)])
+            at += int(n)
+            inst = self.inst_dict[sem_cls][obj_id]
+            if "pcs" not in inst:
+                inst["pcs"] = part
+            else:
+                inst["pcs"] += part
 
     def _frame_instances(self, frame, ids, stats, inst_to_cls, W, H):
         """src/dataset.py:339-383 on one frame's table -> keep (n,) bool; fills inst_dict"""
@@ -453,4 +490,6 @@ class ScanNet(_Base):
             min_x, min_y, max_x, max_y = bbox2d
             _add_frame_info(self.inst_dict, inst_to_cls[obj_id], obj_id, frame,
                             torch.from_numpy(np.array([min_x, max_x, min_y, max_y])))
+            if self._accumulate and obj_id != 0:
+                self._frame_objects.setdefault(frame, []).append((inst_to_cls[obj_id], obj_id))
         return keep

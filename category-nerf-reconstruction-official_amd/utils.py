@@ -225,6 +225,14 @@ class PointCloud:
         p, c, _, _ = voxel_down_sample_device(self.points_device, self.colors_device, voxel_size)
         return PointCloud(p.float(), c.float() if c is not None else None)
 
+    def remove_radius_outlier(self, nb_points, radius):
+        """open3d's remove_radius_outlier: the points with more than nb_points points of this cloud, themselves included, closer
+        than radius (radius_neighbour_counts) -> (the cloud of the kept points in their order, kept_index (m,) int64 device)"""
+        if len(self) == 0:
+            return PointCloud(self.points_device, self.colors_device), torch.zeros(0, dtype=torch.int64, device=self.points_device.device)
+        kept = torch.nonzero(radius_neighbour_counts(self.points_device, radius) > int(nb_points)).reshape(-1)
+        return PointCloud(self.points_device[kept], self.colors_device[kept] if self.colors_device is not None else None), kept
+
     def compute_point_cloud_distance(self, other):
         """per point of this cloud the distance to the nearest point of `other` -> (n,) f32 device tensor"""
         from . import metrics
@@ -238,9 +246,9 @@ def _intrinsics(intrinsic):
     return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
 
 
-def _unproject_frames(frames, inst_ids, intrinsic, dev):
+def _unproject_frames(frames, inst_ids, intrinsic, dev, return_counts=False):
     """frames: [(image (W,H,3) u8, depth (W,H) f32, obj_mask (W,H) i32, T_WC (4,4))], one instance id each -> PointCloud of all
-    frames' kept pixels in frame order.  One read-back (the counts) for all frames."""
+    frames' kept pixels in frame order.  One read-back (the counts) for all frames; return_counts: -> (cloud, points per entry)."""
     from . import _C
     lib = _C.load()
     fx, fy, cx, cy = _intrinsics(intrinsic)
@@ -264,7 +272,7 @@ def _unproject_frames(frames, inst_ids, intrinsic, dev):
         if c:
             _C.call("cnr_unproject_emit", d, m, im, W, H, inst_id, fx, fy, cx, cy, T, ws, points[o:o + c], colors[o:o + c])
         o += int(c)
-    return PointCloud(points, colors)
+    return (PointCloud(points, colors), counts) if return_counts else PointCloud(points, colors)
 
 
 def unproject_colored_pointcloud(rgb, depth, intrinsic_open3d, T_CW, device=None):
@@ -290,6 +298,207 @@ def accumulate_pointcloud(inst_id, inst_info_list, frame_samples, intrinsic_open
     if len(cloud) == 0:
         raise ValueError(f"instance {inst_id}: no pixel with a valid depth in its {len(frames)} frames")
     return cloud.voxel_down_sample(voxel_size)
+
+
+def unproject_pointcloud(depth, intrinsic_open3d, T_CW, device=None):
+    """src/utils.py:329-339: the pixels with a positive depth of one frame as a cloud without colours in the world frame.  depth
+    is the (H,W) image the reference hands to open3d; points come column by column (the kernel's order), not row by row, and a
+    depth beyond 8 m -- which the loaders have already zeroed -- is dropped."""
+    depth = depth.detach().cpu().numpy() if torch.is_tensor(depth) else np.asarray(depth)
+    d = np.ascontiguousarray(depth.T, dtype=np.float32)
+    cloud = _unproject_frames([(np.zeros(d.shape + (3,), np.uint8), d, np.ones(d.shape, np.int32),
+                                np.linalg.inv(np.asarray(T_CW, np.float64)))], [1], intrinsic_open3d, _cuda_device(device))
+    return PointCloud(cloud.points_device)
+
+
+# ---- TSDF fusion (src/utils.py:212-247) --------------------------------------------------------------------------------
+# DESIGN.md §3.10: open3d's ScalableTSDFVolume restated (equality with open3d is unverified), on the kernels of csrc/tsdf.hip.
+TSDF_UNIT = 16                       # voxels per unit edge (volume_unit_resolution)
+TSDF_AXIS_BITS = 21
+TSDF_BLOCK_BYTES = 20 * TSDF_UNIT ** 3          # tsdf, weight and three colours, f32, per unit
+DEFAULT_TSDF_BLOCK_BYTES = 32 << 30  # what a volume's blocks may take unless told otherwise (a room at 1 cm: about 1.6 GB)
+
+
+def tsdf_depth_image(depth, obj_mask, inst_id, depth_scale=0.001, max_depth=6.0):
+    """The depth image the volume sees, from a sample's metric (W,H) depth (device tensors): masked to obj_mask == inst_id,
+    uint16(trunc(depth / depth_scale)) in fp64 (wrapping like numpy's astype), u16 / 1000 in fp32 (open3d's own default scale,
+    whatever depth_scale is: the reference's quirk), 0 beyond max_depth -> (W,H) f32.  cnr_tsdf_depth_image: torch divides by a
+    scalar as a product with its reciprocal on the device, which is not this contract."""
+    from . import _C
+    depth, obj_mask = depth.to(torch.float32).contiguous(), obj_mask.to(device=depth.device, dtype=torch.int32).contiguous()
+    if depth.shape != obj_mask.shape or depth.numel() == 0:
+        raise ValueError("depth and obj_mask of one frame")
+    out = torch.empty_like(depth)
+    _C.call("cnr_tsdf_depth_image", depth, obj_mask, depth.numel(), int(inst_id), float(depth_scale), float(max_depth), out)
+    return out
+
+
+def tsdf_unit_tables(keys, frames):
+    """The torch side of cnr_tsdf_touch: keys (n,) int64 (negative = unused slot) with their frame numbers (n,), frames ascending
+    -> (units (U,) ascending int64, frame_ofs (U+1,) int64, frame_idx (M,) int32: per unit its frames ascending, neighbours
+    (U,3) int32: the +x, +y, +z unit or -1)"""
+    used = keys >= 0
+    keys, frames = keys[used], frames[used].to(torch.int64)
+    order = torch.sort(keys, stable=True)[1]               # stable: the frames, ascending on entry, stay so inside a unit
+    keys, frames = keys[order], frames[order]
+    head = torch.ones(len(keys), dtype=torch.bool, device=keys.device)
+    head[1:] = (keys[1:] != keys[:-1]) | (frames[1:] != frames[:-1])
+    keys, frames = keys[head], frames[head]
+    units, per_unit = torch.unique_consecutive(keys, return_counts=True)
+    frame_ofs = torch.zeros(len(units) + 1, dtype=torch.int64, device=keys.device)
+    frame_ofs[1:] = torch.cumsum(per_unit, 0)
+    nb = torch.full((len(units), 3), -1, dtype=torch.int32, device=keys.device)
+    if len(units):
+        for a in range(3):
+            shift = (2 - a) * TSDF_AXIS_BITS
+            inside = ((units >> shift) & ((1 << TSDF_AXIS_BITS) - 1)) < (1 << TSDF_AXIS_BITS) - 1
+            want = units + (1 << shift)
+            at = torch.searchsorted(units, want).clamp_(max=len(units) - 1)
+            nb[:, a] = torch.where(inside & (units[at] == want), at, torch.full_like(at, -1)).to(torch.int32)
+    return units.contiguous(), frame_ofs, frames.to(torch.int32).contiguous(), nb.contiguous()
+
+
+class TSDFVolume:
+    """ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) for one batch of frames: integrate_frames once, then
+    extract_point_cloud.  After integrate_frames: units, frame_ofs, frame_idx (and, on request, the kernel's slots),
+    neighbours, tsdf (U,4096), weight (U,4096), color (U,4096,3).  max_block_bytes bounds what the blocks (20 KB per unit) may
+    take; a larger volume raises CnrError before they are allocated."""
+
+    def __init__(self, voxel_length=0.01, sdf_trunc=0.04, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
+        if not (voxel_length > 0 and 0 < 2.0 * sdf_trunc <= TSDF_UNIT * voxel_length):
+            raise ValueError("TSDFVolume: voxel_length > 0 and 0 < sdf_trunc <= 8 voxel_length (a depth sample's [p - trunc, p + trunc] "
+                             "may span two units per axis, not three)")
+        self.voxel_length, self.sdf_trunc, self.max_block_bytes = float(voxel_length), float(sdf_trunc), int(max_block_bytes)
+        self.device = _cuda_device(device)
+        self.units = None
+
+    def integrate_frames(self, depths, colors, intrinsic, T_WC, keep_touch=False):
+        """depths (F,W,H) f32 as tsdf_depth_image gives them, colors (F,W,H,3) u8, T_WC (F,4,4) camera -> world.  Each frame's
+        touch slots are reduced to its distinct units at once, so the list that is sorted holds one entry per unit and frame;
+        keep_touch=True keeps the raw slots as touch_keys / touch_frames (F, slots) for inspection."""
+        from . import _C
+        lib, dev = _C.load(), self.device
+        if self.units is not None:
+            raise ValueError("TSDFVolume: integrate_frames runs once per volume")
+        fx, fy, cx, cy = _intrinsics(intrinsic)
+        depths = torch.as_tensor(depths).to(device=dev, dtype=torch.float32).contiguous()
+        colors = torch.as_tensor(colors).to(device=dev, dtype=torch.uint8).contiguous()
+        F, W, H = depths.shape
+        T_WC = np.ascontiguousarray(np.asarray(T_WC, np.float64).reshape(F, 4, 4))
+        if colors.shape != (F, W, H, 3) or F < 1:
+            raise ValueError("depths (F,W,H) and colors (F,W,H,3) of the same frames")
+        slots = int(lib.cnr_tsdf_touch_slots(W, H))
+        if slots < 0:
+            raise _C.CnrError(f"cnr_tsdf_touch: a {W} x {H} frame is refused ({slots})")
+        keys = torch.empty(F if keep_touch else 1, slots, device=dev, dtype=torch.int64)
+        tags = torch.empty(F if keep_touch else 1, slots, device=dev, dtype=torch.int32)
+        err = torch.zeros(1, device=dev, dtype=torch.int32)
+        T_dev = torch.from_numpy(T_WC).to(dev)
+        per_frame = []
+        for f in range(F):
+            k, t = (keys[f], tags[f]) if keep_touch else (keys[0], tags[0])
+            _C.call("cnr_tsdf_touch", depths[f], W, H, fx, fy, cx, cy, T_dev[f], self.voxel_length, self.sdf_trunc, f, k, t, err)
+            per_frame.append(torch.unique(k[k >= 0]))
+        if keep_touch:
+            self.touch_keys, self.touch_frames = keys, tags
+        frame_of = torch.repeat_interleave(torch.arange(F, device=dev), torch.tensor([len(k) for k in per_frame], device=dev))
+        self.units, self.frame_ofs, self.frame_idx, self.neighbours = tsdf_unit_tables(torch.cat(per_frame), frame_of)
+        U = len(self.units)
+        if int(err.item()):
+            raise _C.CnrError("cnr_tsdf_touch: a depth sample lies more than 2^20 units from the origin, is not a number, or touches "
+                              "three units on an axis")
+        if U * TSDF_BLOCK_BYTES > self.max_block_bytes:
+            raise _C.CnrError(f"TSDFVolume: the blocks of {U} units take {U * TSDF_BLOCK_BYTES} bytes, more than max_block_bytes = "
+                              f"{self.max_block_bytes}")
+        self.tsdf = torch.empty(U, TSDF_UNIT ** 3, device=dev, dtype=torch.float32)
+        self.weight = torch.empty(U, TSDF_UNIT ** 3, device=dev, dtype=torch.float32)
+        self.color = torch.empty(U, TSDF_UNIT ** 3, 3, device=dev, dtype=torch.float32)
+        if U:
+            T_CW = torch.from_numpy(np.ascontiguousarray(np.linalg.inv(T_WC))).to(dev)
+            _C.call("cnr_tsdf_integrate", self.units, U, self.frame_ofs, self.frame_idx, depths, colors, T_CW, F, W, H, fx, fy, cx, cy,
+                    self.voxel_length, self.sdf_trunc, self.tsdf, self.weight, self.color)
+        return self
+
+    def extract_points(self):
+        """-> (points (n,3), colors (n,3)) f64 device tensors in the order unit, voxel, axis"""
+        from . import _C
+        if self.units is None:
+            raise ValueError("TSDFVolume: extract before integrate_frames")
+        U, dev = len(self.units), self.device
+        if U == 0:
+            return torch.zeros(0, 3, device=dev, dtype=torch.float64), torch.zeros(0, 3, device=dev, dtype=torch.float64)
+        ws = _workspace(_C.load().cnr_tsdf_extract_workspace_bytes(U), dev, "cnr_tsdf_extract")
+        cnt = torch.zeros(1, device=dev, dtype=torch.int64)
+        _C.call("cnr_tsdf_extract_count", self.tsdf, self.weight, self.neighbours, U, ws, cnt)
+        n = int(cnt.item())
+        points = torch.empty(n, 3, device=dev, dtype=torch.float64)
+        colors = torch.empty(n, 3, device=dev, dtype=torch.float64)
+        if n:
+            _C.call("cnr_tsdf_extract_emit", self.units, self.tsdf, self.weight, self.color, self.neighbours, U, self.voxel_length,
+                    ws, points, colors)
+        return points, colors
+
+    def extract_point_cloud(self):
+        points, colors = self.extract_points()
+        return PointCloud(points.float(), colors.float())
+
+
+def radius_neighbour_counts(points, radius):
+    """(n,3) f32 device points -> (n,) int32: per point the points with squared distance < radius^2, itself included
+    (cnr_radius_cell_keys, a sort, cnr_radius_count)"""
+    from . import _C
+    points = points.to(torch.float32).contiguous()
+    n, dev = len(points), points.device
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    if n == 0:
+        return torch.zeros(0, device=dev, dtype=torch.int32)
+    keys = torch.empty(n, device=dev, dtype=torch.int64)
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    _C.call("cnr_radius_cell_keys", points, n, float(radius), keys, err)
+    skeys, perm = torch.sort(keys, stable=True)
+    cells, per_cell = torch.unique_consecutive(skeys, return_counts=True)
+    if int(err.item()):
+        raise _C.CnrError("cnr_radius_cell_keys: a point lies more than 2^20 cells from the origin, or is not a number")
+    starts = torch.zeros(len(cells) + 1, dtype=torch.int64, device=dev)
+    starts[1:] = torch.cumsum(per_cell, 0)
+    counts = torch.zeros(n, device=dev, dtype=torch.int32)
+    _C.call("cnr_radius_count", points, n, perm.contiguous(), skeys.contiguous(), cells.contiguous(), starts, len(cells),
+            float(radius), counts)
+    return counts
+
+
+MIN_POINTS_AFTER_OUTLIER_REMOVAL = 100
+
+
+def accumulate_pointcloud_tsdf(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size=0.01, depth_scale=0.001,
+                               max_depth=6.0, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
+    """src/utils.py:212-247: the instance's depth of every frame of inst_info_list fused into a TSDF volume (voxel_size,
+    sdf_trunc = 4 voxel_size, RGB8), its surface points, voxel_down_sample(voxel_size), remove_radius_outlier(100, 0.05) -- and
+    the unfiltered cloud where fewer than 100 points survive that."""
+    dev = _cuda_device(device)
+    depths, images, poses = [], [], []
+    for entry in inst_info_list:
+        s = frame_samples[entry["frame"]]
+        if s["frame_id"] != entry["frame"]:
+            raise ValueError(f"frame {entry['frame']}: sample_dict holds frame {s['frame_id']} under that key")
+        up = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt)
+        depths.append(tsdf_depth_image(up(s["depth"], torch.float32), up(s["obj_mask"], torch.int32), inst_id, depth_scale, max_depth))
+        images.append(up(s["image"], torch.uint8))
+        poses.append(np.asarray(s["T"], np.float64))
+    if not depths:
+        raise ValueError(f"instance {inst_id}: no frames")
+    volume = TSDFVolume(voxel_size, 4 * voxel_size, device=dev, max_block_bytes=max_block_bytes)
+    volume.integrate_frames(torch.stack(depths), torch.stack(images), intrinsic_open3d, np.stack(poses))
+    cloud = volume.extract_point_cloud()
+    if len(cloud) == 0:
+        raise ValueError(f"instance {inst_id}: the TSDF volume of its {len(depths)} frames has no surface point")
+    cloud = cloud.voxel_down_sample(voxel_size)
+    kept, _ = cloud.remove_radius_outlier(nb_points=100, radius=0.05)
+    if len(kept) < MIN_POINTS_AFTER_OUTLIER_REMOVAL:
+        print("too few points left after outlier rejection")
+        return cloud
+    return kept
 
 
 def transform_pointcloud(cloud, T_rel):

@@ -884,6 +884,48 @@ int64_t cnr_clique_workspace_bytes(int N, int max_degree);
 int cnr_clique_search(const uint64_t* adj, const int* order, int N, int max_degree, int budget, void* workspace, int* clique_out,
                       int64_t* info_out, void* stream);
 
+/* ---- TSDF fusion and radius outlier counts for ScanNet registration (src/utils.py:212-247).  DESIGN.md §3.10 has the whole
+ * contract; every launch is deterministic and every fp64 product and sum is rounded on its own.
+ * A volume is a list of units of 16^3 voxels of edge `voxel`; a unit's key is (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20)
+ * of its index floor(p / (16 voxel)); 0 < trunc <= 8 voxel (else CNR_E_SHAPE: a sample's
+ * [p - trunc, p + trunc] then spans at most two units per axis).  Frames are in the loader's (W,H) layout: pixel
+ * (x, y) at x H + y.
+ * cnr_tsdf_touch: for the pixels with x % 4 == 0, y % 4 == 0 and depth > 0, in the order x major, the world point T_WC (4,4
+ * row-major f64, device) . ((x - cx) d / fx, (y - cy) d / fy, d) and the keys of the units floor((p - trunc) / UL) ..
+ * floor((p + trunc) / UL) per axis, 8 slots per sample (slot bits: x, y, z offset; -1 when unused), cnr_tsdf_touch_slots(W, H)
+ * slots in all; frames[slot] = frame.  A unit index outside [-2^20, 2^20) or not a number (or, by rounding at trunc = 8 voxel, a third unit on an axis): bit 0 of *err (device int, the
+ * caller zeroes it) is set and the sample emits nothing.
+ * cnr_tsdf_integrate: units (U,) ascending keys; unit u is updated by frames frame_idx[frame_ofs[u] .. frame_ofs[u + 1]) in that
+ * order (indices into depth (F,W,H) f32, color (F,W,H,3) u8, T_CW (F,4,4) f64: world -> camera).  Writes tsdf (U,4096), weight
+ * (U,4096), colors (U,4096,3) f32, voxel (i, j, k) of a unit at (i 16 + j) 16 + k.
+ * cnr_tsdf_extract_count / _emit: neighbours (U,3) i32 = each unit's +x, +y, +z unit or -1.  count writes count_out (1,) i64
+ * (device) and keeps per-unit offsets in workspace (>= cnr_tsdf_extract_workspace_bytes(U)); emit, with the same inputs and
+ * workspace after it on the same stream, writes count points and colours (f64) in the order unit, voxel, axis. */
+/* cnr_tsdf_depth_image: out[i] = the depth the volume sees, from n pixels of metric f32 depth: 0 unless obj_mask[i] == inst_id,
+ * u16 = uint16(trunc(double(depth) / depth_scale)) (wrapping; 0 when negative or not a number), float(u16) / 1000.0f, 0 when
+ * that exceeds max_depth (compared in fp64). */
+int cnr_tsdf_depth_image(const float* depth, const int* obj_mask, int64_t n, int inst_id, double depth_scale, double max_depth,
+                         float* out, void* stream);
+int64_t cnr_tsdf_touch_slots(int W, int H);
+int cnr_tsdf_touch(const float* depth, int W, int H, double fx, double fy, double cx, double cy, const double* T_WC, double voxel,
+                   double trunc, int frame, int64_t* keys, int* frames, int* err, void* stream);
+int cnr_tsdf_integrate(const int64_t* units, int64_t U, const int64_t* frame_ofs, const int* frame_idx, const float* depth,
+                       const uint8_t* color, const double* T_CW, int F, int W, int H, double fx, double fy, double cx, double cy,
+                       double voxel, double trunc, float* tsdf, float* weight, float* colors, void* stream);
+int64_t cnr_tsdf_extract_workspace_bytes(int64_t U);
+int cnr_tsdf_extract_count(const float* tsdf, const float* weight, const int* neighbours, int64_t U, void* workspace,
+                           int64_t* count_out, void* stream);
+int cnr_tsdf_extract_emit(const int64_t* units, const float* tsdf, const float* weight, const float* colors, const int* neighbours,
+                          int64_t U, double voxel, void* workspace, double* points, double* colors_out, void* stream);
+/* open3d's remove_radius_outlier counts.  cnr_radius_cell_keys: keys[i] = the packed cell floor(double(p) / radius) per axis
+ * (biased like a unit key), or -1 and bit 0 of *err for an index outside [-2^20, 2^20) or not a number.  The caller sorts the
+ * keys (stable) and passes the permutation, the sorted keys, the C distinct keys ascending and starts (C + 1,) i64 (cell c holds
+ * sorted positions starts[c] .. starts[c + 1]).  cnr_radius_count: counts[i] (i32) = the number of points j, i included, with
+ * (dx dx + dy dy) + dz dz < radius radius in fp64 from the f32 coordinates. */
+int cnr_radius_cell_keys(const float* points, int64_t n, double radius, int64_t* keys, int* err, void* stream);
+int cnr_radius_count(const float* points, int64_t n, const int64_t* perm, const int64_t* sorted_keys, const int64_t* cells,
+                     const int64_t* starts, int64_t C, double radius, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
