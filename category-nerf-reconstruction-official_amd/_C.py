@@ -131,6 +131,13 @@ SIGNATURES = {
     "cnr_radius_cell_keys": [_vp, _i64, _d, _vp, _vp, _vp],
     "cnr_radius_count": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _vp, _vp],
     "cnr_bg_tail": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _f, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp],
+    "cnr_hybrid_search_capacity": [],
+    "cnr_hybrid_search": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _d, _i, _vp, _vp, _vp, _vp],
+    "cnr_estimate_normals": [_vp, _i64, _vp, _vp, _i, _d, _d, _d, _vp, _vp],
+    "cnr_spfh": [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp],
+    "cnr_fpfh": [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp],
+    "cnr_feature_nn_workspace_bytes": [_i64, _i64],
+    "cnr_feature_nn": [_vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
 # first, then these fields in this order).  call_struct() wants every field by NAME: a missing, misspelt or surplus argument
@@ -194,7 +201,7 @@ _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_by
               "cnr_face_area_workspace_bytes", "cnr_clip_box_workspace_bytes", "cnr_frame_instances_workspace_bytes",
               "cnr_unproject_workspace_bytes", "cnr_points_min_workspace_bytes", "cnr_voxel_segments_workspace_bytes",
               "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes", "cnr_clique_workspace_bytes",
-              "cnr_tsdf_touch_slots", "cnr_tsdf_extract_workspace_bytes"}
+              "cnr_tsdf_touch_slots", "cnr_tsdf_extract_workspace_bytes", "cnr_feature_nn_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -127,7 +127,7 @@ def get_uncertainty_fields(inst_dict, bbox3d_dict, count_dict, pe_dict, fc_occ_m
 
 
 # ---- point clouds, alignment, sub-categorisation (src/category_registration.py:18-56, :179-324) -------------------------
-# DESIGN.md §3.9 and §3.10.  align_poses(..., solver=) takes IcpSolver (the default) or TeaserSolver.
+# DESIGN.md §3.9 and §3.10.  align_poses(..., solver=) takes IcpSolver (the default), TeaserSolver or FpfhTeaserSolver.
 def get_all_poses(inst_dict, sample_dict, intrinsic_open3d, name="replica", depth_scale=0.001, max_depth=8.0, tsdf=False):
     """:18-56.  Replica: every instance of every class gets 'pcs', its pixels of all its frames as one cloud at 1 cm.  ScanNet
     (only with tsdf=True): an instance's 'pcs' is what the loader gathered frame by frame, down-sampled to 1 cm; an instance
@@ -417,7 +417,7 @@ class TeaserSolver:
     its batch: against the ONE down-sampled first template, each start taken back by inv(S_k) -- where all B coincide, so one ICP
     runs and its result is moved by each S_k.  That equals refining S_k T against a down-sampled template k only while
     down-sampling commutes with S_k (every point alone in its voxel); on dense clouds the voxel centroids of a rotated
-    template differ, and so would that refinement, by an amount that is not measured.  Other templates are solved one by one.  last_info: per solved template group N, edges, clique_size, exact, gnc_iterations, icp_state, the
+    template differ, and so would that refinement, by an amount that is not measured.  Other templates are solved one by one.  last_info: per solved template group N, candidates (the correspondences before sub-sampling), edges, clique_size, exact, gnc_iterations, icp_state, the
     search's step counts, and graph_builds for the call."""
 
     def __init__(self, voxel_size=0.1, noise_bound=0.01, max_correspondences=10000, cbar2=1.0, gnc_factor=1.4,
@@ -440,17 +440,23 @@ class TeaserSolver:
         T[:3, :3], T[:3, 3] = R, tls_translation(a, b, R, self.noise_bound, self.cbar2)
         return T, its
 
+    def correspondences(self, source, template, device=None):
+        """stage 1, the one stage a subclass replaces -> what teaser_correspondences returns and a dict that goes into the
+        solve's info: candidates = the number of correspondences before any sub-sampling"""
+        out = teaser_correspondences(source, template, self.voxel_size, self.max_correspondences,
+                                     np.random.default_rng(self.seed), device)
+        return out + (dict(candidates=len(out[2]) * len(out[3])),)
+
     def solve_one(self, source, template, device=None):
         """one source (n,3) against one template (m,3) -> (T (4,4) after ICP, info)"""
-        A, B, src_ds, tgt_ds, _ = teaser_correspondences(source, template, self.voxel_size, self.max_correspondences,
-                                                         np.random.default_rng(self.seed), device)
+        A, B, src_ds, tgt_ds, _, stage1 = self.correspondences(source, template, device)
         adj, deg = compatibility_graph(A, B, self.noise_bound, self.cbar2)
         clique, found = max_clique(adj, deg, self.search_budget)
         T0, its = self.solve_pose(A, B, torch.from_numpy(clique).to(A.device))
         max_corr = self.noise_bound if self.icp_max_corr is None else self.icp_max_corr
         T, state = icp_device(src_ds.points_device, tgt_ds.points_device, T0[None], max_corr, self.icp_max_iteration)
         info = dict(N=len(A), edges=int(deg.sum(dtype=torch.int64)) // 2, clique_size=len(clique), exact=found["exact"],
-                    gnc_iterations=its, icp_state=state, T_before_icp=T0, clique=clique, search=found)
+                    gnc_iterations=its, icp_state=state, T_before_icp=T0, clique=clique, search=found, **stage1)
         return T[0], info
 
     def __call__(self, source, templates):
@@ -471,6 +477,96 @@ class TeaserSolver:
             out, groups = np.stack([T for T, _ in solved]), [i for _, i in solved]
         self.last_info = dict(groups[0], graph_builds=len(groups), rigid_copies=rel is not None, groups=groups)
         return torch.from_numpy(out[:, :3, :3].copy()), torch.from_numpy(out[:, :3, 3:].copy())
+
+
+# ---- TEASER's FPFH mode (spc=False; src/teaser_utils/helpers.py) -----------------------------------------------
+FEATURE_MAX_D = 64
+
+
+def compute_fpfh_feature(pcd, radius, max_nn):
+    """open3d's compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) for a utils.PointCloud with normals: ONE
+    hybrid search, cnr_spfh, cnr_fpfh -> (n,33) f64 device tensor (open3d's fpfh.data transposed)"""
+    from . import _C
+    from .utils import hybrid_search
+    if pcd.normals_device is None:
+        raise ValueError("compute_fpfh_feature: the cloud has no normals; call estimate_normals first")
+    points, n = pcd.points_device, len(pcd)
+    spfh = torch.empty(n, 33, device=points.device, dtype=torch.float64)
+    fpfh = torch.empty(n, 33, device=points.device, dtype=torch.float64)
+    if n:
+        idx, d2, count = hybrid_search(points, radius, max_nn)
+        _C.call("cnr_spfh", points, pcd.normals_device.contiguous(), n, idx, count, int(max_nn), spfh)
+        _C.call("cnr_fpfh", spfh, n, idx, d2, count, int(max_nn), fpfh)
+    return fpfh
+
+
+def feature_nn(q, p):
+    """cnr_feature_nn: q (nq,D), p (nr,D) device tensors, rounded to f32 -> (index (nq,) int32: the lowest row of p with the
+    least sequential fp32 sum of squared differences, that sum (nq,) f32)"""
+    from . import _C
+    from .utils import _workspace
+    q, p = q.to(torch.float32).contiguous(), p.to(device=q.device, dtype=torch.float32).contiguous()
+    if q.dim() != 2 or p.dim() != 2 or q.shape[1] != p.shape[1] or not 1 <= q.shape[1] <= FEATURE_MAX_D or len(p) < 1:
+        raise ValueError(f"feature_nn: q (nq,D) and p (nr,D) with 1 <= D <= {FEATURE_MAX_D} and nr >= 1")
+    index = torch.empty(len(q), device=q.device, dtype=torch.int32)
+    dist = torch.empty(len(q), device=q.device, dtype=torch.float32)
+    if len(q):
+        ws = _workspace(_C.load().cnr_feature_nn_workspace_bytes(len(q), len(p)), q.device, "cnr_feature_nn")
+        _C.call("cnr_feature_nn", q, len(q), p, len(p), int(q.shape[1]), index, dist, ws)
+    return index, dist
+
+
+def mutual_correspondences(f0, f1, mutual_filter=True):
+    """helpers.find_correspondences on device descriptors (n0,D), (n1,D): i <-> its nearest row of f1 (feature_nn on the f32-rounded
+    descriptors), kept, with mutual_filter, iff i is the nearest row of f0 to that row in turn -> (idx0, idx1) int64 device
+    tensors, idx0 ascending"""
+    if len(f0) == 0 or len(f1) == 0:
+        empty = torch.zeros(0, dtype=torch.int64, device=f0.device)
+        return empty, empty.clone()
+    nn01 = feature_nn(f0, f1)[0].to(torch.int64)
+    idx0 = torch.arange(len(f0), device=f0.device)
+    if not mutual_filter:
+        return idx0, nn01
+    nn10 = feature_nn(f1, f0)[0].to(torch.int64)
+    keep = nn10[nn01] == idx0
+    return idx0[keep], nn01[keep]
+
+
+def extract_fpfh_device(pcd, voxel_size):
+    """helpers.extract_fpfh on the device: normals at 2 voxel_size / 30, FPFH at 5 voxel_size / 100 -> (n,33) f64 device tensor"""
+    pcd.estimate_normals(radius=voxel_size * 2, max_nn=30)
+    return compute_fpfh_feature(pcd, voxel_size * 5, 100)
+
+
+class FpfhTeaserSolver(TeaserSolver):
+    """TeaserSolver with the reference's spc=False correspondences: both clouds down-sampled to voxel_size, FPFH descriptors
+    (extract_fpfh_device), mutual nearest neighbours in descriptor space -- at most min(n_s, n_t) pairs; more than
+    max_correspondences are sub-sampled as in teaser_correspondences.  noise_bound=None means voxel_size, as the reference sets
+    it in this mode.  Graph, clique, rotation, translation and ICP are TeaserSolver's.  last_info gains n_src, n_tgt and
+    correspondences ((N,2) int64: indices into the down-sampled clouds).  No correspondence at all raises a ValueError; between
+    two non-empty clouds the closest pair of descriptors is always mutual, so this only guards a search that returned nothing."""
+
+    def __init__(self, voxel_size=0.05, noise_bound=None, **kw):
+        super().__init__(voxel_size=voxel_size, noise_bound=voxel_size if noise_bound is None else noise_bound, **kw)
+
+    def correspondences(self, source, template, device=None):
+        from .utils import PointCloud
+        as_cloud = lambda c: c if isinstance(c, PointCloud) else PointCloud(np.asarray(c, np.float64), device=device)
+        src_ds, tgt_ds = as_cloud(source).voxel_down_sample(self.voxel_size), as_cloud(template).voxel_down_sample(self.voxel_size)
+        if int(self.max_correspondences) < 1 or int(self.max_correspondences) > TEASER_MAX_N:
+            raise ValueError(f"max_correspondences must lie in [1, {TEASER_MAX_N}]")
+        i0, i1 = mutual_correspondences(extract_fpfh_device(src_ds, self.voxel_size), extract_fpfh_device(tgt_ds, self.voxel_size))
+        pairs = torch.stack([i0, i1], 1).cpu().numpy().astype(np.int64)
+        candidates = len(pairs)
+        if candidates > int(self.max_correspondences):
+            pairs = pairs[np.sort(np.random.default_rng(self.seed).choice(candidates, int(self.max_correspondences), replace=False))]
+        if candidates == 0:
+            raise ValueError(f"FpfhTeaserSolver: no mutual FPFH correspondence between the {len(src_ds)} source and {len(tgt_ds)} "
+                             f"template points at voxel_size {self.voxel_size}")
+        dev = src_ds.points_device.device
+        A = src_ds.points_device[torch.from_numpy(pairs[:, 0]).to(dev)].contiguous()
+        B = tgt_ds.points_device.to(dev)[torch.from_numpy(pairs[:, 1]).to(dev)].contiguous()
+        return A, B, src_ds, tgt_ds, pairs, dict(candidates=candidates, n_src=len(src_ds), n_tgt=len(tgt_ds), correspondences=pairs)
 
 
 def _mean_nn_distance(points_from, points_to):

@@ -187,8 +187,9 @@ def voxel_down_sample_device(points, colors, voxel_size):
 
 class PointCloud:
     """The part of open3d.geometry.PointCloud that registration uses, on the device: ``points`` / ``colors`` (numpy float64
-    views of the fp32 device arrays, as np.asarray(pcd.points) gives), ``+=``, ``voxel_down_sample`` and
-    ``compute_point_cloud_distance``."""
+    views of the fp32 device arrays, as np.asarray(pcd.points) gives), ``+=``, ``voxel_down_sample``,
+    ``compute_point_cloud_distance`` and ``estimate_normals`` / ``normals`` (float64, device-backed; ``voxel_down_sample`` and
+    ``+=`` drop them).  ``remove_radius_outlier`` keeps the kept points' normals."""
 
     def __init__(self, points=None, colors=None, device=None):
         dev = points.device if torch.is_tensor(points) and points.is_cuda else _cuda_device(device)
@@ -196,6 +197,7 @@ class PointCloud:
             device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
         self.points_device = as_dev(points) if points is not None else torch.zeros(0, 3, device=dev)
         self.colors_device = as_dev(colors) if colors is not None else None
+        self.normals_device = None
         if self.colors_device is not None and len(self.colors_device) != len(self.points_device):
             raise ValueError("a colour per point")
 
@@ -210,7 +212,21 @@ class PointCloud:
     def colors(self):
         return self.colors_device.double().cpu().numpy() if self.colors_device is not None else np.zeros((0, 3))
 
+    @property
+    def normals(self):
+        return self.normals_device.cpu().numpy() if self.normals_device is not None else np.zeros((0, 3))
+
+    def has_normals(self):
+        return self.normals_device is not None
+
+    def estimate_normals(self, radius, max_nn):
+        """open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) with this package's orientation (every normal
+        points away from the cloud's centroid): fills `normals` (float64, held on the device)"""
+        self.normals_device = estimate_normals_device(self.points_device, radius, max_nn)
+        return self
+
     def __iadd__(self, other):
+        self.normals_device = None
         both = self.colors_device is not None and other.colors_device is not None and len(self) and len(other)
         if len(self) == 0:
             self.points_device, self.colors_device = other.points_device, other.colors_device
@@ -231,7 +247,9 @@ class PointCloud:
         if len(self) == 0:
             return PointCloud(self.points_device, self.colors_device), torch.zeros(0, dtype=torch.int64, device=self.points_device.device)
         kept = torch.nonzero(radius_neighbour_counts(self.points_device, radius) > int(nb_points)).reshape(-1)
-        return PointCloud(self.points_device[kept], self.colors_device[kept] if self.colors_device is not None else None), kept
+        out = PointCloud(self.points_device[kept], self.colors_device[kept] if self.colors_device is not None else None)
+        out.normals_device = self.normals_device[kept] if self.normals_device is not None else None
+        return out, kept
 
     def compute_point_cloud_distance(self, other):
         """per point of this cloud the distance to the nearest point of `other` -> (n,) f32 device tensor"""
@@ -443,6 +461,23 @@ class TSDFVolume:
         return PointCloud(points.float(), colors.float())
 
 
+def _radius_cell_tables(points, radius):
+    """The cell tables cnr_radius_count and cnr_hybrid_search take, for (n,3) f32 device points (n >= 1) and cells of edge
+    radius: cnr_radius_cell_keys, a stable sort, the distinct cells and their starts -> (perm, sorted keys, cells, starts)"""
+    from . import _C
+    n, dev = len(points), points.device
+    keys = torch.empty(n, device=dev, dtype=torch.int64)
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    _C.call("cnr_radius_cell_keys", points, n, float(radius), keys, err)
+    skeys, perm = torch.sort(keys, stable=True)
+    cells, per_cell = torch.unique_consecutive(skeys, return_counts=True)
+    if int(err.item()):
+        raise _C.CnrError("cnr_radius_cell_keys: a point lies more than 2^20 cells from the origin, or is not a number")
+    starts = torch.zeros(len(cells) + 1, dtype=torch.int64, device=dev)
+    starts[1:] = torch.cumsum(per_cell, 0)
+    return perm.contiguous(), skeys.contiguous(), cells.contiguous(), starts
+
+
 def radius_neighbour_counts(points, radius):
     """(n,3) f32 device points -> (n,) int32: per point the points with squared distance < radius^2, itself included
     (cnr_radius_cell_keys, a sort, cnr_radius_count)"""
@@ -453,19 +488,54 @@ def radius_neighbour_counts(points, radius):
         raise ValueError("radius must be positive")
     if n == 0:
         return torch.zeros(0, device=dev, dtype=torch.int32)
-    keys = torch.empty(n, device=dev, dtype=torch.int64)
-    err = torch.zeros(1, device=dev, dtype=torch.int32)
-    _C.call("cnr_radius_cell_keys", points, n, float(radius), keys, err)
-    skeys, perm = torch.sort(keys, stable=True)
-    cells, per_cell = torch.unique_consecutive(skeys, return_counts=True)
-    if int(err.item()):
-        raise _C.CnrError("cnr_radius_cell_keys: a point lies more than 2^20 cells from the origin, or is not a number")
-    starts = torch.zeros(len(cells) + 1, dtype=torch.int64, device=dev)
-    starts[1:] = torch.cumsum(per_cell, 0)
+    perm, skeys, cells, starts = _radius_cell_tables(points, radius)
     counts = torch.zeros(n, device=dev, dtype=torch.int32)
-    _C.call("cnr_radius_count", points, n, perm.contiguous(), skeys.contiguous(), cells.contiguous(), starts, len(cells),
-            float(radius), counts)
+    _C.call("cnr_radius_count", points, n, perm, skeys, cells, starts, len(cells), float(radius), counts)
     return counts
+
+
+HYBRID_MAX_NN = 128
+
+
+def hybrid_search(points, radius, max_nn):
+    """open3d's KDTreeSearchParamHybrid(radius, max_nn) for every point of (n,3) f32 device points against the cloud itself
+    (cnr_hybrid_search): the points with fp64 squared distance < radius^2, the point itself included, by (distance, index)
+    ascending, the first max_nn -> (idx (n,max_nn) int32 padded with -1, d2 (n,max_nn) f64 padded with 0, count (n,) int32)"""
+    from . import _C
+    points = points.to(torch.float32).contiguous()
+    n, dev, max_nn = len(points), points.device, int(max_nn)
+    if not radius > 0:
+        raise ValueError("radius must be positive")
+    if not 1 <= max_nn <= HYBRID_MAX_NN:
+        raise ValueError(f"max_nn must lie in [1, {HYBRID_MAX_NN}]")
+    idx = torch.empty(n, max_nn, device=dev, dtype=torch.int32)
+    d2 = torch.empty(n, max_nn, device=dev, dtype=torch.float64)
+    count = torch.empty(n, device=dev, dtype=torch.int32)
+    if n:
+        perm, skeys, cells, starts = _radius_cell_tables(points, radius)
+        _C.call("cnr_hybrid_search", points, n, perm, skeys, cells, starts, len(cells), float(radius), max_nn, idx, d2, count)
+    return idx, d2, count
+
+
+def sequential_centroid(points):
+    """the fp64 mean of (n,3) f32 device points, summed one after the other on the host (the reference point of the normals'
+    orientation: one read-back of the cloud per estimate_normals) -> (3,) float64 numpy"""
+    p = points.double().cpu().numpy()
+    return np.cumsum(p, axis=0)[-1] / float(len(p))
+
+
+def estimate_normals_device(points, radius, max_nn, centroid=None):
+    """(n,3) f32 device points -> normals (n,3) f64 device tensor: hybrid_search(radius, max_nn), cnr_estimate_normals with the
+    cloud's sequential_centroid (or `centroid`)"""
+    from . import _C
+    points = points.to(torch.float32).contiguous()
+    n = len(points)
+    normals = torch.empty(n, 3, device=points.device, dtype=torch.float64)
+    if n:
+        idx, _, count = hybrid_search(points, radius, max_nn)
+        c = sequential_centroid(points) if centroid is None else np.asarray(centroid, np.float64).reshape(3)
+        _C.call("cnr_estimate_normals", points, n, idx, count, int(max_nn), float(c[0]), float(c[1]), float(c[2]), normals)
+    return normals
 
 
 MIN_POINTS_AFTER_OUTLIER_REMOVAL = 100

@@ -926,6 +926,58 @@ int cnr_radius_cell_keys(const float* points, int64_t n, double radius, int64_t*
 int cnr_radius_count(const float* points, int64_t n, const int64_t* perm, const int64_t* sorted_keys, const int64_t* cells,
                      const int64_t* starts, int64_t C, double radius, int* counts, void* stream);
 
+/* ---- TEASER's FPFH mode (src/teaser_utils/helpers.py: extract_fpfh, find_correspondences).  The contracts
+ * above hold: caller-allocated outputs, an explicit stream, argument errors as return codes before the device is touched, no
+ * float atomics, every loop bounded, results bit-identical run to run.  Every fp64 product, sum and quotient is rounded on its
+ * own (no fused multiply-add), so a numpy restatement repeats it.  Equality with open3d is unverified.
+ * cnr_hybrid_search: open3d's KDTreeSearchParamHybrid(radius, max_nn) for every point of the cloud against the cloud itself.
+ * points (n,3) f32; perm, sorted_keys, cells, starts, C: the cell tables of cnr_radius_cell_keys at edge `radius`, built by the
+ * caller as for cnr_radius_count.  The candidates of point i are the points j of the 27 cells around it, i included, with d2 =
+ * (dx dx + dy dy) + dz dz < radius radius in fp64 from the f32 coordinates; ordered by (d2, j) ascending, the first max_nn are
+ * kept: idx (n, max_nn) i32 padded with -1, d2 (n, max_nn) f64 padded with 0, count (n,) i32.  1 <= max_nn <= 128, n < 2^31
+ * (else CNR_E_SHAPE).  A point whose key is -1 (not a number, or outside the cell range) gets count 0 and is nobody's
+ * neighbour.  One wave per point; the candidates pass through a buffer of cnr_hybrid_search_capacity() entries per wave that is
+ * cut back to the best max_nn whenever it fills: a neighbourhood with more candidates than that is still exact. */
+int cnr_hybrid_search_capacity(void);
+int cnr_hybrid_search(const float* points, int64_t n, const int64_t* perm, const int64_t* sorted_keys, const int64_t* cells,
+                      const int64_t* starts, int64_t C, double radius, int max_nn, int* idx, double* d2, int* count,
+                      void* stream);
+/* normals (n,3) f64 from the lists idx (n, max_nn), count (n,) of a hybrid search.  Fewer than 3 neighbours (or an entry
+ * outside [0, n)): (0, 0, 1).  Otherwise, with k = count[i] and the listed points in list order: mean = (sequential sum) / k;
+ * covariance entries = (sequential sum of (p - mean)_a (p - mean)_b) / k; cyclic Jacobi on the pairs (0,1), (0,2), (1,2), 8
+ * sweeps, per pair with a_pq != 0: theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta theta + 1))
+ * (sign(0) = 1), c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, (a_rp, a_rq) <- (c a_rp - s a_rq,
+ * s a_rp + c a_rq), the same for every row of V.  The normal is the column of V of the smallest diagonal entry (the first of
+ * equals), divided by its length sqrt((x x + y y) + z z), negated when d = (n_x (p_x - c_x) + n_y (p_y - c_y)) + n_z (p_z -
+ * c_z) < 0 with p = point i and c = (cx, cy, cz), the centroid of the whole cloud, which the caller computes once; when d == 0,
+ * negated when its component of largest magnitude (the first of equals) is negative.  open3d keeps the eigen-solver's sign:
+ * this orientation is a deliberate difference (it moves with the cloud under a rigid motion; the descriptors need that). */
+int cnr_estimate_normals(const float* points, int64_t n, const int* idx, const int* count, int max_nn, double cx, double cy,
+                         double cz, double* normals, void* stream);
+/* spfh (n,33) f64 from points, normals (n,3) f64 and the lists of one hybrid search.  Row i with k = count[i] <= 1 is zero.
+ * Otherwise every listed neighbour after the first (the first is i itself) adds 1 to three integer histograms of 11 bins at
+ * offsets 0, 11, 22: the bins min(max(floor(x), 0), 10) of x = (11 (f0 + pi)) / (2 pi), (11 (f1 + 1)) 0.5, (11 (f2 + 1)) 0.5
+ * of the pair feature of (p1, n1) = point i and (p2, n2) = the neighbour: dp = p2 - p1, d = sqrt((dp_x dp_x + dp_y dp_y) +
+ * dp_z dp_z); d == 0: f = 0.  a1 = n1.dp / d, a2 = n2.dp / d (dots as (x x + y y) + z z); if fabs(a1) < fabs(a2) the normals
+ * swap, dp = -dp and f2 = -a2, else f2 = a1.  v = dp x n1, |v| == 0: f = 0 (f2 too); v = v / |v| per component, w = n1 x v,
+ * f1 = v.n2, f0 = atan2(w.n2, n1.n2).  The row is (double)count (100.0 / (k - 1)).
+ * cnr_fpfh: fpfh (n,33) f64 from spfh and the lists with their d2.  Row i with k <= 1 is zero.  Otherwise over the listed
+ * neighbours after the first with d2 != 0, in list order, and j = 0..32 in order: val = spfh[nbr][j] / d2, out[j] += val,
+ * sum[j / 11] += val; then out[j] = out[j] (100.0 / sum[j / 11]) where that sum is not 0; then out[j] += spfh[i][j]. */
+int cnr_spfh(const float* points, const double* normals, int64_t n, const int* idx, const int* count, int max_nn, double* spfh,
+             void* stream);
+int cnr_fpfh(const double* spfh, int64_t n, const int* idx, const double* d2, const int* count, int max_nn, double* fpfh,
+             void* stream);
+/* The exact nearest neighbour in descriptor space: q (nq,D), p (nr,D) f32, 1 <= D <= 64, nr < 2^31 (else CNR_E_SHAPE).
+ * dist2(i, r) = the sequential fp32 sum over j = 0..D-1 of (q_ij - p_rj)^2 from 0, one rounded subtraction, one rounded product
+ * and one rounded sum each (no expanded square, no matrix instruction); index_out[i] (i32) = the lowest r that attains the
+ * minimum (row 0 when nothing compares below it), dist_out[i] (f32) = that minimum.  p is tiled through LDS, in chunks of rows
+ * spread over the grid so that few queries still fill the device; the chunks' minima pass through workspace (>=
+ * cnr_feature_nn_workspace_bytes(nq, nr); nq < 2^31) and are merged in chunk order, so the result is the same for any split. */
+int64_t cnr_feature_nn_workspace_bytes(int64_t nq, int64_t nr);
+int cnr_feature_nn(const float* q, int64_t nq, const float* p, int64_t nr, int D, int* index_out, float* dist_out, void* workspace,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
