@@ -8,10 +8,11 @@
 //     element); the trunk entries the latent path adds to are finished by the AdamW blocks themselves
 //     (latent_trunk_term: n_obj multiply-adds from dbiasrows and zl);
 //   * the epilogue blocks only read the render-loss partials, the depth pool and the CURRENT state.
-//   * (records != NULL) the fixed-order reduction of the field backward's records moves in as well: a block sums 64
-//     record entries over all workgroups and applies AdamW to them at once; the latent path takes its input, the
-//     per-object bias-row sums, from a fixed-point table the field backward filled with integer atomics (order-free,
-//     hence still bitwise reproducible) instead of waiting for that reduction.
+//   * (records != NULL) the fixed-order reduction of the field backward's records moves in as well: a block sums
+//     TAIL_EPB record entries over all workgroups from 16-byte loads -- every load of the block, records included, in ONE
+//     round trip (reduce_block) -- and applies AdamW to them at once; the latent path takes its input, the per-object
+//     bias-row sums, from a fixed-point table the field backward filled with integer atomics (order-free, hence still
+//     bitwise reproducible) instead of waiting for that reduction.
 // grid: [ do_latent ? NL latent blocks per class : 0 ] [ NA AdamW blocks over the flat (C, P) buffer, or with records
 //        NR = REC_ENTRIES / TAIL_EPB reduce-and-update blocks per class ] [ C epilogue ].
 // With do_latent = 0 (the gradient was completed by cnr_latent_bwd, e.g. before a multi-GPU all-reduce) the AdamW
@@ -129,6 +130,148 @@ __device__ __forceinline__ void publish_rows_fix(const TailArgs& a, int c) {
   }
 }
 
+// ---- A reducing block: TAIL_EPB = 64 record entries of class c summed over all nwg records, the latent path's share added, AdamW.
+// The sums are record_range_sum's, bit for bit (records_common.h), over the four quarters of the record range, combined
+// t0 += t2, t1 += t3, t0 += t1 -- from 16-byte loads, one tile of 64 entries (record_tile_*).  Nothing a block loads has an
+// address that depends on a loaded value, so EVERYTHING goes out in one round in front of one scheduling barrier: the table
+// entries and z of the latent-path term, theta / m / v of the entries the block finishes, and every record load (at
+// nwg <= 256; more records, or more than two objects per chain of the latent-path term, loop behind that round).
+// (Blocks of 128 entries -- half the blocks, twice the loads in flight per thread -- measured no faster than two-byte loads:
+// CHANGELOG.md, profiles/tail_wide_reduce.txt.)
+static_assert(cnr_rec::TAIL_EPB == cnr_rec::TILE, "a reducing block owns one tile");
+// blocks with dB entries (record entries [TRUNK, TRUNK + 63); their second addends are the entries 63 further on, which a
+// 16-byte load cannot reach from the first addend's lane: these blocks sum the tile behind their own as well and pick
+// entry + 63 out of LDS)
+constexpr int DB_BLK0 = TRUNK / cnr_rec::TAIL_EPB, DB_BLK1 = (TRUNK + 62) / cnr_rec::TAIL_EPB;
+static_assert((DB_BLK1 + 2) * cnr_rec::TILE <= cnr_rec::REC_ENTRIES, "the extra tile lies inside the record");
+static_assert(OFF_T1_B + 32 <= DB_BLK0 * cnr_rec::TAIL_EPB, "no latent-conditioned entry in a dB block");
+// LDS floats of a reducing block: transposition buffer, quarter sums of two tiles, the latent-path term's four chains
+constexpr int TAIL_REDUCE_LDS = cnr_rec::TILE_LDS_FLOATS + 2 * 4 * cnr_rec::TILE + 4 * cnr_rec::TILE;
+constexpr int LAT_B = 2;   // objects per chain of the latent-path term in flight at a time
+
+// the record sums of NT tiles from entry i0 on, as acc[tile][quarter][entry of the thread's group] per accumulator slot of the
+// thread.  K = 1: a quarter has at most 32 records (nwg <= 128), one load per quarter and tile; K = 2: two, and a loop
+// beyond 256 records.  The first round's loads end in front of the scheduling barrier that the caller's loads share.
+template <int NT, int K>
+__device__ __forceinline__ void reduce_tiles(float (&acc)[NT][4][8], const cnr_rec::rec_t* rc, int i0, int nwg) {
+  using namespace cnr_rec;
+  const int nk = ((nwg + 3) / 4 + 31) / 32;      // values of k in a quarter
+  rec8_t v[NT][4][K];
+  record_tile_issue<NT, K>(v, rc, i0, nwg, 0);
+  __builtin_amdgcn_sched_barrier(0);             // ---- everything above is in flight together
+  record_tile_accumulate<NT, K>(acc, v, nwg, 0);
+  for (int k0 = K; k0 < nk; k0 += K) {           // (more than 256 records)
+    record_tile_issue<NT, K>(v, rc, i0, nwg, k0);
+    __builtin_amdgcn_sched_barrier(0);
+    record_tile_accumulate<NT, K>(acc, v, nwg, k0);
+  }
+}
+
+template <int NT, bool LAT>
+__device__ __forceinline__ void reduce_block(const TailArgs& a, int c, int blk, float* sm, float step_size, float inv_bc2_sqrt) {
+  using namespace cnr_rec;
+  float* tr = sm;                                // [4 * 64][32] swizzled
+  float* qs = sm + TILE_LDS_FLOATS;              // [NT * 64][4]: quarter sums of the block's entries (and the tile behind them)
+  float* lat = qs + 2 * 4 * TILE;                // [64][4]: the latent-path term's chains
+  const int P = (int)a.lay.stride;
+  const int le = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int i = blk * TILE + le;
+  // The latent path's share of a latent-conditioned layer's weight / bias gradient, sum over objects of d biasrow[ob][k][o] *
+  // (z[ob][k][j] | 1), in four chains per entry: thread (le, q) runs chain q (objects q, q + 4, ..) and reads its table entries
+  // straight into registers, LAT_B objects at a time.  Every load is unconditional -- from object 0 where the chain has no
+  // such object, dropped afterwards: loads under a condition become branches with waits inside.
+  int lk = 0, lo_ = 0, lj = 0;
+  bool has_lat = false;
+  if constexpr (LAT) has_lat = i < TRUNK && latent_trunk_index(i, lk, lo_, lj);
+  const int n_obj = a.lay.n_obj, n = n_obj * 128;
+  const long long* tabc = a.rows_fix + (size_t)c * n;
+  const float* zc = a.zl + (int64_t)c * n;
+  long long f[LAT_B][ROWS_FIX_COPIES];
+  float zz[LAT_B];
+  float lat_part = 0.0f;
+  if constexpr (LAT) {
+#pragma unroll
+    for (int u = 0; u < LAT_B; ++u) {
+      const int ob = q + 4 * u, ix = ((ob < n_obj ? ob : 0) * 4 + lk) * 32;
+#pragma unroll
+      for (int k = 0; k < ROWS_FIX_COPIES; ++k) f[u][k] = tabc[(size_t)k * a.C * n + ix + lo_];
+      zz[u] = zc[ix + (lj & 31)];
+    }
+  }
+  // trunk entries and the first dB half own an output; the second dB half is the other addend of the first.  Thread le of the
+  // block finishes entry le.
+  const bool owner = q == 0 && i < TRUNK + 63;
+  const int64_t idx = (int64_t)c * P + (i < TRUNK ? i : a.off_B + (i - TRUNK));
+  float p0 = 0.f, m0 = 0.f, v0 = 0.f;
+  if (!a.grad_only) {                            // (uniform; a thread that owns nothing loads the class's first element)
+    const int64_t ic = owner ? idx : (int64_t)c * P;
+    p0 = a.theta_in[ic]; m0 = a.m[ic]; v0 = a.v[ic];
+  }
+  const rec_t* rc = a.records + (size_t)c * a.nwg * REC_ENTRIES;
+  float acc[NT][4][8];
+#pragma unroll
+  for (int p = 0; p < NT; ++p) {
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[p][qq][j] = 0.0f;
+    }
+  }
+  if (a.nwg <= 4 * 32) reduce_tiles<NT, 1>(acc, rc, blk * TILE, a.nwg);   // (uniform)
+  else reduce_tiles<NT, 2>(acc, rc, blk * TILE, a.nwg);
+  if constexpr (LAT) {
+    for (int b0 = 0;;) {
+#pragma unroll
+      for (int u = 0; u < LAT_B; ++u) {
+        const bool on = has_lat && q + 4 * (b0 + u) < n_obj;
+        long long t = 0;
+#pragma unroll
+        for (int k = 0; k < ROWS_FIX_COPIES; ++k) t += f[u][k];
+        const float z = on ? (lj < 32 ? zz[u] : 1.0f) : 0.0f;
+        lat_part = fmaf((float)((double)(on ? t : 0) * (1.0 / ROWS_FIX_SCALE)), z, lat_part);
+      }
+      b0 += LAT_B;
+      if (4 * b0 >= n_obj) break;                // (more than 4 LAT_B objects: further rounds)
+#pragma unroll
+      for (int u = 0; u < LAT_B; ++u) {
+        const int ob = q + 4 * (b0 + u), ix = ((ob < n_obj ? ob : 0) * 4 + lk) * 32;
+#pragma unroll
+        for (int k = 0; k < ROWS_FIX_COPIES; ++k) f[u][k] = tabc[(size_t)k * a.C * n + ix + lo_];
+        zz[u] = zc[ix + (lj & 31)];
+      }
+    }
+    lat[le * 4 + q] = lat_part;
+  }
+#pragma unroll
+  for (int p = 0; p < NT; ++p) {
+    float t = record_tile_finish(acc[p], tr);    // thread (le, q): quarter q of entry blk * 64 + 64 p + le
+    // entries no launch writes sit in uncleared workspace: their sums are dropped here, per entry
+    if (!rec_entry_written(blk * TILE + p * TILE + le, n_obj)) t = 0.0f;
+    qs[(p * TILE + le) * 4 + q] = t;
+  }
+  __syncthreads();
+  if (owner) {
+    auto quarters = [](const float* pp) {        // fixed-order pairwise sum of an entry's four partials
+      float t0 = pp[0], t1 = pp[1];
+      const float t2 = pp[2], t3 = pp[3];
+      t0 += t2; t1 += t3; t0 += t1;
+      return t0;
+    };
+    float g = quarters(qs + le * 4);
+    if (i >= TRUNK) g += quarters(qs + (le + 63) * 4);
+    if constexpr (LAT) { if (i < TRUNK) g += quarters(lat + le * 4); }   // (+0 for an entry the latent path does not reach)
+    a.grad[idx] = g;
+    if (!a.grad_only) {
+      float pi = p0 * (1.0f - a.lr * a.wd);
+      const float mi = m0 + (g - m0) * (1.0f - a.b1);
+      const float vi = v0 * a.b2 + (1.0f - a.b2) * g * g;
+      const float denom = sqrtf(vi) * inv_bc2_sqrt + a.eps;
+      pi -= step_size * (mi / denom);
+      a.theta_out[idx] = pi; a.m[idx] = mi; a.v[idx] = vi;
+    }
+  }
+}
+
 #ifdef CNR_TAIL_STAMPS  // tools/exp only
 __device__ unsigned long long g_tail_t[8];  // [type 0..2][min start, max end], [6] = min start over all
 #define TAIL_T0() const unsigned long long tt0 = __builtin_amdgcn_s_memrealtime(); \
@@ -200,86 +343,13 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
     return;
   }
   b -= nlat;
-  if (a.records) {  // ---- reduce 64 record entries of class c over all workgroups, finish the gradient, AdamW
+  if (a.records) {  // ---- reduce TAIL_EPB record entries of class c over all workgroups, finish the gradient, AdamW
     if (b < a.NR * C) {
       const int c = b / a.NR, blk = b % a.NR;
-      // EPB record entries per block, NQ = 256 / EPB sub-ranges of the workgroup range per entry: every thread sums
-      // nwg / NQ records.  Measured at configs[1] (256 records): EPB = 64 (two rounds of 32 loads per thread, 256-byte
-      // segments per wave load) 30.75 M rays/s; EPB = 32 29.9 M; EPB = 16 (one round, 64-byte segments, 4 x the blocks) 24.2 M
-      constexpr int EPB = cnr_rec::TAIL_EPB, NQ = 256 / EPB;
-      float* part = sm;                      // [NQ][EPB] (+ [NQ][EPB] for the second dB addend, + [NQ][EPB] for the latent-path term)
-      const int e = threadIdx.x % EPB, q = threadIdx.x / EPB;
-      const int i = blk * EPB + e;
-      // The latent path's share of a latent-conditioned layer's weight / bias gradient, sum over objects of d biasrow[ob][k][o] *
-      // (z[ob][k][j] | 1): the NQ threads of an entry split the objects (ob = q, q + NQ, ..) and read their table entries straight
-      // into registers -- no walk over the whole table, no barrier, nothing that grows with the object count beyond n_obj / NQ
-      // entries per thread; the loads go out together with the record loads below.
-      float lat_part = 0.0f;
-      {
-        int lk, lo_, lj;
-        if (i < TRUNK && latent_trunk_index(i, lk, lo_, lj)) {
-          const int n_obj = a.lay.n_obj, n = n_obj * 128;
-          const long long* tabc = a.rows_fix + (size_t)c * n;
-          const float* zc = a.zl + (int64_t)c * n;
-          for (int ob0 = q; ob0 < n_obj; ob0 += 4 * NQ) {       // four objects (32 table loads) in flight at a time
-            long long f[4][cnr_rec::ROWS_FIX_COPIES];
-            float zz[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int ob = ob0 + u * NQ, on = ob < n_obj, idx = ((on ? ob : 0) * 4 + lk) * 32;
-#pragma unroll
-              for (int k = 0; k < cnr_rec::ROWS_FIX_COPIES; ++k) f[u][k] = on ? tabc[(size_t)k * a.C * n + idx + lo_] : 0;
-              zz[u] = on ? (lj < 32 ? zc[idx + lj] : 1.0f) : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              long long t = 0;
-#pragma unroll
-              for (int k = 0; k < cnr_rec::ROWS_FIX_COPIES; ++k) t += f[u][k];
-              lat_part = fmaf((float)((double)t * (1.0 / cnr_rec::ROWS_FIX_SCALE)), zz[u], lat_part);
-            }
-          }
-        }
-      }
-      // trunk entries and the first dB half own an output; the second dB half is the other addend of the first
-      const bool owner = i < TRUNK + 63;
-      float s0 = 0.0f, s1 = 0.0f;
-      const int64_t idx = (int64_t)c * P + (i < TRUNK ? i : a.off_B + (i - TRUNK));
-      float p0 = 0.f, m0 = 0.f, v0 = 0.f;
-      if (q == 0 && owner && !a.grad_only) { p0 = a.theta_in[idx]; m0 = a.m[idx]; v0 = a.v[idx]; }   // in flight under the record sum
-      if (owner) {
-        const int per = (a.nwg + NQ - 1) / NQ, w0 = q * per, w1 = min(a.nwg, w0 + per);
-        const cnr_rec::rec_t* r = a.records + (size_t)c * a.nwg * cnr_rec::REC_ENTRIES + i;
-        if (cnr_rec::rec_entry_written(i, a.lay.n_obj)) s0 = cnr_rec::record_range_sum(r, w0, w1);
-        if (i >= TRUNK) s1 = cnr_rec::record_range_sum(r + 63, w0, w1);
-      }
-      part[q * EPB + e] = s0; part[256 + q * EPB + e] = s1; part[512 + q * EPB + e] = lat_part;
-      __syncthreads();
-      if (q == 0 && owner) {
-        auto tree = [&](const float* pp) {       // fixed-order pairwise sum of the NQ partials of entry e
-          float t[NQ];
-#pragma unroll
-          for (int k = 0; k < NQ; ++k) t[k] = pp[k * EPB + e];
-#pragma unroll
-          for (int st = NQ / 2; st >= 1; st >>= 1) {
-#pragma unroll
-            for (int k = 0; k < st; ++k) t[k] += t[k + st];
-          }
-          return t[0];
-        };
-        float g = tree(part);
-        if (i >= TRUNK) g += tree(part + 256);
-        if (i < TRUNK) g += tree(part + 512);
-        a.grad[idx] = g;
-        if (!a.grad_only) {
-          float pi = p0 * (1.0f - a.lr * a.wd);
-          const float mi = m0 + (g - m0) * (1.0f - a.b1);
-          const float vi = v0 * a.b2 + (1.0f - a.b2) * g * g;
-          const float denom = sqrtf(vi) * inv_bc2_sqrt + a.eps;
-          pi -= step_size * (mi / denom);
-          a.theta_out[idx] = pi; a.m[idx] = mi; a.v[idx] = vi;
-        }
-      }
+      // (block-uniform) the blocks that own dB entries also sum the tile behind their own: the second addends sit 63 entries on
+      if (blk > DB_BLK1) return;                 // second dB halves and row sums only: no output of its own
+      if (blk >= DB_BLK0) reduce_block<2, false>(a, c, blk, sm, step_size, inv_bc2_sqrt);
+      else reduce_block<1, true>(a, c, blk, sm, step_size, inv_bc2_sqrt);
       TAIL_T1(1);
       return;
     }
@@ -345,13 +415,15 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 }  // namespace
 
 constexpr int LOCAL_MIN_OBJ = 5;   // classes of up to four objects take the one-trip latent blocks (latent_bwd_block_1trip)
-// dynamic LDS of a tail block: the reducing blocks' three partial arrays (768 floats), the general latent blocks' two whole
+// dynamic LDS of a tail block: the reducing blocks' transposition buffer and partial sums (TAIL_REDUCE_LDS floats, 35 KB: two
+// blocks per CU as before), the epilogue's 8 floats, the general latent blocks' two whole
 // (n_obj, 4, 32) tables + norms, or the per-block form's own rows (latent_local_lds_floats) -- which is what lets a class hold up to
 // ROWS_TILE_MAX objects: 100 objects need 29 KB there, where the whole tables would need 103 KB and one block per CU
-static size_t tail_lds_bytes(int do_latent, int local_latent, int L, int n_obj) {
+static size_t tail_lds_bytes(int do_latent, int local_latent, int L, int n_obj, bool reducing) {
   const int general = 2 * n_obj * 128 + 2 * n_obj + 520;
   const int local = latent_local_lds_floats(L, n_obj) + 8;
-  const int need = !do_latent ? 776 : local_latent ? (local > 776 ? local : 776) : general;
+  int need = !do_latent ? 776 : local_latent ? (local > 776 ? local : 776) : general;
+  if (reducing && need < TAIL_REDUCE_LDS) need = TAIL_REDUCE_LDS;
   return (size_t)need * sizeof(float);
 }
 
@@ -379,6 +451,7 @@ extern "C" int cnr_step_tail(const cnr_step_tail_args* args, void* stream) {
   // (more than ROWS_MAX object rows: the records carry no row sums, the fixed-point table has them all -- cnr_field_train's
   //  one-object-per-tile form)
   if (records && (!do_latent || !rows_fix || nwg <= 0 || n_obj > cnr_rec::ROWS_TILE_MAX)) return CNR_E_ARG;
+  if (records && ((uintptr_t)records & 15)) return CNR_E_ARG;   // the reduction loads 16 bytes at a time
   if (rows_fix && !do_latent) return CNR_E_ARG;
   if (n_obj > cnr_rec::ROWS_TILE_MAX) return CNR_E_SHAPE;
   if (n_obj > 32 && do_latent && !(rows_fix && latent_local_ok(L, n_obj))) return CNR_E_SHAPE;   // the general latent blocks keep whole tables in LDS
@@ -408,7 +481,7 @@ extern "C" int cnr_step_tail(const cnr_step_tail_args* args, void* stream) {
   a.records = (const cnr_rec::rec_t*)records; a.nwg = nwg; a.rows_fix = rows_fix; a.NR = cnr_rec::REC_ENTRIES / cnr_rec::TAIL_EPB;
   a.clamp_flags = clamp_flags;
   const unsigned grid = (unsigned)((a.do_latent ? a.NL * C : 0) + (records ? a.NR * C : a.NA) + C);
-  const size_t lds = tail_lds_bytes(a.do_latent, a.local_latent, L, n_obj);
+  const size_t lds = tail_lds_bytes(a.do_latent, a.local_latent, L, n_obj, records != nullptr);
   hipLaunchKernelGGL(tail_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -425,6 +498,7 @@ extern "C" int cnr_step_grad(const float* theta, float* grad, int64_t class_stri
   if (!theta || !grad || class_stride <= 0 || L <= 0 || n_obj <= 0 || C <= 0 || !zl || !dbiasrows || !records ||
       nwg <= 0 || !rows_fix)
     return CNR_E_ARG;
+  if ((uintptr_t)records & 15) return CNR_E_ARG;   // the reduction loads 16 bytes at a time
   if (n_obj > cnr_rec::ROWS_TILE_MAX) return CNR_E_SHAPE;
   TailArgs a{};
   a.theta_in = theta; a.grad = grad;
@@ -439,7 +513,7 @@ extern "C" int cnr_step_grad(const float* theta, float* grad, int64_t class_stri
   a.records = (const cnr_rec::rec_t*)records; a.nwg = nwg; a.rows_fix = rows_fix; a.NR = cnr_rec::REC_ENTRIES / cnr_rec::TAIL_EPB;
   const unsigned grid = (unsigned)(a.NL * C + a.NR * C);
   if (n_obj > 32 && !a.local_latent) return CNR_E_SHAPE;
-  const size_t lds = tail_lds_bytes(1, a.local_latent, L, n_obj);
+  const size_t lds = tail_lds_bytes(1, a.local_latent, L, n_obj, true);
   hipLaunchKernelGGL(tail_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
   CNR_LAUNCH_CHECK();
   return CNR_OK;

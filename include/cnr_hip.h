@@ -407,7 +407,8 @@ int cnr_adamw_epilogue(float* param, const float* grad, float* exp_avg, float* e
  * cnr_field_bwd_pipe(..., skip_reduce = 1): `records` is that call's workspace, nwg =
  * cnr_field_bwd_pipe_blocks(...), and rows_fix the (8, C, n_obj, 4, 32) int64 table that call accumulated (2^-40 fixed
  * point, integer atomics: any order, same sum) -- zero it before every field backward.  dbiasrows then receives the
- * float form of that table.
+ * float form of that table.  `records` must be 16-byte aligned (the reduction loads 16 bytes at a time; a record is
+ * 32 256 bytes, so every record then is): CNR_E_ARG otherwise.
  * rl_blocks: loss partials per class in rl_workspace; 0 = cnr_render_loss's own block count.
  * code_lr > 0: the shape / texture code tables are an AdamW group of their own (code_lr, code_weight_decay: train.py:40,
  * 54-64, configs' code_lr / code_weight_decay); 0 = they share lr / weight_decay. */
@@ -464,7 +465,7 @@ int cnr_step_tail(const cnr_step_tail_args* args, void* stream);
 
 /* The gradient half of cnr_step_tail on its own (records reduction + latent backward + code regulariser in one launch,
  * no optimiser, no epilogue): for hosts that need the finished gradient first, e.g. to all-reduce it across GPUs.
- * Same arguments as the corresponding ones of cnr_step_tail; follow it (after the collective) with
+ * Same arguments as the corresponding ones of cnr_step_tail (`records` 16-byte aligned, CNR_E_ARG otherwise); follow it (after the collective) with
  * cnr_step_tail(..., do_latent = 0, ..., records = NULL, nwg = 0, rows_fix = NULL, ...). */
 int cnr_step_grad(const float* theta, float* grad, int64_t class_stride, int64_t off_B, int64_t off_latW,
                   int64_t off_latb, int64_t off_shape, int64_t off_tex, int L, int n_obj, int C, const float* zl,
