@@ -9,6 +9,10 @@
 // backward, with g_i = dD z_i + dC.c_i + dO (+ d_term_i) and Suf_i = sum_{k>i} term_k g_k:
 //   d occ_i = T_i g_i - Suf_i / f_i          (same division ATen's cumprod backward performs)
 //   d alpha_i = d occ_i occ_i (1 - occ_i) ; d c_i = term_i dC
+// T and term are fp32 as in the forward; g, the suffix sum and d occ are formed in double and rounded once.  T_i g_i and
+// Suf_i / f_i nearly cancel wherever g varies slowly along the ray, which leaves the fp32 roundings of g_i and of the
+// suffix sum standing at up to 17 ulp of the result; ATen's CPU cumsum / cumprod, which the reference's backward runs
+// through, accumulate float32 in double as well.
 #include "cnr_common.h"
 
 // no fused multiply-add contraction in this file: composite.hip and render_loss.hip evaluate the same expressions and
@@ -28,13 +32,20 @@ __device__ __forceinline__ float wave_incl_prod(float v, int lane) {
   return v;
 }
 // inclusive suffix sum across the wave
-__device__ __forceinline__ float wave_incl_suffix_sum(float v, int lane) {
+__device__ __forceinline__ double wave_incl_suffix_sum(double v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const float p = __shfl_down(v, o, 64);
+    const double p = __shfl_down(v, o, 64);
     if (lane + o < 64) v += p;
   }
   return v;
+}
+
+// exclusive suffix sum (k > i) from the inclusive one: the next lane's value.  Not (incl - v): that difference carries the
+// rounding of v = term_i g_i, which the backward divides by f_i, and f_i is 1e-10 where occ_i = 1.
+__device__ __forceinline__ double wave_excl_suffix(double incl, int lane) {
+  const double nxt = __shfl_down(incl, 1, 64);
+  return lane == 63 ? 0.0 : nxt;
 }
 
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -124,7 +135,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     carry *= __shfl(incl, 63, 64);
   }
   // pass 2 (back to front) with the suffix sum carried across chunks
-  float suf_carry = 0.0f;  // sum_{k in later chunks} term_k g_k
+  double suf_carry = 0.0;  // sum_{k in later chunks} term_k g_k
   for (int ch = nchunk - 1; ch >= 0; --ch) {
     const int s = ch * 64 + lane;
     const bool live = s < S;
@@ -135,18 +146,20 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     if (lane == 0) excl = 1.0f;
     const float T = carry_in[ch] * excl;
     const float term = occ * T;
-    float g = 0.0f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    double g = 0.0;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     if (live) {
       if (color) { const float* cp = color + (base + s) * 3; c0 = cp[0]; c1 = cp[1]; c2 = cp[2]; }
-      g = dD * (z ? z[base + s] : 0.0f) + dR * c0 + dG * c1 + dBl * c2 + dO;
-      if (d_term) g += d_term[base + s];
+      g = (double)dD * (double)(z ? z[base + s] : 0.0f) + (double)dR * (double)c0 + (double)dG * (double)c1 +
+          (double)dBl * (double)c2 + (double)dO;
+      if (d_term) g += (double)d_term[base + s];
     }
-    const float tg = term * g;
-    const float incl_suf = wave_incl_suffix_sum(tg, lane);
-    const float suf = (incl_suf - tg) + suf_carry;  // exclusive: k > i
+    const double tg = (double)term * g;
+    const double incl_suf = wave_incl_suffix_sum(tg, lane);
+    const double suf = wave_excl_suffix(incl_suf, lane) + suf_carry;  // exclusive: k > i
     if (live) {
-      const float docc = T * g - suf / f;
-      d_alpha[base + s] = in_is_occ ? docc : docc * occ * (1.0f - occ);
+      const double docc = (double)T * g - suf / (double)f;
+      d_alpha[base + s] = (float)(in_is_occ ? docc : docc * (double)occ * (1.0 - (double)occ));
       if (d_color) { float* dc = d_color + (base + s) * 3; dc[0] = term * dR; dc[1] = term * dG; dc[2] = term * dBl; }
     }
     suf_carry += __shfl(incl_suf, 0, 64);

@@ -338,9 +338,12 @@ __global__ __launch_bounds__(256) void mask_counts_kernel(const uint8_t* __restr
 // loss gradient w.r.t. the ray's renders and the composite backward, with the per-sample sigma / colour never leaving
 // registers (cnr_field_fwd + cnr_render_loss write and re-read 16 B per sample between two launches).  A wave owns
 // whole rays: K = S / 32 consecutive tiles, lane (half 0) = sample; the exclusive-cumprod runs as a 32-lane scan per
-// tile with the transmittance carried from tile to tile, the backward's suffix sums the other way.  Same expressions as
-// render_loss.hip; sums over lanes run over 32-lane tiles instead of 64-lane chunks, so the results agree to summation
-// order, not bitwise.  grid (blocks, C); block b of class c writes loss partial (c, b) -- nb = gridDim.x for
+// tile with the transmittance carried from tile to tile, the backward's suffix sums the other way.  The forward, the
+// losses and their gradients are render_loss.hip's expressions; sums over lanes run over 32-lane tiles instead of 64-lane
+// chunks, so those agree to summation order, not bitwise.  The composite BACKWARD is fp32 throughout here, with the
+// exclusive suffix sum as (inclusive - own term): render_loss.hip and composite.hip take it from the next lane and form
+// g, the sum and d occ in double.  With alpha as input, the only input here, occ (1 - occ) takes the 1 / f back, so the two
+// differ by an ulp of term_i g_i per sample -- below this path's f16 operand error by orders of magnitude.  grid (blocks, C); block b of class c writes loss partial (c, b) -- nb = gridDim.x for
 // finish_class.
 template <int K, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(

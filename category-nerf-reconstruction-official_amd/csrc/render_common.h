@@ -43,13 +43,19 @@ __device__ __forceinline__ float incl_prod(float v, int lane) {
   }
   return v;
 }
-__device__ __forceinline__ float incl_suffix_sum(float v, int lane) {
+__device__ __forceinline__ double incl_suffix_sum(double v, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const float p = __shfl_down(v, o, 64);
+    const double p = __shfl_down(v, o, 64);
     if (lane + o < 64) v += p;
   }
   return v;
+}
+// exclusive suffix sum (k > i) from the inclusive one: the next lane's value, as composite.hip's wave_excl_suffix
+// (not incl - v, whose rounding the backward divides by f_i).  g, the suffix sum and d occ in double, as there.
+__device__ __forceinline__ double excl_suffix(double incl, int lane) {
+  const double nxt = __shfl_down(incl, 1, 64);
+  return lane == 63 ? 0.0 : nxt;
 }
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
@@ -98,15 +104,17 @@ __device__ __forceinline__ RayOut ray_small(const float* __restrict__ sigmas, co
   const float dG = grad_scale * color_scaling * sgn(rc1) * fo * wc;
   const float dBl = grad_scale * color_scaling * sgn(rc2) * fo * wc;
   const float dO = grad_scale * opacity_scaling * sgn(ro) * fs * wo;
-  const float g = live ? dD * zz + dR * c0 + dG * c1 + dBl * c2 + dO : 0.0f;
-  const float tg = term * g;
-  const float incl_suf = incl_suffix_sum(tg, lane);
-  const float suf = (incl_suf - tg) + 0.0f;
+  const double g = live ? (double)dD * (double)zz + (double)dR * (double)c0 + (double)dG * (double)c1 +
+                              (double)dBl * (double)c2 + (double)dO
+                        : 0.0;
+  const double tg = (double)term * g;
+  const double incl_suf = incl_suffix_sum(tg, lane);
+  const double suf = excl_suffix(incl_suf, lane) + 0.0;
   r.live = live;
   r.dsig = 0.0f; r.dc0 = 0.0f; r.dc1 = 0.0f; r.dc2 = 0.0f;
   if (live) {
-    const float docc = T * g - suf / f;
-    r.dsig = docc * occ * (1.0f - occ);
+    const double docc = (double)T * g - suf / (double)f;
+    r.dsig = (float)(docc * (double)occ * (1.0 - (double)occ));
     r.dc0 = term * dR; r.dc1 = term * dG; r.dc2 = term * dBl;
   }
   return r;

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
     const float dBl = grad_scale * color_scaling * sgn(rc2) * fo * wc;
     const float dO = grad_scale * opacity_scaling * sgn(ro) * fs * wo;
     // ---- backward composite (back to front, suffix sum carried across chunks) ------------------------------------
-    float suf_carry = 0.0f;
+    double suf_carry = 0.0;
     for (int ch = nchunk - 1; ch >= 0; --ch) {
       const int s = ch * 64 + lane;
       const bool live = s < S;
@@ -161,17 +161,18 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
       if (lane == 0) excl = 1.0f;
       const float T = carry_in[ch] * excl;
       const float term = occ * T;
-      float g = 0.0f;
+      double g = 0.0;  // g, the suffix sum and d occ in double, as composite.hip
       if (live) {
         const float* cp = colors + (base + s) * 3;
-        g = dD * z[base + s] + dR * cp[0] + dG * cp[1] + dBl * cp[2] + dO;
+        g = (double)dD * (double)z[base + s] + (double)dR * (double)cp[0] + (double)dG * (double)cp[1] +
+            (double)dBl * (double)cp[2] + (double)dO;
       }
-      const float tg = term * g;
-      const float incl_suf = incl_suffix_sum(tg, lane);
-      const float suf = (incl_suf - tg) + suf_carry;
+      const double tg = (double)term * g;
+      const double incl_suf = incl_suffix_sum(tg, lane);
+      const double suf = excl_suffix(incl_suf, lane) + suf_carry;
       if (live) {
-        const float docc = T * g - suf / f;
-        d_sigmas[base + s] = docc * occ * (1.0f - occ);
+        const double docc = (double)T * g - suf / (double)f;
+        d_sigmas[base + s] = (float)(docc * (double)occ * (1.0 - (double)occ));
         float* dc = d_colors + (base + s) * 3;
         dc[0] = term * dR; dc[1] = term * dG; dc[2] = term * dBl;
       }

@@ -35,6 +35,23 @@ def _trunk_forward(p, e, zlat):
     return sig, torch.sigmoid(lin("rgb.2", y))
 
 
+def _trunk_preacts(p, e, zlat):
+    """Every ReLU pre-activation of _trunk_forward, in layer order: the four masked layers (encoding_xyz, shape_layer_1,
+    cat_layer, encoding_viewdir), shape_layer_2, texture_layer_1 and rgb.0 -- each (C, R, S, width)."""
+    lin = lambda n, x: torch.matmul(x, p[n + ".weight"].transpose(-1, -2)[:, None]) + p[n + ".bias"][:, None, None, :]
+    z = lambda k: zlat[:, :, None, k, :]
+    e1, e2 = e[..., :E1], e[..., E1:]
+    a0 = lin("encoding_xyz.0", e1)
+    a1 = lin("shape_layer_1.0", torch.relu(a0) + z(0))
+    a2 = lin("cat_layer.0", torch.cat((torch.relu(a1) + z(1), e1), -1))
+    s2 = lin("shape_layer_2.0", torch.relu(a2) + z(2))
+    y = lin("encoding_shape", torch.relu(s2))
+    a3 = lin("encoding_viewdir.0", torch.cat((y, e2), -1))
+    t1 = lin("texture_layer_1.0", torch.relu(a3) + z(3))
+    r0 = lin("rgb.0", torch.relu(t1))
+    return [a0, a1, a2, a3, s2, t1, r0]
+
+
 def _with_grad(fn):
     def wrapped(*a, **k):
         with torch.enable_grad():      # these run inside autograd.Function.backward, where grad mode is off
