@@ -1,0 +1,402 @@
+// Scene view rendering: which pixel rays meet which entity's volume and over what depth range
+// (cnr_view_segments_*), the sample points of every segment in its field's frame (cnr_view_points), and the per-pixel merge
+// of several fields' samples into one alpha composite with an instance label (cnr_view_composite).  The field values in
+// between come from the existing kernels (cnr_field_fwd, the background forward).
+//
+// An entity is a box: to_box (3,4) maps a world point into [-1,1]^3.  Ray directions are (x, y, 1) in the camera frame (z-depth
+// convention, not normalised) and every transform is a similarity, so the parameter z of o + z d is the camera depth in every
+// frame; samples of different entities along one pixel ray are merged by z.
+//
+// Determinism: no atomics.  Segment positions come from wave ballots and one exclusive scan of the per-wave counts; the
+// composite's sums run in a fixed order.  The count and emit launches evaluate the same slab test (one device function,
+// no fused multiply-add contraction) so that they agree on every hit.
+#include "cnr_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int KMAX = CNR_VIEW_KMAX;
+constexpr int SMAX = CNR_VIEW_SMAX;
+
+struct Cam { float r[9]; float t[3]; };
+
+__device__ __forceinline__ Cam load_cam(const float* __restrict__ T) {
+  Cam c;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c.r[i * 3 + j] = T[i * 4 + j];
+    c.t[i] = T[i * 4 + 3];
+  }
+  return c;
+}
+
+// a (3,4) affine applied to a point / to a direction, sums left to right
+__device__ __forceinline__ void affine_point(const float* __restrict__ A, float x, float y, float z, float* out) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = A[k * 4 + 0] * x + A[k * 4 + 1] * y + A[k * 4 + 2] * z + A[k * 4 + 3];
+}
+__device__ __forceinline__ void affine_dir(const float* __restrict__ A, float x, float y, float z, float* out) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = A[k * 4 + 0] * x + A[k * 4 + 1] * y + A[k * 4 + 2] * z;
+}
+
+// slab test of t + z dw against the box of `A`; [zn, zf] clipped to [zmin, zmax].  An axis with a zero direction component
+// passes iff the origin lies inside the slab and bounds nothing (no 0 * inf).
+__device__ __forceinline__ bool slab(const float* __restrict__ A, const Cam& cam, const float* dw, float zmin, float zmax,
+                                     float& zn, float& zf) {
+  float o[3], d[3];
+  affine_point(A, cam.t[0], cam.t[1], cam.t[2], o);
+  affine_dir(A, dw[0], dw[1], dw[2], d);
+  zn = zmin; zf = zmax;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (d[k] == 0.0f) {
+      ok = ok && (fabsf(o[k]) <= 1.0f);
+    } else {
+      const float t1 = (-1.0f - o[k]) / d[k], t2 = (1.0f - o[k]) / d[k];
+      zn = fmaxf(zn, fminf(t1, t2));
+      zf = fminf(zf, fmaxf(t1, t2));
+    }
+  }
+  return ok && zf > zn;
+}
+
+__device__ __forceinline__ void world_dir(const Cam& cam, const float* __restrict__ dirs, int64_t p, float* dw) {
+  const float x = dirs[p * 3 + 0], y = dirs[p * 3 + 1], z = dirs[p * 3 + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dw[k] = cam.r[k * 3 + 0] * x + cam.r[k * 3 + 1] * y + cam.r[k * 3 + 2] * z;
+}
+
+// workspace: counts (E * nw) i32 | over (nw) i32 | offsets (E * nw) i64, nw = waves of 64 pixels
+__host__ __device__ inline int64_t n_waves(int64_t P) { return (P + 63) / 64; }
+__host__ __device__ inline int64_t ws_counts_bytes(int64_t P, int E) { return ((E + 1) * n_waves(P) * 4 + 15) / 16 * 16; }
+
+__global__ __launch_bounds__(256) void segments_count_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                             const float* __restrict__ to_box, int64_t P, int E, float zmin,
+                                                             float zmax, int* __restrict__ counts, int* __restrict__ over) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = n_waves(P);
+  const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= nw) return;
+  const int64_t p = wv * 64 + lane;
+  const bool live = p < P;
+  const Cam cam = load_cam(T_wc);
+  float dw[3] = {0.f, 0.f, 0.f};
+  if (live) world_dir(cam, dirs, p, dw);
+  int mine = 0;
+  for (int e = 0; e < E; ++e) {
+    float zn, zf;
+    const bool hit = live && slab(to_box + (int64_t)e * 12, cam, dw, zmin, zmax, zn, zf);
+    const unsigned long long m = __ballot(hit);
+    mine += hit ? 1 : 0;
+    if (lane == 0) counts[(int64_t)e * nw + wv] = __popcll(m);
+  }
+  const unsigned long long mo = __ballot(mine > KMAX);
+  if (lane == 0) over[wv] = __popcll(mo);
+}
+
+// one block: exclusive scan of the (E * nw) counts in (entity, wave) order -> offsets; entity_offset, total, overflow
+__global__ __launch_bounds__(1024) void segments_scan_kernel(const int* __restrict__ counts, const int* __restrict__ over,
+                                                             int64_t nw, int E, int64_t* __restrict__ offsets,
+                                                             int64_t* __restrict__ entity_offset, int64_t* __restrict__ total,
+                                                             int64_t* __restrict__ overflow) {
+  __shared__ long long part[1024];
+  const int t = threadIdx.x;
+  const int64_t M = nw * E;
+  const int64_t per = (M + 1023) / 1024;
+  const int64_t lo = (int64_t)t * per, hi = lo + per < M ? lo + per : M;
+  long long s = 0;
+  for (int64_t i = lo; i < hi; ++i) s += counts[i];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const long long v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  long long run = t ? part[t - 1] : 0;
+  for (int64_t i = lo; i < hi; ++i) { offsets[i] = run; run += counts[i]; }
+  if (t == 1023) { total[0] = part[1023]; if (entity_offset) entity_offset[E] = part[1023]; }
+  __syncthreads();
+  if (entity_offset) for (int e = t; e < E; e += 1024) entity_offset[e] = offsets[(int64_t)e * nw];
+  if (overflow) {
+    long long ov = 0;
+    for (int64_t i = t; i < nw; i += 1024) ov += over[i];
+    __syncthreads();
+    part[t] = ov;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) { if (t < o) part[t] += part[t + o]; __syncthreads(); }
+    if (t == 0) overflow[0] = part[0];
+  }
+}
+
+__global__ __launch_bounds__(256) void segments_emit_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                            const float* __restrict__ to_box, int64_t P, int E, float zmin,
+                                                            float zmax, const int64_t* __restrict__ offsets,
+                                                            int* __restrict__ seg_pixel, int* __restrict__ seg_entity,
+                                                            float* __restrict__ seg_z, int* __restrict__ pix_segs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = n_waves(P);
+  const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= nw) return;
+  const int64_t p = wv * 64 + lane;
+  const bool live = p < P;
+  const Cam cam = load_cam(T_wc);
+  float dw[3] = {0.f, 0.f, 0.f};
+  if (live) world_dir(cam, dirs, p, dw);
+  int ks[KMAX];
+  float kz[KMAX];
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) { ks[j] = -1; kz[j] = 0.f; }
+  int n = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int e = 0; e < E; ++e) {
+    float zn, zf;
+    const bool hit = live && slab(to_box + (int64_t)e * 12, cam, dw, zmin, zmax, zn, zf);
+    const unsigned long long m = __ballot(hit);
+    if (!hit) continue;
+    const int64_t s = offsets[(int64_t)e * nw + wv] + __popcll(m & below);
+    seg_pixel[s] = (int)p;
+    seg_entity[s] = e;
+    seg_z[s * 2 + 0] = zn;
+    seg_z[s * 2 + 1] = zf;
+    if (n < KMAX) {
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j) if (j == n) { ks[j] = (int)s; kz[j] = zn; }
+      ++n;
+    } else {                       // more than KMAX boxes: keep the KMAX nearest by z_near (ties: the earlier entity), entity order
+      int w = 0;
+      float wz = kz[0];
+#pragma unroll
+      for (int j = 1; j < KMAX; ++j) if (kz[j] >= wz) { w = j; wz = kz[j]; }
+      if (zn < wz) {
+#pragma unroll
+        for (int j = 0; j < KMAX - 1; ++j) if (j >= w) { ks[j] = ks[j + 1]; kz[j] = kz[j + 1]; }
+        ks[KMAX - 1] = (int)s; kz[KMAX - 1] = zn;
+      }
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) pix_segs[p * KMAX + j] = ks[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void points_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                     const float* __restrict__ to_field, const int* __restrict__ seg_pixel,
+                                                     const int* __restrict__ seg_entity, const float* __restrict__ seg_z,
+                                                     int64_t N, int S, float* __restrict__ z_out,
+                                                     float* __restrict__ pts) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= N * S) return;
+  const int64_t s = idx / S;
+  const int i = (int)(idx - s * S);
+  const Cam cam = load_cam(T_wc);
+  const int64_t p = seg_pixel[s];
+  const float* F = to_field + (int64_t)seg_entity[s] * 12;
+  const float zn = seg_z[s * 2], zf = seg_z[s * 2 + 1];
+  const float z = zn + ((float)i + 0.5f) * (zf - zn) / (float)S;
+  const float cx = z * dirs[p * 3 + 0], cy = z * dirs[p * 3 + 1], cz = z * dirs[p * 3 + 2];
+  float w[3], f[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w[k] = cam.r[k * 3 + 0] * cx + cam.r[k * 3 + 1] * cy + cam.r[k * 3 + 2] * cz + cam.t[k];
+  affine_point(F, w[0], w[1], w[2], f);
+  z_out[idx] = z;
+  pts[idx * 3 + 0] = f[0]; pts[idx * 3 + 1] = f[1]; pts[idx * 3 + 2] = f[2];
+}
+
+__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// the number of elements of the ascending run zs[0..S) that are < v (strict) or <= v
+__device__ __forceinline__ int count_below(const float* zs, int S, float v, bool or_equal) {
+  int lo = 0, hi = S;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const float m = zs[mid];
+    if (or_equal ? (m <= v) : (m < v)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One wave (= one workgroup) per pixel.  LDS: zin | occ (later: term) | order, KMAX * S entries each.
+__global__ __launch_bounds__(64) void composite_kernel(const float* __restrict__ sigma, const float* __restrict__ color,
+                                                       const float* __restrict__ z, const int* __restrict__ pix_segs,
+                                                       const int* __restrict__ seg_entity, const int* __restrict__ entity_inst,
+                                                       int64_t P, int S, float thr, float* __restrict__ rgb_out,
+                                                       float* __restrict__ depth_out, float* __restrict__ opa_out,
+                                                       float* __restrict__ var_out, float* __restrict__ mass_out,
+                                                       int* __restrict__ inst_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int cap = KMAX * S;
+  float* zin = reinterpret_cast<float*>(smem);
+  float* occ = zin + cap;
+  unsigned short* order = reinterpret_cast<unsigned short*>(occ + cap);
+  const int lane = threadIdx.x;
+  const int64_t p = blockIdx.x;
+  int segs[KMAX];
+  int K = 0;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) { segs[j] = pix_segs[p * KMAX + j]; if (segs[j] >= 0 && K == j) K = j + 1; }
+  if (K == 0) {
+    if (lane == 0) {
+      rgb_out[p * 3 + 0] = 0.f; rgb_out[p * 3 + 1] = 0.f; rgb_out[p * 3 + 2] = 0.f;
+      depth_out[p] = 0.f; opa_out[p] = 0.f; var_out[p] = 0.f; inst_out[p] = -1;
+    }
+    if (lane < KMAX) mass_out[p * KMAX + lane] = 0.f;
+    return;
+  }
+  const int n = K * S;
+  // stage: z and occupancy of every sample, segment after segment
+  for (int idx = lane; idx < n; idx += 64) {
+    const int k = idx / S, i = idx - k * S;
+    int sg = segs[0];
+#pragma unroll
+    for (int j = 1; j < KMAX; ++j) if (j == k) sg = segs[j];
+    const int64_t g = (int64_t)sg * S + i;
+    zin[idx] = z[g];
+    occ[idx] = sigmoid_exact(sigma[g]);
+  }
+  __syncthreads();
+  // merged rank by (z, segment, sample): own index plus a binary search in every other segment
+  for (int idx = lane; idx < n; idx += 64) {
+    const int k = idx / S, i = idx - k * S;
+    const float v = zin[idx];
+    int r = i;
+    for (int k2 = 0; k2 < K; ++k2)
+      if (k2 != k) r += count_below(zin + k2 * S, S, v, k2 < k);
+    order[r] = (unsigned short)idx;
+  }
+  __syncthreads();
+  // transmittance: per-lane serial products over c consecutive ranks (c odd: conflict-free LDS stride), one exclusive scan
+  int c = (n + 63) / 64;
+  c |= 1;
+  const int r0 = lane * c;
+  float prod = 1.0f;
+  for (int j = 0; j < c; ++j) {
+    const int r = r0 + j;
+    if (r < n) prod *= 1.0f - occ[min((int)order[r], n - 1)] + 1e-10f;
+  }
+  float incl = prod;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float q = __shfl_up(incl, o, 64);
+    if (lane >= o) incl *= q;
+  }
+  float T = __shfl_up(incl, 1, 64);
+  if (lane == 0) T = 1.0f;
+  for (int j = 0; j < c; ++j) {
+    const int r = r0 + j;
+    if (r < n) {
+      const int idx = min((int)order[r], n - 1);      // (a rank is unique when every segment's z ascends, as documented)
+      const float oc = occ[idx];
+      occ[idx] = oc * T;                   // term, back at the sample's own place
+      T *= 1.0f - oc + 1e-10f;
+    }
+  }
+  __syncthreads();
+  // sums in source order: coalesced colour loads, one wave reduction per output
+  float so = 0.f, sd = 0.f, sr = 0.f, sg_ = 0.f, sb = 0.f;
+  float best = -1.0f;
+  int best_k = 0;
+  for (int k = 0; k < K; ++k) {
+    int sg = segs[0];
+#pragma unroll
+    for (int j = 1; j < KMAX; ++j) if (j == k) sg = segs[j];
+    float m = 0.f;
+    for (int i = lane; i < S; i += 64) {
+      const float term = occ[k * S + i];
+      const float* cp = color + ((int64_t)sg * S + i) * 3;
+      m += term;
+      sd += term * zin[k * S + i];
+      sr += term * cp[0]; sg_ += term * cp[1]; sb += term * cp[2];
+    }
+    m = cnr::wave_sum(m);
+    so += m;
+    if (m > best) { best = m; best_k = k; }
+    if (lane == 0) mass_out[p * KMAX + k] = m;
+  }
+  if (lane == 0) for (int k = K; k < KMAX; ++k) mass_out[p * KMAX + k] = 0.f;
+  sd = cnr::wave_sum(sd);
+  sr = cnr::wave_sum(sr); sg_ = cnr::wave_sum(sg_); sb = cnr::wave_sum(sb);
+  float sv = 0.f;
+  for (int idx = lane; idx < n; idx += 64) { const float dz = zin[idx] - sd; sv += occ[idx] * dz * dz; }
+  sv = cnr::wave_sum(sv);
+  if (lane == 0) {
+    int sgb = segs[0];
+#pragma unroll
+    for (int j = 1; j < KMAX; ++j) if (j == best_k) sgb = segs[j];
+    rgb_out[p * 3 + 0] = sr; rgb_out[p * 3 + 1] = sg_; rgb_out[p * 3 + 2] = sb;
+    depth_out[p] = sd; opa_out[p] = so; var_out[p] = sv;
+    inst_out[p] = so >= thr ? entity_inst[seg_entity[sgb]] : -1;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t cnr_view_segments_workspace_bytes(int64_t P, int E) {
+  if (P <= 0 || E <= 0) return 0;
+  return ws_counts_bytes(P, E) + n_waves(P) * E * 8;
+}
+
+extern "C" int cnr_view_segments_count(const float* T_wc, const float* dirs, const float* to_box, int64_t P, int E, float zmin,
+                                       float zmax, void* workspace, int64_t* entity_offset, int64_t* count_out,
+                                       int64_t* overflow, void* stream) {
+  if (!T_wc || !dirs || !to_box || !workspace || !entity_offset || !count_out || !overflow || P <= 0 || E <= 0)
+    return CNR_E_ARG;
+  if (P >= (1ll << 31) || E > 32767) return CNR_E_SHAPE;
+  const int64_t nw = n_waves(P);
+  int* counts = static_cast<int*>(workspace);
+  int* over = counts + nw * E;
+  int64_t* offsets = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + ws_counts_bytes(P, E));
+  hipLaunchKernelGGL(segments_count_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, (hipStream_t)stream, T_wc, dirs,
+                     to_box, P, E, zmin, zmax, counts, over);
+  CNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(segments_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, over, nw, E, offsets,
+                     entity_offset, count_out, overflow);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_segments_emit(const float* T_wc, const float* dirs, const float* to_box, int64_t P, int E, float zmin,
+                                      float zmax, const void* workspace, int* seg_pixel, int* seg_entity, float* seg_z,
+                                      int* pix_segs, void* stream) {
+  if (!T_wc || !dirs || !to_box || !workspace || !pix_segs || P <= 0 || E <= 0) return CNR_E_ARG;
+  if (P >= (1ll << 31) || E > 32767) return CNR_E_SHAPE;
+  const int64_t nw = n_waves(P);
+  const int64_t* offsets = reinterpret_cast<const int64_t*>(static_cast<const char*>(workspace) + ws_counts_bytes(P, E));
+  hipLaunchKernelGGL(segments_emit_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, (hipStream_t)stream, T_wc, dirs,
+                     to_box, P, E, zmin, zmax, offsets, seg_pixel, seg_entity, seg_z, pix_segs);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_points(const float* T_wc, const float* dirs, const float* to_field, const int* seg_pixel,
+                               const int* seg_entity, const float* seg_z, int64_t N, int S, float* z, float* pts,
+                               void* stream) {
+  if (!T_wc || !dirs || !to_field || !seg_pixel || !seg_entity || !seg_z || !z || !pts || N <= 0) return CNR_E_ARG;
+  if (S < 1 || S > SMAX) return CNR_E_SHAPE;
+  const int64_t blocks = (N * S + 255) / 256;
+  if (blocks >= (1ll << 31)) return CNR_E_SHAPE;
+  hipLaunchKernelGGL(points_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T_wc, dirs, to_field,
+                     seg_pixel, seg_entity, seg_z, N, S, z, pts);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_composite(const float* sigma, const float* color, const float* z, const int* pix_segs,
+                                  const int* seg_entity, const int* entity_inst, int64_t P, int S, float opacity_threshold,
+                                  float* rgb, float* depth, float* opacity, float* var, float* mass, int* instance,
+                                  void* stream) {
+  if (!sigma || !color || !z || !pix_segs || !seg_entity || !entity_inst || !rgb || !depth || !opacity || !var || !mass || !instance || P <= 0) return CNR_E_ARG;
+  if (S < 1 || S > SMAX) return CNR_E_SHAPE;
+  if (P >= (1ll << 31)) return CNR_E_SHAPE;
+  const unsigned lds = (unsigned)(KMAX * S * 10);        // <= 10 KiB: z, occupancy / term (f32) and the merged order (u16)
+  hipLaunchKernelGGL(composite_kernel, dim3((unsigned)P), dim3(64), lds, (hipStream_t)stream, sigma, color, z, pix_segs,
+                     seg_entity, entity_inst, P, S, opacity_threshold, rgb, depth, opacity, var, mass, instance);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}

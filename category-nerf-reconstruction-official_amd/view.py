@@ -1,0 +1,240 @@
+"""Scene view rendering: a camera pose in, an image of the composed scene out -- colour, depth, opacity,
+depth variance and an instance label per pixel -- with two edits that leave the trained state alone: move an entity by a
+world-to-world similarity, or hide it.
+
+An *entity* is one field with the box ``Trainer.meshing`` evaluates for it: the background, or one object of a category.
+Rays are cut against every box (``cnr_view_segments_*``), each segment gets uniform midpoint samples in its field's frame
+(``cnr_view_points``), the fields are evaluated by the kernels meshing uses (``cnr_field_fwd`` on the precise geometry
+branch, one launch per category; the background through ``eval_points``' three paths), and ``cnr_view_composite`` merges the
+samples of all segments of a pixel by camera depth into one alpha composite -- for one segment exactly the per-ray formulas
+of the training renderer (src/render_rays.py:25-50, src/loss.py:41-48).  There is no reference renderer to compare a whole
+image against: the composite is pinned to those per-ray formulas and the volumes to ``Trainer.meshing``'s."""
+import os
+
+import numpy as np
+import torch
+
+from . import _C, ops
+from .utils import get_transform_from_tensor_sim3
+
+KMAX, SMAX = 8, 128
+
+
+class Entity:
+    """inst_id, to_box / to_field (3,4) float64, and where its field lives: ``cat`` = -1 for the background, else the index of
+    its category in cls_dict order, ``row`` = the object's row in the category's code tables."""
+
+    def __init__(self, inst_id, to_box, to_field, cat, row):
+        self.inst_id, self.to_box, self.to_field, self.cat, self.row = int(inst_id), to_box, to_field, cat, row
+
+
+def _box_affine(center, R, half):
+    """diag(1/h) R^T [I | -c] (float64)"""
+    A = np.diag(1.0 / np.asarray(half, np.float64)) @ np.asarray(R, np.float64).T
+    return np.concatenate([A, -(A @ np.asarray(center, np.float64).reshape(3))[:, None]], 1)
+
+
+def _sim3_matrix(vec):
+    return get_transform_from_tensor_sim3(torch.as_tensor(vec).detach().cpu().double()).numpy()
+
+
+def scene_entities(cls_dict, scene_bg):
+    """The entity list of a scene: the background first, if present, then the categories in ``cls_dict`` order with their
+    objects in ``obj_ids`` order.  The volumes are the ones ``Trainer.meshing`` evaluates (trainer.py)."""
+    ident = np.eye(4)[:3]
+    out = []
+    if scene_bg is not None:
+        t = scene_bg.trainer
+        b = t.bound
+        out.append(Entity(0, _box_affine(b.center, b.R, np.asarray(b.extent, np.float64) / (2.0 * t.bound_extent)), ident.copy(), -1, 0))
+    for k, sc in enumerate(cls_dict.values()):
+        t = sc.trainer
+        for inst_id in sc.obj_ids:
+            if t.n_obj == 1:               # world frame
+                b = t.bound_dict[inst_id]
+                h = np.asarray(b.extent, np.float64) / (2.0 * t.bound_extent)
+                out.append(Entity(inst_id, _box_affine(b.center, b.R, h), ident.copy(), k, 0))
+            else:
+                extent = np.asarray(t.extent_dict[inst_id], np.float64)
+                h = (extent / np.max(extent / 2)) / (2.0 * t.bound_extent)
+                to_field = np.linalg.inv(_sim3_matrix(sc.object_tensor_dict[inst_id]))[:3]
+                out.append(Entity(inst_id, np.diag(1.0 / h) @ to_field, to_field, k, t.inst_id_to_index[inst_id]))
+    return out
+
+
+def edited(entities, transforms=None, hidden=()):
+    """The entities a render launches for: ``hidden`` dropped, ``transforms`` {inst_id: E (4,4) world -> world} applied as
+    to_box <- to_box E^-1, to_field <- to_field E^-1."""
+    transforms, hidden = dict(transforms or {}), set(hidden)
+    ids = [e.inst_id for e in entities]
+    for i in list(transforms) + list(hidden):
+        if ids.count(i) != 1:        # (a dataset may give an object the background's id 0: such an id cannot address an edit)
+            raise ValueError("inst_id {} names {} entities".format(i, ids.count(i)))
+    out = []
+    for e in entities:
+        if e.inst_id in hidden:
+            continue
+        if e.inst_id in transforms:
+            Einv = np.linalg.inv(np.asarray(transforms[e.inst_id], np.float64).reshape(4, 4))
+            e = Entity(e.inst_id, e.to_box @ Einv, e.to_field @ Einv, e.cat, e.row)
+        out.append(e)
+    return out
+
+
+def _bg_logits(t, pts, chunk_size=500000):
+    """sigma (x10 logit) and colour of the background field at pts (M,3): the three paths of Trainer.eval_points"""
+    sig, col = [], []
+    fused = t.eval_precision == "fused" and t.hidden_feature_size == 128
+    if fused:
+        flat = torch.cat([p.reshape(-1) for p in t.fc_occ_map.parameters()] + [t.pe.B_layer.weight.reshape(-1)]).contiguous()
+        assert flat.numel() == int(_C.load().cnr_bg_param_count())
+        packed = torch.empty(int(_C.load().cnr_bg_pack_bytes()), device=flat.device, dtype=torch.uint8)
+        _C.call("cnr_bg_pack", flat, packed)
+    for k in range(0, pts.shape[0], chunk_size):
+        p = pts[k:k + chunk_size].contiguous()
+        if fused:
+            s, c = torch.empty(p.shape[0], device=p.device), torch.empty(p.shape[0], 3, device=p.device)
+            _C.call("cnr_bg_forward", p, flat, packed, float(t.pe._scale), p.shape[0], s, c, None, None)
+        else:
+            s, c = t.fc_occ_map(t.pe(p[:, None, :]))
+        sig.append(s.reshape(-1))
+        col.append(c.reshape(-1, 3))
+    return torch.cat(sig), torch.cat(col)
+
+
+class SceneRenderer:
+    """``SceneRenderer(cls_dict, scene_bg, cfg)``: the arguments of ``FullStepTrainer.from_scene``.  Reads the modules'
+    parameters at every ``render`` -- after fused training run ``sync_to_modules()`` first, as for meshing."""
+
+    def __init__(self, cls_dict, scene_bg, cfg):
+        self.cls_dict, self.scene_bg, self.cfg = cls_dict, scene_bg, cfg
+        self.categories = list(cls_dict.values())
+        self.entities = scene_entities(cls_dict, scene_bg)
+        self.device = torch.device(cfg.training_device)
+        self.W, self.H = int(cfg.W), int(cfg.H)
+        self.zmin, self.zmax = float(cfg.min_depth), float(cfg.max_depth)
+        self._dirs = None
+        self.stage_events = None       # a list: render appends (stage name, device event) after every stage (tools/time_view.py)
+
+    def _mark(self, name):
+        if self.stage_events is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.stage_events.append((name, ev))
+
+    def dirs(self):
+        """the cameraInfo cache rows (W*H, 3), pixel w * H + h"""
+        if self._dirs is None:
+            from .scene_cateogries import cameraInfo
+            self._dirs = cameraInfo(self.cfg, device=self.device).rays_dir_cache.reshape(-1, 3).contiguous()
+        return self._dirs
+
+    def _category_operands(self, cats):
+        """{category index: (B, packed, packed_lo, bias rows (n_obj,4,32), scale)} of the categories in use"""
+        out = {}
+        for k in cats:
+            t = self.categories[k].trainer
+            rows = [t._codenerf_rows(i) for i in self.categories[k].obj_ids]
+            trunk, B = rows[0][0], rows[0][1]
+            brows = torch.cat([r[2] for r in rows], 0).contiguous()
+            out[k] = (B, ops.pack_weights(trunk), ops.pack_weights_lo(trunk), brows, float(t.pe._scale))
+        return out
+
+    def render(self, T_wc, n_samples=64, transforms=None, hidden=(), chunk=65536, opacity_threshold=0.5, return_samples=False):
+        """-> {rgb (W,H,3), depth, opacity, var (W,H) float32, instance (W,H) int32 (-1: nothing opaque enough)}; (W,H,...) as
+        every image here.  Pixels go through in chunks of ``chunk``; the result does not depend on it.  A pixel met by more
+        than 8 boxes raises ValueError.  ``return_samples``: also the intermediate arrays (single chunk only)."""
+        S, dev = int(n_samples), self.device
+        if not 1 <= S <= SMAX:
+            raise ValueError("n_samples must be in 1 .. {}".format(SMAX))
+        ents = edited(self.entities, transforms, hidden)
+        P_all = self.W * self.H
+        out = dict(rgb=torch.zeros(P_all, 3, device=dev), depth=torch.zeros(P_all, device=dev),
+                   opacity=torch.zeros(P_all, device=dev), var=torch.zeros(P_all, device=dev),
+                   instance=torch.full((P_all,), -1, device=dev, dtype=torch.int32))
+        shape = lambda r: {k: v.reshape(self.W, self.H, *v.shape[1:]) for k, v in r.items()}
+        if not ents:
+            return shape(out)
+        if return_samples and chunk < P_all:
+            raise ValueError("return_samples wants the whole image in one chunk")
+        E = len(ents)
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+        T = f32(np.asarray(T_wc.detach().cpu() if torch.is_tensor(T_wc) else T_wc, np.float64).reshape(4, 4))
+        to_box, to_field = f32(np.stack([e.to_box for e in ents])), f32(np.stack([e.to_field for e in ents]))
+        inst = torch.tensor([e.inst_id for e in ents], dtype=torch.int32, device=dev)
+        # entity runs that share a field evaluation: the background alone, a category's objects together
+        runs, e0 = [], 0
+        while e0 < E:
+            e1 = e0
+            while e1 < E and ents[e1].cat == ents[e0].cat:
+                e1 += 1
+            runs.append((ents[e0].cat, e0, e1))
+            e0 = e1
+        row_of = torch.tensor([e.row for e in ents], dtype=torch.int32, device=dev)
+        dirs_all = self.dirs()
+        with torch.no_grad(), torch.cuda.device(dev):
+            operands = self._category_operands([c for c, _, _ in runs if c >= 0])
+            for p0 in range(0, P_all, int(chunk)):
+                self._mark("start")
+                dirs = dirs_all[p0:p0 + int(chunk)]
+                P = dirs.shape[0]
+                ws = torch.empty(max(int(_C.load().cnr_view_segments_workspace_bytes(P, E)), 16), device=dev, dtype=torch.uint8)
+                ent_off = torch.empty(E + 1, device=dev, dtype=torch.int64)
+                counts = torch.empty(2, device=dev, dtype=torch.int64)
+                _C.call("cnr_view_segments_count", T, dirs, to_box, P, E, self.zmin, self.zmax, ws, ent_off, counts[0:1], counts[1:2])
+                N, overflow = (int(v) for v in counts.tolist())
+                if overflow > 0:
+                    raise ValueError("{} pixels are met by more than {} entity boxes".format(overflow, KMAX))
+                pix_segs = torch.empty(P, KMAX, device=dev, dtype=torch.int32)
+                seg_pixel = torch.empty(max(N, 1), device=dev, dtype=torch.int32)
+                seg_entity = torch.empty(max(N, 1), device=dev, dtype=torch.int32)
+                seg_z = torch.empty(max(N, 1), 2, device=dev)
+                _C.call("cnr_view_segments_emit", T, dirs, to_box, P, E, self.zmin, self.zmax, ws, seg_pixel, seg_entity, seg_z, pix_segs)
+                self._mark("segments")
+                if N == 0:
+                    continue
+                z, pts = torch.empty(N, S, device=dev), torch.empty(N, S, 3, device=dev)
+                _C.call("cnr_view_points", T, dirs, to_field, seg_pixel, seg_entity, seg_z, N, S, z, pts)
+                self._mark("points")
+                sigma, color = torch.empty(N, S, device=dev), torch.empty(N, S, 3, device=dev)
+                off = ent_off.tolist()
+                for cat, a, b in runs:
+                    s0, s1 = off[a], off[b]
+                    if s1 == s0:
+                        continue
+                    if cat < 0:
+                        sg, cl = _bg_logits(self.scene_bg.trainer, pts[s0:s1].reshape(-1, 3))
+                    else:
+                        B, packed, lo, brows, scale = operands[cat]
+                        ray_row = row_of[seg_entity[s0:s1].long()].reshape(1, -1).contiguous()
+                        sg, cl = ops.field_fwd(pts[s0:s1].reshape(1, s1 - s0, S, 3), B, packed, brows, ray_row, scale, packed_lo=lo)
+                    sigma[s0:s1], color[s0:s1] = sg.reshape(-1, S), cl.reshape(-1, S, 3)
+                    self._mark("field background" if cat < 0 else "field category {}".format(cat))
+                mass = torch.empty(P, KMAX, device=dev)
+                sl = slice(p0, p0 + P)
+                _C.call("cnr_view_composite", sigma, color, z, pix_segs, seg_entity, inst, P, S, float(opacity_threshold),
+                        out["rgb"][sl], out["depth"][sl], out["opacity"][sl], out["var"][sl], mass, out["instance"][sl])
+                self._mark("composite")
+                if return_samples:
+                    out["samples"] = dict(seg_pixel=seg_pixel[:N], seg_entity=seg_entity[:N], seg_z=seg_z[:N], entity_offset=ent_off,
+                                          pix_segs=pix_segs, z=z, pts=pts, sigma=sigma, color=color, mass=mass,
+                                          to_box=to_box, to_field=to_field, inst_ids=inst)
+        samples = out.pop("samples", None)
+        res = shape(out)
+        if samples is not None:
+            res["samples"] = samples
+        return res
+
+
+def render_to_files(result, out_dir):
+    """rgb.png (8 bit), depth.png (16 bit, millimetres) and instance.png (16 bit, -1 as 65535), transposed back to H x W."""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = (result["rgb"].detach().clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy().transpose(1, 0, 2)
+    Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(os.path.join(out_dir, "rgb.png"))
+    mm = (result["depth"].detach().double() * 1000).round().clamp(0, 65535).cpu().numpy().astype(np.uint16).T
+    Image.fromarray(np.ascontiguousarray(mm)).save(os.path.join(out_dir, "depth.png"))
+    inst = result["instance"].detach().cpu().numpy().astype(np.int64).T
+    if inst.max(initial=-1) >= 65535:
+        raise ValueError("instance ids above 65534 do not fit a 16-bit image")
+    Image.fromarray(np.ascontiguousarray(np.where(inst < 0, 65535, inst).astype(np.uint16))).save(os.path.join(out_dir, "instance.png"))

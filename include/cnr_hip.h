@@ -979,6 +979,47 @@ int64_t cnr_feature_nn_workspace_bytes(int64_t nq, int64_t nr);
 int cnr_feature_nn(const float* q, int64_t nq, const float* p, int64_t nr, int D, int* index_out, float* dist_out, void* workspace,
                    void* stream);
 
+/* ---- Scene view rendering: a camera pose in, an image of the composed scene out.  DESIGN.md section 3.11.
+ * An entity is a field with a box: to_box (E,3,4) maps a world point into [-1,1]^3 of the volume that is meshed for it,
+ * to_field (E,3,4) into the frame its field takes.  T_wc (4,4) row-major camera-to-world, dirs (P,3) the camera-frame pixel
+ * directions (x, y, 1) of cnr_camera_rays: the ray parameter z is the camera depth in every frame, since every transform is a
+ * similarity.  No atomics anywhere: every output is the same bit for bit from run to run.
+ *
+ * Segments.  Per (pixel, entity) a slab test of T_wc (z d, 1) in box coordinates: an axis whose direction component is exactly
+ * zero passes iff |origin| <= 1 there and bounds nothing; otherwise [z_near, z_far] is the intersection of the three slabs
+ * with [zmin, zmax], and a segment exists iff z_far > z_near.  cnr_view_segments_count writes count_out (1,) i64 = N,
+ * entity_offset (E+1,) i64 and overflow (1,) i64 = the number of pixels met by more than CNR_VIEW_KMAX boxes (all on the
+ * device) and keeps per-wave offsets in workspace (>= cnr_view_segments_workspace_bytes(P, E)); cnr_view_segments_emit, with
+ * the same inputs and workspace after it on the same stream, writes the segments in (entity, pixel) order -- seg_pixel (N,)
+ * i32, seg_entity (N,) i32, seg_z (N,2) f32 = z_near, z_far; entity e owns [entity_offset[e], entity_offset[e+1]) -- and
+ * pix_segs (P, CNR_VIEW_KMAX) i32: the segment indices of every pixel in entity order, -1-padded.  A pixel met by more boxes
+ * keeps the CNR_VIEW_KMAX nearest by z_near (ties: the earlier entity) in pix_segs; all of its segments are still emitted.
+ * P < 2^31, E <= 32767 (else CNR_E_SHAPE).  With N = 0 the three seg_* pointers may be NULL. */
+#define CNR_VIEW_KMAX 8
+#define CNR_VIEW_SMAX 128
+int64_t cnr_view_segments_workspace_bytes(int64_t P, int E);
+int cnr_view_segments_count(const float* T_wc, const float* dirs, const float* to_box, int64_t P, int E, float zmin,
+                            float zmax, void* workspace, int64_t* entity_offset, int64_t* count_out, int64_t* overflow,
+                            void* stream);
+int cnr_view_segments_emit(const float* T_wc, const float* dirs, const float* to_box, int64_t P, int E, float zmin,
+                           float zmax, const void* workspace, int* seg_pixel, int* seg_entity, float* seg_z, int* pix_segs,
+                           void* stream);
+/* S uniform midpoints per segment: z (N,S), z_i = z_near + (i + 0.5) (z_far - z_near) / S, and pts (N,S,3) =
+ * to_field[seg_entity] . (T_wc . (z_i d, 1)).  1 <= S <= CNR_VIEW_SMAX (else CNR_E_SHAPE). */
+int cnr_view_points(const float* T_wc, const float* dirs, const float* to_field, const int* seg_pixel, const int* seg_entity,
+                    const float* seg_z, int64_t N, int S, float* z, float* pts, void* stream);
+/* The merged composite.  sigma (N,S) the field kernels' x10 logit, color (N,S,3), z (N,S) ascending within a segment.  The
+ * samples of a pixel's segments (pix_segs row, at most CNR_VIEW_KMAX S of them) are ordered by (z, position in the row, sample
+ * index); occ_i = sigmoid(sigma_i), term_i = occ_i prod_{j<i} (1 - occ_j + 1e-10) as in cnr_composite_fwd, and
+ *   rgb (P,3) = sum term c | depth (P,) = sum term z | opacity (P,) = sum term | var (P,) = sum term (z - depth)^2
+ *   mass (P, CNR_VIEW_KMAX) = sum term per segment of the row (0 where the row is padded)
+ *   instance (P,) i32 = entity_inst[seg_entity[.]] of the segment with the largest mass (ties: the earlier one) when
+ *   opacity >= opacity_threshold, else -1.
+ * A pixel without a segment gives zeros and -1.  1 <= S <= CNR_VIEW_SMAX (else CNR_E_SHAPE), P < 2^31. */
+int cnr_view_composite(const float* sigma, const float* color, const float* z, const int* pix_segs, const int* seg_entity,
+                       const int* entity_inst, int64_t P, int S, float opacity_threshold, float* rgb, float* depth,
+                       float* opacity, float* var, float* mass, int* instance, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

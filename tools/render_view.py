@@ -1,0 +1,69 @@
+"""Renders the trained scene from one of the dataset's camera poses: builds the categories as train.py does (cameraInfo,
+get_dataset, one sceneCategory per class), loads the newest checkpoint of each from --logdir, and writes rgb.png, depth.png
+(16 bit, millimetres) and instance.png (16 bit, 65535 = nothing) into --out.  Two edits, neither of which touches the trained
+state: --move INST tx ty tz translates an instance in world coordinates, --hide INST leaves it out.
+
+    python tools/render_view.py --config configs/Replica/config_replica_room0.json --logdir logs/room0 --frame 0 --out view0
+        [--samples 64] [--move 12 0.3 0 0] [--hide 7]"""
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+
+def newest_checkpoint(logdir, cls_id):
+    files = sorted(glob.glob(os.path.join(logdir, "**", "cls_{}_iteration_*.pth".format(cls_id)), recursive=True),
+                   key=lambda f: int(os.path.splitext(f)[0].rsplit("_", 1)[1]))
+    return files[-1] if files else None
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--logdir", required=True, help="where save_checkpoints wrote cls_<id>_iteration_<n>.pth")
+    ap.add_argument("--frame", type=int, default=0, help="the dataset frame whose pose is rendered")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--samples", type=int, default=64)
+    ap.add_argument("--move", nargs=4, action="append", default=[], metavar=("INST", "TX", "TY", "TZ"))
+    ap.add_argument("--hide", type=int, action="append", default=[], metavar="INST")
+    ap.add_argument("--allow-pickle", action="store_true", help="unpickle the checkpoints instead of the weights-only read: needed for a background's box object and for numpy "
+                    "scalar ids (trusted files only)")
+    a = ap.parse_args()
+    import cnr_amd as cnr
+    from cnr_amd.scene_cateogries import cameraInfo, sceneCategory
+    cfg = cnr.cfg.Config(a.config)
+    cam_info = cameraInfo(cfg)
+    data = cnr.dataset.get_dataset(cfg)
+    cls_dict, scene_bg = {}, None
+    for cls_id in data.inst_dict.keys():                              # train.py:46-64
+        sc = sceneCategory(cfg, cls_id, data.inst_dict[cls_id], data.sample_dict, cam_info.rays_dir_cache)
+        ckpt = newest_checkpoint(a.logdir, cls_id)
+        if ckpt is None:
+            raise SystemExit("no checkpoint of class {} under {}".format(cls_id, a.logdir))
+        sc.load_checkpoints(ckpt, allow_pickle=a.allow_pickle)
+        if cls_id == 0:
+            scene_bg = sc
+        else:
+            cls_dict[cls_id] = sc
+    renderer = cnr.view.SceneRenderer(cls_dict, scene_bg, cfg)
+    transforms = {}
+    for inst, tx, ty, tz in a.move:
+        E = np.eye(4)
+        E[:3, 3] = float(tx), float(ty), float(tz)
+        transforms[int(inst)] = E
+    T_wc = np.asarray(data.sample_dict[a.frame]["T"], np.float64)
+    with torch.no_grad():
+        result = renderer.render(T_wc, n_samples=a.samples, transforms=transforms, hidden=set(a.hide))
+    cnr.view.render_to_files(result, a.out)
+    shown = sorted(int(i) for i in torch.unique(result["instance"]).tolist())
+    print("wrote rgb.png, depth.png, instance.png to {}; instances in view: {}".format(a.out, shown))
+
+
+if __name__ == "__main__":
+    main()
