@@ -342,6 +342,14 @@ def render_loss_workspace_bytes(C, R):
     return int(load().cnr_render_loss_workspace_bytes(int(C), int(R)))
 
 
+def workspace(nbytes, dev, what):
+    """the uint8 device tensor for a `*_workspace_bytes` answer (at least one byte); a negative answer is the query's error"""
+    nbytes = int(nbytes)
+    if nbytes < 0:
+        raise CnrError(f"{what}: workspace query failed with {nbytes}")
+    return torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+
+
 def device_info():
     n_cu, lds, is950 = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     rc = load().cnr_device_info(ctypes.byref(n_cu), ctypes.byref(lds), ctypes.byref(is950))

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import embedding, model, render_rays
+from . import _C, embedding, model, render_rays
 from .scene_cateogries import stratified_bins
 
 N_PROBE = 100          # phi x theta grid (src/category_registration.py:96-98)
@@ -178,14 +178,10 @@ def icp_device(source, target, T0, max_corr, max_iteration=100):
     cnr_icp_step / cnr_icp_update together; open3d's convergence test (1e-6 on fitness and rmse), at most max_iteration
     updates.  A converged start freezes on the device; the host reads the flags every 10 iterations.
     -> (T (B,4,4) f64 numpy, state (B,4) numpy: fitness, rmse, flag, updates)"""
-    from . import _C
     dev = source.device
     T = torch.from_numpy(np.ascontiguousarray(np.asarray(T0, np.float64).reshape(-1, 4, 4))).to(dev)
     B, n, m = len(T), len(source), len(target)
-    nbytes = int(_C.load().cnr_icp_workspace_bytes(n, m, B))
-    if nbytes < 0:
-        raise _C.CnrError(f"cnr_icp_step: workspace query failed with {nbytes}")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    ws = _C.workspace(_C.load().cnr_icp_workspace_bytes(n, m, B), dev, "cnr_icp_step")
     state = torch.zeros(B, 4, device=dev, dtype=torch.float64)
     sums = torch.zeros(B, 17, device=dev, dtype=torch.float64)
     for it in range(int(max_iteration) + 1):
@@ -298,7 +294,6 @@ def compatibility_threshold(noise_bound=0.01, cbar2=1.0):
 def compatibility_graph(A, B, noise_bound=0.01, cbar2=1.0):
     """Stage 2 (cnr_teaser_graph).  A, B (N,3) f32 device tensors -> (adj (N, ceil(N/64)) int64 device tensor: bit j & 63 of word
     j >> 6 of row i says i ~ j, i.e. | |B_i - B_j| - |A_i - A_j| | <= 2 noise_bound sqrt(cbar2) in fp32; deg (N,) int32)"""
-    from . import _C
     N = len(A)
     if not 1 <= N <= TEASER_MAX_N or A.shape != (N, 3) or B.shape != (N, 3):
         raise ValueError(f"compatibility_graph: (N,3) correspondences with 1 <= N <= {TEASER_MAX_N}")
@@ -323,8 +318,6 @@ def max_clique(adj, deg, search_budget=None):
     """Stage 3 (cnr_clique_search).  -> (clique: int64 host array of vertices, ascending in clique_order(deg); info: size, exact,
     steps, find_steps, max_root_steps, roots_out_of_budget, greedy_size, flags).  With exact the clique is the maximum clique
     that is lexicographically smallest in positions of clique_order(deg); without, it is a clique and its size a lower bound."""
-    from . import _C
-    from .utils import _workspace
     N, dev = len(deg), adj.device
     if not (adj.is_cuda and deg.device == dev and adj.dtype == torch.int64 and adj.shape == (N, (N + 63) // 64)
             and deg.dtype == torch.int32 and deg.dim() == 1 and 1 <= N <= TEASER_MAX_N):
@@ -335,7 +328,7 @@ def max_clique(adj, deg, search_budget=None):
         raise ValueError("search_budget must lie in [1, 2^31)")
     order = clique_order(deg)
     max_degree = int(deg.max())
-    ws = _workspace(_C.load().cnr_clique_workspace_bytes(N, max_degree), dev, "cnr_clique_search")
+    ws = _C.workspace(_C.load().cnr_clique_workspace_bytes(N, max_degree), dev, "cnr_clique_search")
     out = torch.zeros(max_degree + 1, device=dev, dtype=torch.int32)
     info = torch.zeros(8, device=dev, dtype=torch.int64)
     _C.call("cnr_clique_search", adj, order, N, max_degree, budget, ws, out, info)
@@ -486,7 +479,6 @@ FEATURE_MAX_D = 64
 def compute_fpfh_feature(pcd, radius, max_nn):
     """open3d's compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) for a utils.PointCloud with normals: ONE
     hybrid search, cnr_spfh, cnr_fpfh -> (n,33) f64 device tensor (open3d's fpfh.data transposed)"""
-    from . import _C
     from .utils import hybrid_search
     if pcd.normals_device is None:
         raise ValueError("compute_fpfh_feature: the cloud has no normals; call estimate_normals first")
@@ -503,15 +495,13 @@ def compute_fpfh_feature(pcd, radius, max_nn):
 def feature_nn(q, p):
     """cnr_feature_nn: q (nq,D), p (nr,D) device tensors, rounded to f32 -> (index (nq,) int32: the lowest row of p with the
     least sequential fp32 sum of squared differences, that sum (nq,) f32)"""
-    from . import _C
-    from .utils import _workspace
     q, p = q.to(torch.float32).contiguous(), p.to(device=q.device, dtype=torch.float32).contiguous()
     if q.dim() != 2 or p.dim() != 2 or q.shape[1] != p.shape[1] or not 1 <= q.shape[1] <= FEATURE_MAX_D or len(p) < 1:
         raise ValueError(f"feature_nn: q (nq,D) and p (nr,D) with 1 <= D <= {FEATURE_MAX_D} and nr >= 1")
     index = torch.empty(len(q), device=q.device, dtype=torch.int32)
     dist = torch.empty(len(q), device=q.device, dtype=torch.float32)
     if len(q):
-        ws = _workspace(_C.load().cnr_feature_nn_workspace_bytes(len(q), len(p)), q.device, "cnr_feature_nn")
+        ws = _C.workspace(_C.load().cnr_feature_nn_workspace_bytes(len(q), len(p)), q.device, "cnr_feature_nn")
         _C.call("cnr_feature_nn", q, len(q), p, len(p), int(q.shape[1]), index, dist, ws)
     return index, dist
 

@@ -14,14 +14,20 @@
 // No float atomics, every loop bounded, results bit-identical run to run.  Every fp64 (and, in cnr_feature_nn, fp32) product,
 // sum and quotient is rounded on its own: no contraction in this file.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #include <math.h>
 
 #pragma clang fp contract(off)
 
+// (not all of namespace cnr: cnr_feature_nn has tile constants of its own under the names of cnr_nn_dist's)
+using cnr::align256;
+using cnr::AXIS_BITS;
+using cnr::AXIS_MASK;
+using cnr::grid_of;
+using cnr::lower_bound;
+
 namespace {
-constexpr int AXIS_BITS = 21;                              // the cell keys of cnr_radius_cell_keys (csrc/tsdf.hip)
-constexpr int64_t AXIS_MASK = ((int64_t)1 << AXIS_BITS) - 1;
 constexpr int WAVE = 64;
 constexpr int HS_MAX_NN = 128;
 constexpr int HS_CAP = 512;                                // candidates a wave buffers before it cuts back: 6 KB of LDS
@@ -34,21 +40,6 @@ constexpr int JACOBI_SWEEPS = 8;
 constexpr int NN_BLOCK = 256;                              // queries per workgroup of cnr_feature_nn
 constexpr int NN_TILE = 64;                                // reference rows per LDS tile
 constexpr int NN_MAX_D = 64;
-
-inline unsigned grid_of(int64_t n, int block, int64_t cap) {
-  const int64_t b = (n + block - 1) / block;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-// first index in the ascending cells[0 .. C) whose value is >= key
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ cells, int64_t C, int64_t key) {
-  int64_t lo = 0, hi = C;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (cells[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // ---- hybrid search -----------------------------------------------------------------------------------------------------
 // (key, index) ascending: key = the bits of the non-negative double d2, which order like the doubles themselves
@@ -410,7 +401,7 @@ inline NnPlan nn_plan(int64_t nq, int64_t nr) {
   want = want < 1 ? 1 : (want > tiles ? tiles : (want > 65535 ? 65535 : want));
   P.chunk_rows = (tiles + want - 1) / want * NN_TILE;
   P.chunks = (int)((nr + P.chunk_rows - 1) / P.chunk_rows);
-  P.off_dist = (P.chunks * nq * (int64_t)sizeof(int) + 255) / 256 * 256;
+  P.off_dist = align256(P.chunks * nq * (int64_t)sizeof(int));
   P.bytes = P.off_dist + P.chunks * nq * (int64_t)sizeof(float);
   return P;
 }

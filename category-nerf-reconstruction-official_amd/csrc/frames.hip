@@ -12,8 +12,11 @@
 //                                          row / column / class min and max into LDS partials when the frame has at most
 //                                          FR_PRIV ids, else straight into the global table.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #pragma clang fp contract(off)
+
+using cnr::align256;
 
 namespace {
 constexpr int FR_BLOCK = 256;
@@ -23,7 +26,6 @@ constexpr int FR_MAX_WORDS = (FR_MAX_BOUND + 31) / 32;
 constexpr int FR_PRIV = 1024;                    // LDS-privatised statistics up to this many ids per frame
 constexpr int FR_NSTAT = CNR_FRAME_NSTAT;        // count, row min, row max, col min, col max, class min, class max
 
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 struct FrLayout {
   int64_t nw, off_rank, off_cnt, bytes;
 };

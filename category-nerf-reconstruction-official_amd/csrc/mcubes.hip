@@ -12,21 +12,22 @@
 // In-wave prefix sums run on ballots and mbcnt over the bit planes of the per-lane counts (counts < 8 for vertices, < 8 for
 // triangles per cell: three planes each), the wave totals through LDS.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #define MC_CONST __constant__ const
 #include "mc_table.h"
 
+using namespace cnr;
+
 namespace {
 constexpr int MC_BLOCK = 256;
 constexpr int MC_WAVES = MC_BLOCK / 64;
-constexpr int MC_SCAN_THREADS = 1024;
 
 // workspace: info (u16 per point: bits 0-2 owned crossed edges, bits 3-10 the cell's case) | vbase (i32 per point) |
 // per-workgroup counts (i32 x 2) | their exclusive offsets (i64 x 2)
 struct McLayout {
   int64_t n, nblk, off_vbase, off_cnt, off_ofs, bytes;
 };
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 inline McLayout mc_layout(int D) {
   McLayout L;
   L.n = (int64_t)D * D * D;
@@ -40,35 +41,11 @@ inline McLayout mc_layout(int D) {
 
 __device__ __forceinline__ bool inside(float v, float level) { return v > level; }   // NaN: outside
 
-// exclusive prefix over the lanes below this one, and the wave total, of a per-lane count in [0, 8)
-__device__ __forceinline__ int wave_prefix3(int c, int* total) {
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    const uint64_t m = __ballot((c >> b) & 1);
-    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    pre += below << b;
-    tot += __popcll(m) << b;
-  }
-  *total = tot;
-  return pre;
-}
-
 // block-wide exclusive prefix of c (each < 8) in point order, and the block total
 __device__ __forceinline__ int block_prefix(int c, int* s_wave, int* block_total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int wtot;
-  const int pre = wave_prefix3(c, &wtot);
-  if (lane == 0) s_wave[wave] = wtot;
-  __syncthreads();
-  int base = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < MC_WAVES; ++w) {
-    base += w < wave ? s_wave[w] : 0;
-    all += s_wave[w];
-  }
-  *block_total = all;
-  return base + pre;
+  const int pre = wave_prefix_bits<3>(c, &wtot);
+  return block_prefix_waves<MC_WAVES>(pre, wtot, s_wave, block_total);
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_classify_kernel(const float* __restrict__ vol, int D, float level,
@@ -95,61 +72,12 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_kernel(const float* __re
     }
     info[p] = (uint16_t)(mask | (cs << 3));
   }
-  int vt, tt;
-  const int nv = __popc(mask), nt = MC_NTRI[cs];
-  wave_prefix3(nv, &vt);
-  wave_prefix3(nt, &tt);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_v[wave] = vt;
-    s_t[wave] = tt;
-  }
-  __syncthreads();
+  int a, b;
+  block_prefix(__popc(mask), s_v, &a);
+  block_prefix(MC_NTRI[cs], s_t, &b);
   if (threadIdx.x == 0) {
-    int a = 0, b = 0;
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; ++w) {
-      a += s_v[w];
-      b += s_t[w];
-    }
     blk_counts[2 * blockIdx.x] = a;
     blk_counts[2 * blockIdx.x + 1] = b;
-  }
-}
-
-// one workgroup: every thread sums a contiguous run of workgroup counts, a block scan of those sums, then the run again
-__global__ __launch_bounds__(MC_SCAN_THREADS) void mc_scan_kernel(const int* __restrict__ blk_counts, int64_t nblk,
-                                                                  int64_t* __restrict__ ofs, int64_t* __restrict__ totals) {
-  __shared__ int64_t s[2][MC_SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t per = (nblk + MC_SCAN_THREADS - 1) / MC_SCAN_THREADS;
-  const int64_t b0 = t * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-  int64_t sv = 0, st = 0;
-  for (int64_t b = b0; b < b1; ++b) {
-    sv += blk_counts[2 * b];
-    st += blk_counts[2 * b + 1];
-  }
-  s[0][t] = sv;
-  s[1][t] = st;
-  __syncthreads();
-  // Hillis-Steele inclusive scan over the thread sums (exact integer sums: the order does not matter for the result)
-  for (int d = 1; d < MC_SCAN_THREADS; d <<= 1) {
-    const int64_t av = t >= d ? s[0][t - d] : 0, at = t >= d ? s[1][t - d] : 0;
-    __syncthreads();
-    s[0][t] += av;
-    s[1][t] += at;
-    __syncthreads();
-  }
-  int64_t ov = s[0][t] - sv, ot = s[1][t] - st;
-  for (int64_t b = b0; b < b1; ++b) {
-    ofs[2 * b] = ov;
-    ofs[2 * b + 1] = ot;
-    ov += blk_counts[2 * b];
-    ot += blk_counts[2 * b + 1];
-  }
-  if (t == MC_SCAN_THREADS - 1) {
-    totals[0] = s[0][t];
-    totals[1] = s[1][t];
   }
 }
 
@@ -281,8 +209,8 @@ extern "C" int cnr_mc_count(const float* vol, int D, float level, void* workspac
   hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)L.nblk), dim3(MC_BLOCK), 0, (hipStream_t)stream, vol, D, level,
                      (uint16_t*)ws, (int*)(ws + L.off_cnt));
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, (hipStream_t)stream, (const int*)(ws + L.off_cnt),
-                     L.nblk, (int64_t*)(ws + L.off_ofs), counts_out);
+  hipLaunchKernelGGL((blocks_scan_kernel<2, int64_t, int>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream,
+                     (const int*)(ws + L.off_cnt), L.nblk, (int64_t*)(ws + L.off_ofs), counts_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }

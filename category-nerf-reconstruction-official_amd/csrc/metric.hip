@@ -15,39 +15,23 @@
 //   cnr_clip_box_*       Sutherland-Hodgman against 6 planes in registers (fp64), fan triangulation; classify, scan, emit as
 //                        csrc/mcubes.hip does, so the output is in (face, fan) order.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #include <math.h>
 
+using namespace cnr;
+
 namespace {
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
-
 // ---- nearest-neighbour distance ----------------------------------------------------------------------------------------
-constexpr int NN_BLOCK = 256;
-constexpr int NN_QPT = 8;                                 // queries per lane
-constexpr int NN_QBLK = NN_BLOCK * NN_QPT;                // queries per workgroup
-constexpr int NN_TILE = 256;                              // reference points per LDS tile (4 KB)
-constexpr int64_t NN_TARGET_WG = 2048;                    // 8 workgroups per CU on 256 CUs
-
 struct NnLayout {
   int64_t qblocks, chunks, chunk_len, bytes;
 };
 inline NnLayout nn_layout(int64_t nq, int64_t nr) {
   NnLayout L;
   L.qblocks = (nq + NN_QBLK - 1) / NN_QBLK;
-  const int64_t tiles = (nr + NN_TILE - 1) / NN_TILE;
-  int64_t want = (NN_TARGET_WG + L.qblocks - 1) / L.qblocks;
-  if (want > tiles) want = tiles;
-  if (want < 1) want = 1;
-  const int64_t tiles_per_chunk = (tiles + want - 1) / want;
-  L.chunk_len = tiles_per_chunk * NN_TILE;
-  L.chunks = (nr + L.chunk_len - 1) / L.chunk_len;
+  nn_chunks(L.qblocks, nr, &L.chunk_len, &L.chunks);
   L.bytes = align256(L.chunks * nq * 4);
   return L;
-}
-
-__device__ __forceinline__ float sq_dist(float qx, float qy, float qz, float4 p) {
-  const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
 __global__ __launch_bounds__(NN_BLOCK) void nn_partial_kernel(const float* __restrict__ q, int64_t nq,
@@ -181,7 +165,6 @@ __device__ __forceinline__ double tri_area(D3 a, D3 b, D3 c) {
 constexpr int FA_BLOCK = 256;
 constexpr int FA_ITEMS = 4;
 constexpr int FA_PER_BLOCK = FA_BLOCK * FA_ITEMS;
-constexpr int SCAN_THREADS = 1024;
 
 struct FaLayout {
   int64_t nblk, off_ofs, bytes;
@@ -192,20 +175,6 @@ inline FaLayout fa_layout(int64_t F) {
   L.off_ofs = align256(L.nblk * 8);
   L.bytes = L.off_ofs + align256(L.nblk * 8);
   return L;
-}
-
-// inclusive Hillis-Steele scan of one double per thread over the block (fixed order); returns this thread's inclusive value
-__device__ __forceinline__ double block_scan_incl(double v, double* s) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < FA_BLOCK; d <<= 1) {
-    const double a = t >= d ? s[t - d] : 0.0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  return s[t];
 }
 
 __global__ __launch_bounds__(FA_BLOCK) void fa_reduce_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -223,32 +192,8 @@ __global__ __launch_bounds__(FA_BLOCK) void fa_reduce_kernel(const float* __rest
       run += a;
     }
   }
-  const double incl = block_scan_incl(run, s);
+  const double incl = block_scan<FA_BLOCK>(run, s);
   if (threadIdx.x == FA_BLOCK - 1) blk_sum[blockIdx.x] = incl;
-}
-
-// one workgroup: exclusive offsets of the block sums (each thread a contiguous run, a block scan of the run sums, the run again)
-__global__ __launch_bounds__(SCAN_THREADS) void fa_blocks_scan_kernel(const double* __restrict__ blk_sum, int64_t nblk,
-                                                                      double* __restrict__ ofs) {
-  __shared__ double s[SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t b0 = t * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-  double run = 0.0;
-  for (int64_t b = b0; b < b1; ++b) run += blk_sum[b];
-  s[t] = run;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    const double a = t >= d ? s[t - d] : 0.0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  double o = t > 0 ? s[t - 1] : 0.0;
-  for (int64_t b = b0; b < b1; ++b) {
-    ofs[b] = o;
-    o += blk_sum[b];
-  }
 }
 
 __global__ __launch_bounds__(FA_BLOCK) void fa_scan_kernel(const double* __restrict__ area, int64_t F,
@@ -261,7 +206,7 @@ __global__ __launch_bounds__(FA_BLOCK) void fa_scan_kernel(const double* __restr
     a[k] = f0 + k < F ? area[f0 + k] : 0.0;
     run += a[k];
   }
-  block_scan_incl(run, s);
+  block_scan<FA_BLOCK>(run, s);
   double base = threadIdx.x > 0 ? s[threadIdx.x - 1] : 0.0;
   const double o = ofs[blockIdx.x];
 #pragma unroll
@@ -349,20 +294,6 @@ __device__ int clip_face(const float* __restrict__ verts, const int* __restrict_
   return n >= 3 ? n : 0;
 }
 
-// exclusive prefix over the lanes below this one, and the wave total, of a per-lane count in [0, 16)
-__device__ __forceinline__ int wave_prefix4(int c, int* total) {
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const uint64_t m = __ballot((c >> b) & 1);
-    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    pre += below << b;
-    tot += __popcll(m) << b;
-  }
-  *total = tot;
-  return pre;
-}
-
 __global__ __launch_bounds__(CL_BLOCK) void clip_count_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
                                                               int64_t F, const double* __restrict__ planes,
                                                               int* __restrict__ blk_counts) {
@@ -374,40 +305,10 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_count_kernel(const float* __res
     const int n = clip_face(verts, faces, f, planes, P);
     nt = n ? n - 2 : 0;
   }
-  int wt;
-  wave_prefix4(nt, &wt);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = wt;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int a = 0;
-#pragma unroll
-    for (int w = 0; w < CL_WAVES; ++w) a += s_w[w];
-    blk_counts[blockIdx.x] = a;
-  }
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void clip_scan_kernel(const int* __restrict__ blk_counts, int64_t nblk,
-                                                                 int64_t* __restrict__ ofs, int64_t* __restrict__ total) {
-  __shared__ int64_t s[SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t b0 = t * per, b1 = b0 + per < nblk ? b0 + per : nblk;
-  int64_t run = 0;
-  for (int64_t b = b0; b < b1; ++b) run += blk_counts[b];
-  s[t] = run;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    const int64_t a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int64_t o = s[t] - run;
-  for (int64_t b = b0; b < b1; ++b) {
-    ofs[b] = o;
-    o += blk_counts[b];
-  }
-  if (t == SCAN_THREADS - 1) *total = s[t];
+  int wt, total;
+  wave_prefix_bits<4>(nt, &wt);
+  block_prefix_waves<CL_WAVES>(0, wt, s_w, &total);
+  if (threadIdx.x == 0) blk_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void clip_emit_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
@@ -419,16 +320,10 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_emit_kernel(const float* __rest
   int n = 0;
   if (f < F) n = clip_face(verts, faces, f, planes, P);
   const int nt = n ? n - 2 : 0;
-  int wt;
-  const int pre = wave_prefix4(nt, &wt);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_w[wave] = wt;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < CL_WAVES; ++w) base += w < wave ? s_w[w] : 0;
+  int wt, total;
+  const int pre = block_prefix_waves<CL_WAVES>(wave_prefix_bits<4>(nt, &wt), wt, s_w, &total);
   if (!nt) return;
-  float* o = tris + (ofs[blockIdx.x] + base + pre) * 9;
+  float* o = tris + (ofs[blockIdx.x] + pre) * 9;
   for (int k = 0; k < nt; ++k) {
     const D3 c[3] = {P[0], P[k + 1], P[k + 2]};
 #pragma unroll
@@ -438,11 +333,6 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_emit_kernel(const float* __rest
       o[9 * k + 3 * v + 2] = (float)c[v].z;
     }
   }
-}
-
-inline unsigned grid_of(int64_t n, int64_t cap) {
-  const int64_t b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 }  // namespace
 
@@ -460,7 +350,7 @@ extern "C" int cnr_nn_dist(const float* q, int64_t nq, const float* p, int64_t n
   hipLaunchKernelGGL(nn_partial_kernel, dim3((unsigned)L.qblocks, (unsigned)L.chunks), dim3(NN_BLOCK), 0, (hipStream_t)stream, q,
                      nq, p, nr, L.chunk_len, (float*)workspace);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(nn_finish_kernel, dim3(grid_of(nq, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nq,
+  hipLaunchKernelGGL(nn_finish_kernel, dim3(grid_of(nq, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nq,
                      L.chunks, dist_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -501,8 +391,8 @@ extern "C" int cnr_face_area_scan(const float* verts, const int* faces, int64_t 
   hipLaunchKernelGGL(fa_reduce_kernel, dim3((unsigned)L.nblk), dim3(FA_BLOCK), 0, (hipStream_t)stream, verts, faces, F, area,
                      (double*)ws);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fa_blocks_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const double*)ws, L.nblk,
-                     (double*)(ws + L.off_ofs));
+  hipLaunchKernelGGL((blocks_scan_kernel<1, double, double>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream,
+                     (const double*)ws, L.nblk, (double*)(ws + L.off_ofs), (double*)nullptr);
   CNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(fa_scan_kernel, dim3((unsigned)L.nblk), dim3(FA_BLOCK), 0, (hipStream_t)stream, (const double*)area, F,
                      (const double*)(ws + L.off_ofs), cum);
@@ -515,7 +405,7 @@ extern "C" int cnr_sample_surface(const float* verts, const int* faces, int64_t 
   if (!verts || !cum || !u || !out) return CNR_E_ARG;
   if (F < 1 || n < 0) return CNR_E_SHAPE;
   if (n == 0) return CNR_OK;
-  hipLaunchKernelGGL(sample_kernel, dim3(grid_of(n, 4096)), dim3(256), 0, (hipStream_t)stream, verts, faces, F, cum, u, n, out);
+  hipLaunchKernelGGL(sample_kernel, dim3(grid_of(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, verts, faces, F, cum, u, n, out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }
@@ -535,7 +425,7 @@ extern "C" int cnr_clip_box_count(const float* verts, const int* faces, int64_t 
   hipLaunchKernelGGL(clip_count_kernel, dim3((unsigned)L.nblk), dim3(CL_BLOCK), 0, (hipStream_t)stream, verts, faces, F, planes,
                      (int*)ws);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(clip_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
+  hipLaunchKernelGGL((blocks_scan_kernel<1, int64_t, int>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
                      (int64_t*)(ws + L.off_ofs), count_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;

@@ -15,16 +15,16 @@
 //   cnr_icp_update                per candidate: Horn's quaternion (largest eigenvector of a symmetric 4x4 by cyclic Jacobi) =
 //                                 the proper rotation maximising tr(R H), which is V diag(1,1,det(V U^T)) U^T of H = U S V^T.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #include <math.h>
 
-namespace {
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+using namespace cnr;
 
+namespace {
 constexpr int PC_BLOCK = 256;
 constexpr int PC_ITEMS = 4;
 constexpr int PC_PER_BLOCK = PC_BLOCK * PC_ITEMS;
-constexpr int SCAN_THREADS = 1024;
 constexpr float DEPTH_TRUNC = 8.0f;                       // unproject_colored_pointcloud's depth_trunc
 
 // compaction workspace: per-block counts (int), then their exclusive offsets (int64)
@@ -37,46 +37,6 @@ inline CompactLayout compact_layout(int64_t n) {
   L.off_ofs = align256(L.nblk * 4);
   L.bytes = L.off_ofs + align256(L.nblk * 8);
   return L;
-}
-
-// exclusive prefix of one small count per thread over the block (Hillis-Steele in LDS, fixed order); *total = the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* s, int* total) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < PC_BLOCK; d <<= 1) {
-    const int a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  *total = s[PC_BLOCK - 1];
-  return s[t] - v;
-}
-
-// one workgroup: exclusive offsets of the per-block counts and their total
-__global__ __launch_bounds__(SCAN_THREADS) void blocks_scan_kernel(const int* __restrict__ blk_counts, int64_t nblk,
-                                                                   int64_t* __restrict__ ofs, int64_t* __restrict__ total) {
-  __shared__ int64_t s[SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t b0 = t * per < nblk ? t * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-  int64_t run = 0;
-  for (int64_t b = b0; b < b1; ++b) run += blk_counts[b];
-  s[t] = run;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    const int64_t a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int64_t o = s[t] - run;
-  for (int64_t b = b0; b < b1; ++b) {
-    ofs[b] = o;
-    o += blk_counts[b];
-  }
-  if (t == SCAN_THREADS - 1) *total = s[t];
 }
 
 // ---- unprojection ------------------------------------------------------------------------------------------------------
@@ -96,7 +56,7 @@ __global__ __launch_bounds__(PC_BLOCK) void unproject_count_kernel(const float* 
   for (int k = 0; k < PC_ITEMS; ++k)
     if (i0 + k < npix && pixel_kept(depth, obj_mask, i0 + k, inst_id)) ++c;
   int total;
-  block_excl_scan(c, s, &total);
+  block_excl_scan<PC_BLOCK>(c, s, &total);
   if (threadIdx.x == 0) blk_counts[blockIdx.x] = total;
 }
 
@@ -116,7 +76,7 @@ __global__ __launch_bounds__(PC_BLOCK) void unproject_emit_kernel(const float* _
     c += keep[k] ? 1 : 0;
   }
   int total;
-  int64_t o = ofs[blockIdx.x] + block_excl_scan(c, s, &total);
+  int64_t o = ofs[blockIdx.x] + block_excl_scan<PC_BLOCK>(c, s, &total);
 #pragma unroll
   for (int k = 0; k < PC_ITEMS; ++k) {
     if (!keep[k]) continue;
@@ -135,7 +95,6 @@ __global__ __launch_bounds__(PC_BLOCK) void unproject_emit_kernel(const float* _
 
 // ---- voxel down-sample -------------------------------------------------------------------------------------------------
 constexpr int MIN_BLOCKS = 256;
-constexpr int VOXEL_AXIS_BITS = 21;
 
 __device__ __forceinline__ void block_min3(float* sx, float* sy, float* sz) {
   const int t = threadIdx.x;
@@ -179,13 +138,13 @@ static_assert(MIN_BLOCKS == PC_BLOCK, "min_final_kernel reads one partial per th
 
 __global__ __launch_bounds__(PC_BLOCK) void voxel_keys_kernel(const float* __restrict__ p, int64_t n, const float* __restrict__ mn,
                                                               double voxel, int64_t* __restrict__ keys) {
-  const double lim = (double)(1 << VOXEL_AXIS_BITS);
+  const double lim = (double)(1 << AXIS_BITS);
   const double m0 = (double)mn[0] - voxel * 0.5, m1 = (double)mn[1] - voxel * 0.5, m2 = (double)mn[2] - voxel * 0.5;
   for (int64_t i = (int64_t)blockIdx.x * PC_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * PC_BLOCK) {
     const double a = floor(((double)p[3 * i] - m0) / voxel), b = floor(((double)p[3 * i + 1] - m1) / voxel),
                  c = floor(((double)p[3 * i + 2] - m2) / voxel);
     const bool ok = a >= 0.0 && a < lim && b >= 0.0 && b < lim && c >= 0.0 && c < lim;   // false for NaN too
-    keys[i] = ok ? ((int64_t)a << (2 * VOXEL_AXIS_BITS)) | ((int64_t)b << VOXEL_AXIS_BITS) | (int64_t)c : (int64_t)-1;
+    keys[i] = ok ? ((int64_t)a << (2 * AXIS_BITS)) | ((int64_t)b << AXIS_BITS) | (int64_t)c : (int64_t)-1;
   }
 }
 
@@ -200,7 +159,7 @@ __global__ __launch_bounds__(PC_BLOCK) void segments_count_kernel(const int64_t*
   for (int k = 0; k < PC_ITEMS; ++k)
     if (i0 + k < n && run_head(keys, i0 + k)) ++c;
   int total;
-  block_excl_scan(c, s, &total);
+  block_excl_scan<PC_BLOCK>(c, s, &total);
   if (threadIdx.x == 0) blk_counts[blockIdx.x] = total;
 }
 
@@ -220,7 +179,7 @@ __global__ __launch_bounds__(PC_BLOCK) void segments_emit_kernel(const int64_t* 
     c += head[k] ? 1 : 0;
   }
   int total;
-  int64_t o = ofs[blockIdx.x] + block_excl_scan(c, s, &total);
+  int64_t o = ofs[blockIdx.x] + block_excl_scan<PC_BLOCK>(c, s, &total);
   for (int k = 0; k < PC_ITEMS; ++k) {
     if (!head[k]) continue;
     const int64_t key = keys[i0 + k];
@@ -254,11 +213,6 @@ __global__ __launch_bounds__(PC_BLOCK) void segments_emit_kernel(const int64_t* 
 }
 
 // ---- nearest neighbour with its index, batched over candidate transforms -----------------------------------------------
-constexpr int NN_BLOCK = 256;
-constexpr int NN_QPT = 8;                                 // queries per lane
-constexpr int NN_QBLK = NN_BLOCK * NN_QPT;                // queries per workgroup
-constexpr int NN_TILE = 256;                              // target points per LDS tile (4 KB)
-constexpr int64_t NN_TARGET_WG = 2048;                    // 8 workgroups per CU on 256 CUs
 constexpr int ICP_RB = 64;                                // workgroups per candidate in the reduction
 constexpr int ICP_NSUM = 17;                              // pairs, sum d^2, sum a (3), sum b (3), sum a b^T (9)
 constexpr int ICP_NSTATE = 4;                             // fitness, rmse, flag (0 = running), iterations
@@ -269,22 +223,11 @@ struct NniLayout {
 inline NniLayout nni_layout(int64_t nq, int64_t nr, int64_t B) {
   NniLayout L;
   L.qblocks = (nq + NN_QBLK - 1) / NN_QBLK;
-  const int64_t tiles = (nr + NN_TILE - 1) / NN_TILE;
-  int64_t want = (NN_TARGET_WG + L.qblocks * B - 1) / (L.qblocks * B);
-  if (want > tiles) want = tiles;
-  if (want < 1) want = 1;
-  const int64_t tiles_per_chunk = (tiles + want - 1) / want;
-  L.chunk_len = tiles_per_chunk * NN_TILE;
-  L.chunks = (nr + L.chunk_len - 1) / L.chunk_len;
+  nn_chunks(L.qblocks * B, nr, &L.chunk_len, &L.chunks);
   L.off_idx = align256(L.chunks * B * nq * 4);
   L.off_red = L.off_idx + align256(L.chunks * B * nq * 4);
   L.bytes = L.off_red + align256(B * ICP_RB * ICP_NSUM * 8);
   return L;
-}
-
-__device__ __forceinline__ float sq_dist(float qx, float qy, float qz, float4 p) {
-  const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
 // row r of T (4,4 row-major, fp64) applied to the fp32 point, rounded once; explicit fmas so that every kernel that
@@ -559,11 +502,6 @@ __global__ __launch_bounds__(64) void icp_update_kernel(const double* __restrict
   st[3] += 1.0;
   if (st[3] >= (double)max_iter) st[2] = 3.0;
 }
-
-inline unsigned grid_of(int64_t n, int64_t cap) {
-  const int64_t b = (n + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
 }  // namespace
 
 // ---- entry points ------------------------------------------------------------------------------------------------------
@@ -583,7 +521,7 @@ extern "C" int cnr_unproject_count(const float* depth, const int* obj_mask, int 
   hipLaunchKernelGGL(unproject_count_kernel, dim3((unsigned)L.nblk), dim3(PC_BLOCK), 0, (hipStream_t)stream, depth, obj_mask, npix,
                      inst_id, (int*)ws);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(blocks_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
+  hipLaunchKernelGGL((blocks_scan_kernel<1, int64_t, int>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
                      (int64_t*)(ws + L.off_ofs), count_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -622,7 +560,7 @@ extern "C" int cnr_points_min(const float* points, int64_t n, void* workspace, f
 extern "C" int cnr_voxel_keys(const float* points, int64_t n, const float* min_xyz, double voxel, int64_t* keys, void* stream) {
   if (!points || !min_xyz || !keys) return CNR_E_ARG;
   if (n < 1 || !(voxel > 0.0)) return CNR_E_SHAPE;
-  hipLaunchKernelGGL(voxel_keys_kernel, dim3(grid_of(n, 4096)), dim3(PC_BLOCK), 0, (hipStream_t)stream, points, n, min_xyz, voxel,
+  hipLaunchKernelGGL(voxel_keys_kernel, dim3(grid_of(n, PC_BLOCK, 4096)), dim3(PC_BLOCK), 0, (hipStream_t)stream, points, n, min_xyz, voxel,
                      keys);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -641,7 +579,7 @@ extern "C" int cnr_voxel_segments_count(const int64_t* sorted_keys, int64_t n, v
   char* ws = (char*)workspace;
   hipLaunchKernelGGL(segments_count_kernel, dim3((unsigned)L.nblk), dim3(PC_BLOCK), 0, (hipStream_t)stream, sorted_keys, n, (int*)ws);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(blocks_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
+  hipLaunchKernelGGL((blocks_scan_kernel<1, int64_t, int>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, L.nblk,
                      (int64_t*)(ws + L.off_ofs), count_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -684,7 +622,7 @@ extern "C" int cnr_nn_index(const float* q, int64_t nq, const float* p, int64_t 
   hipLaunchKernelGGL(nni_partial_kernel, dim3((unsigned)L.qblocks, (unsigned)L.chunks, 1), dim3(NN_BLOCK), 0, (hipStream_t)stream, q,
                      nq, p, nr, L.chunk_len, (const double*)nullptr, (const double*)nullptr, (float*)ws, (int*)(ws + L.off_idx));
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(nni_finish_kernel, dim3(grid_of(nq, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
+  hipLaunchKernelGGL(nni_finish_kernel, dim3(grid_of(nq, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
                      (const int*)(ws + L.off_idx), nq, L.chunks, dist_out, index_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;

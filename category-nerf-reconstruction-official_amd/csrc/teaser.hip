@@ -15,12 +15,13 @@
 // was cut short the size is a lower bound, and if the second pass cannot re-find it in its budget the greedy clique of the
 // first pass (deterministic) is returned.  Either way exact = 0.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #include <limits.h>
 
-namespace {
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+using cnr::align256;
 
+namespace {
 constexpr int TG_BLOCK = 256;                 // 4 waves
 constexpr int TG_WAVES = TG_BLOCK / 64;
 constexpr int CLIQUE_MAX_N = CNR_TEASER_MAX_N;

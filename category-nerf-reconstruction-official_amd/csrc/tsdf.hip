@@ -15,29 +15,23 @@
 // No float atomics; the only atomic is the integer OR of an error flag.  Every fp64 product and sum is rounded on its own
 // (no contraction in this file), so a numpy restatement reproduces every bit.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #include <math.h>
 
 #pragma clang fp contract(off)
 
-namespace {
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+using namespace cnr;
 
+namespace {
 constexpr int TS_BLOCK = 256;
 constexpr int UNIT_RES = 16;                              // ScalableTSDFVolume's volume_unit_resolution
 constexpr int UNIT_VOX = UNIT_RES * UNIT_RES * UNIT_RES;
 constexpr int VOX_PER_LANE = UNIT_VOX / TS_BLOCK;
 constexpr int TOUCH_STRIDE = 4;                           // depth_sampling_stride
 constexpr int TOUCH_SLOTS = 8;
-constexpr int AXIS_BITS = 21;
-constexpr int64_t AXIS_BIAS = (int64_t)1 << (AXIS_BITS - 1);
-constexpr int64_t AXIS_MASK = ((int64_t)1 << AXIS_BITS) - 1;
-constexpr int SCAN_THREADS = 1024;
 static_assert(VOX_PER_LANE == UNIT_RES, "a lane of the integration holds one row of voxels along x");
 
-__device__ __forceinline__ int64_t pack_key(int64_t ix, int64_t iy, int64_t iz) {
-  return ((ix + AXIS_BIAS) << (2 * AXIS_BITS)) | ((iy + AXIS_BIAS) << AXIS_BITS) | (iz + AXIS_BIAS);
-}
 __device__ __forceinline__ double key_axis(int64_t key, int a) {
   return (double)(((key >> ((2 - a) * AXIS_BITS)) & AXIS_MASK) - AXIS_BIAS);
 }
@@ -177,46 +171,6 @@ inline ExtractLayout extract_layout(int64_t U) {
   return L;
 }
 
-// exclusive prefix of one small count per thread over the block (Hillis-Steele in LDS, fixed order); *total = the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* s, int* total) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < TS_BLOCK; d <<= 1) {
-    const int a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  *total = s[TS_BLOCK - 1];
-  return s[t] - v;
-}
-
-// one workgroup: exclusive offsets of the per-block counts and their total, for any number of blocks (csrc/pointcloud.hip's)
-__global__ __launch_bounds__(SCAN_THREADS) void blocks_scan_kernel(const int* __restrict__ blk_counts, int64_t nblk,
-                                                                   int64_t* __restrict__ ofs, int64_t* __restrict__ total) {
-  __shared__ int64_t s[SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int64_t per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-  const int64_t b0 = t * per < nblk ? t * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-  int64_t run = 0;
-  for (int64_t b = b0; b < b1; ++b) run += blk_counts[b];
-  s[t] = run;
-  __syncthreads();
-  for (int d = 1; d < SCAN_THREADS; d <<= 1) {
-    const int64_t a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int64_t o = s[t] - run;
-  for (int64_t b = b0; b < b1; ++b) {
-    ofs[b] = o;
-    o += blk_counts[b];
-  }
-  if (t == SCAN_THREADS - 1) *total = s[t];
-}
-
 __device__ __forceinline__ bool voxel_valid(float f, float w) { return w != 0.0f && f < 0.98f && f >= -0.98f; }
 
 // Lane t walks the voxels t 16 .. t 16 + 15 (ix = t >> 4, iy = t & 15, iz the walk), so lane order is voxel order.  (Lanes are 64 B
@@ -285,7 +239,7 @@ __global__ __launch_bounds__(TS_BLOCK) void extract_count_kernel(const float* __
   __shared__ int s[TS_BLOCK];
   const int c = extract_walk<false>(nullptr, tsdf, weight, nullptr, nb, U, 0.0, 0, nullptr, nullptr);
   int total;
-  block_excl_scan(c, s, &total);
+  block_excl_scan<TS_BLOCK>(c, s, &total);
   if (threadIdx.x == 0) blk_counts[blockIdx.x] = total;
 }
 
@@ -297,7 +251,7 @@ __global__ __launch_bounds__(TS_BLOCK) void extract_emit_kernel(const int64_t* _
   __shared__ int s[TS_BLOCK];
   const int c = extract_walk<false>(nullptr, tsdf, weight, nullptr, nb, U, 0.0, 0, nullptr, nullptr);
   int total;
-  const int64_t o = ofs[blockIdx.x] + block_excl_scan(c, s, &total);
+  const int64_t o = ofs[blockIdx.x] + block_excl_scan<TS_BLOCK>(c, s, &total);
   extract_walk<true>(units, tsdf, weight, colors, nb, U, voxel, o, out_p, out_c);
 }
 
@@ -311,16 +265,6 @@ __global__ __launch_bounds__(TS_BLOCK) void cell_keys_kernel(const float* __rest
     if (!ok) atomicOr(err, 1);
     keys[i] = ok ? pack_key((int64_t)a, (int64_t)b, (int64_t)c) : (int64_t)-1;
   }
-}
-
-// first index in the ascending cells[0 .. C) whose value is >= key
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ cells, int64_t C, int64_t key) {
-  int64_t lo = 0, hi = C;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (cells[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // Lane j takes the j-th point in cell order (neighbours in the wave share cells).  The three cells (X, Y, cz - 1 .. cz + 1) are
@@ -357,11 +301,6 @@ __global__ __launch_bounds__(TS_BLOCK) void radius_count_kernel(const float* __r
   }
 }
 
-inline unsigned grid_of(int64_t n, int64_t cap) {
-  const int64_t b = (n + TS_BLOCK - 1) / TS_BLOCK;
-  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 inline bool camera_ok(int W, int H, double fx, double fy) { return W >= 1 && H >= 1 && W <= 32768 && H <= 32768 && fx != 0.0 && fy != 0.0; }
 // [p - trunc, p + trunc] may not be longer than a unit's edge: a sample then touches at most two units per axis, the 8 slots
 inline bool volume_ok(double voxel, double trunc) { return voxel > 0.0 && trunc > 0.0 && 2.0 * trunc <= (double)UNIT_RES * voxel; }
@@ -372,8 +311,8 @@ extern "C" int cnr_tsdf_depth_image(const float* depth, const int* obj_mask, int
                                     double max_depth, float* out, void* stream) {
   if (!depth || !obj_mask || !out) return CNR_E_ARG;
   if (n < 1 || !(depth_scale > 0.0)) return CNR_E_SHAPE;
-  hipLaunchKernelGGL(depth_image_kernel, dim3(grid_of(n, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, depth, obj_mask, n, inst_id,
-                     depth_scale, max_depth, out);
+  hipLaunchKernelGGL(depth_image_kernel, dim3(grid_of(n, TS_BLOCK, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, depth, obj_mask, n,
+                     inst_id, depth_scale, max_depth, out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }
@@ -388,7 +327,7 @@ extern "C" int cnr_tsdf_touch(const float* depth, int W, int H, double fx, doubl
   if (!depth || !T_WC || !keys || !frames || !err) return CNR_E_ARG;
   if (!camera_ok(W, H, fx, fy) || !volume_ok(voxel, trunc) || frame < 0) return CNR_E_SHAPE;
   const int64_t ns = cnr_tsdf_touch_slots(W, H) / TOUCH_SLOTS;
-  hipLaunchKernelGGL(touch_kernel, dim3(grid_of(ns, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, depth, W, H, fx, fy, cx, cy,
+  hipLaunchKernelGGL(touch_kernel, dim3(grid_of(ns, TS_BLOCK, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, depth, W, H, fx, fy, cx, cy,
                      T_WC, (double)UNIT_RES * voxel, trunc, frame, keys, frames, err);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -420,7 +359,7 @@ extern "C" int cnr_tsdf_extract_count(const float* tsdf, const float* weight, co
   hipLaunchKernelGGL(extract_count_kernel, dim3((unsigned)U), dim3(TS_BLOCK), 0, (hipStream_t)stream, tsdf, weight, neighbours, U,
                      (int*)ws);
   CNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(blocks_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, U,
+  hipLaunchKernelGGL((blocks_scan_kernel<1, int64_t, int>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (const int*)ws, U,
                      (int64_t*)(ws + L.off_ofs), count_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
@@ -442,7 +381,8 @@ extern "C" int cnr_tsdf_extract_emit(const int64_t* units, const float* tsdf, co
 extern "C" int cnr_radius_cell_keys(const float* points, int64_t n, double radius, int64_t* keys, int* err, void* stream) {
   if (!points || !keys || !err) return CNR_E_ARG;
   if (n < 1 || !(radius > 0.0)) return CNR_E_SHAPE;
-  hipLaunchKernelGGL(cell_keys_kernel, dim3(grid_of(n, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, points, n, radius, keys, err);
+  hipLaunchKernelGGL(cell_keys_kernel, dim3(grid_of(n, TS_BLOCK, 4096)), dim3(TS_BLOCK), 0, (hipStream_t)stream, points, n, radius, keys,
+                     err);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }
@@ -451,7 +391,7 @@ extern "C" int cnr_radius_count(const float* points, int64_t n, const int64_t* p
                                 const int64_t* cells, const int64_t* starts, int64_t C, double radius, int* counts, void* stream) {
   if (!points || !perm || !sorted_keys || !cells || !starts || !counts) return CNR_E_ARG;
   if (n < 1 || C < 1 || C > n || !(radius > 0.0)) return CNR_E_SHAPE;
-  hipLaunchKernelGGL(radius_count_kernel, dim3(grid_of(n, 65536)), dim3(TS_BLOCK), 0, (hipStream_t)stream, points, n, perm,
+  hipLaunchKernelGGL(radius_count_kernel, dim3(grid_of(n, TS_BLOCK, 65536)), dim3(TS_BLOCK), 0, (hipStream_t)stream, points, n, perm,
                      sorted_keys, cells, starts, C, radius, counts);
   CNR_LAUNCH_CHECK();
   return CNR_OK;

@@ -11,6 +11,7 @@
 // composite's sums run in a fixed order.  The count and emit launches evaluate the same slab test (one device function,
 // no fused multiply-add contraction) so that they agree on every hit.
 #include "cnr_common.h"
+#include "geom_common.h"
 
 #pragma clang fp contract(off)
 
@@ -103,28 +104,14 @@ __global__ __launch_bounds__(1024) void segments_scan_kernel(const int* __restri
                                                              int64_t nw, int E, int64_t* __restrict__ offsets,
                                                              int64_t* __restrict__ entity_offset, int64_t* __restrict__ total,
                                                              int64_t* __restrict__ overflow) {
-  __shared__ long long part[1024];
+  __shared__ int64_t part[cnr::SCAN_THREADS];
   const int t = threadIdx.x;
-  const int64_t M = nw * E;
-  const int64_t per = (M + 1023) / 1024;
-  const int64_t lo = (int64_t)t * per, hi = lo + per < M ? lo + per : M;
-  long long s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  long long run = t ? part[t - 1] : 0;
-  for (int64_t i = lo; i < hi; ++i) { offsets[i] = run; run += counts[i]; }
-  if (t == 1023) { total[0] = part[1023]; if (entity_offset) entity_offset[E] = part[1023]; }
+  cnr::scan_block_counts<1>(counts, nw * E, offsets, total, part);
+  if (t == 1023 && entity_offset) entity_offset[E] = part[1023];
   __syncthreads();
   if (entity_offset) for (int e = t; e < E; e += 1024) entity_offset[e] = offsets[(int64_t)e * nw];
   if (overflow) {
-    long long ov = 0;
+    int64_t ov = 0;
     for (int64_t i = t; i < nw; i += 1024) ov += over[i];
     __syncthreads();
     part[t] = ov;

@@ -160,8 +160,7 @@ class FrameTable:
             raise TypeError("label frames are uint16 or int32, instance and class maps alike")
         self.F, self.H, self.W = F, Hs - 2 * edge, Ws - 2 * edge
         dev = inst.device
-        nbytes = int(_C.load().cnr_frame_instances_workspace_bytes(F, ID_BOUND))
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.workspace = _C.workspace(_C.load().cnr_frame_instances_workspace_bytes(F, ID_BOUND), dev, "cnr_frame_instances")
         self.offsets_dev = torch.empty(F + 1, dtype=torch.int64, device=dev)
         _C.call("cnr_frame_instances_count", inst, self.label_i32, F, self.H, self.W, edge, id_shift, ID_BOUND, self.workspace,
                 self.offsets_dev)

@@ -36,19 +36,12 @@ def _points(x, dev=None):
     return t
 
 
-def _ws(nbytes, dev, what):
-    nbytes = int(nbytes)
-    if nbytes < 0:
-        raise _C.CnrError(f"{what}: workspace query failed with {nbytes}")
-    return torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-
-
 # ---- distances ---------------------------------------------------------------------------------------------------------
 def nn_dist(query, ref):
     """-> (nq,) f32 device tensor: the distance of every query point to the nearest reference point (exact, cnr_nn_dist)"""
     q = _points(query)
     p = _points(ref, q.device)
-    ws = _ws(_C.load().cnr_nn_workspace_bytes(len(q), len(p)), q.device, "cnr_nn_dist")
+    ws = _C.workspace(_C.load().cnr_nn_workspace_bytes(len(q), len(p)), q.device, "cnr_nn_dist")
     out = torch.empty(len(q), device=q.device, dtype=torch.float32)
     _C.call("cnr_nn_dist", q, len(q), p, len(p), out, ws)
     return out
@@ -56,7 +49,7 @@ def nn_dist(query, ref):
 
 def _stats_device(dist, th):
     d = dist.contiguous()
-    ws = _ws(_C.load().cnr_dist_stats_workspace_bytes(len(d)), d.device, "cnr_dist_stats")
+    ws = _C.workspace(_C.load().cnr_dist_stats_workspace_bytes(len(d)), d.device, "cnr_dist_stats")
     s = torch.empty(1, device=d.device, dtype=torch.float64)
     c = torch.empty(1, device=d.device, dtype=torch.int64)
     _C.call("cnr_dist_stats", d, len(d), float(th), ws, s, c)
@@ -110,7 +103,7 @@ def _mesh_device(mesh, dev):
 
 def _area_scan(tri):
     verts, faces, F = tri
-    ws = _ws(_C.load().cnr_face_area_workspace_bytes(F), verts.device, "cnr_face_area_scan")
+    ws = _C.workspace(_C.load().cnr_face_area_workspace_bytes(F), verts.device, "cnr_face_area_scan")
     area = torch.empty(F, device=verts.device, dtype=torch.float64)
     cum = torch.empty(F, device=verts.device, dtype=torch.float64)
     _C.call("cnr_face_area_scan", verts, faces, F, ws, area, cum)
@@ -248,7 +241,7 @@ def _clip(tri, planes):
         return None
     dev = verts.device
     pl = torch.from_numpy(np.ascontiguousarray(planes, np.float64)).to(dev)
-    ws = _ws(_C.load().cnr_clip_box_workspace_bytes(F), dev, "cnr_clip_box")
+    ws = _C.workspace(_C.load().cnr_clip_box_workspace_bytes(F), dev, "cnr_clip_box")
     cnt = torch.empty(1, device=dev, dtype=torch.int64)
     _C.call("cnr_clip_box_count", verts, faces, F, pl, ws, cnt)
     T = int(cnt.item())

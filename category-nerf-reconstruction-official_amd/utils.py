@@ -144,14 +144,6 @@ def _cuda_device(device=None):
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _workspace(nbytes, dev, what):
-    from . import _C
-    nbytes = int(nbytes)
-    if nbytes < 0:
-        raise _C.CnrError(f"{what}: workspace query failed with {nbytes}")
-    return torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-
-
 def voxel_down_sample_device(points, colors, voxel_size):
     """open3d's voxel_down_sample on (n,3) f32 device points (colors (n,3) f32 or None): voxel index floor((p - (min - v / 2)) / v)
     per axis in fp64, the mean of each voxel's points and colours in fp64, summed in input order.
@@ -165,11 +157,11 @@ def voxel_down_sample_device(points, colors, voxel_size):
     if not voxel_size > 0:
         raise ValueError("voxel_size must be positive")
     mn = torch.empty(3, device=dev, dtype=torch.float32)
-    _C.call("cnr_points_min", points, n, _workspace(lib.cnr_points_min_workspace_bytes(n), dev, "cnr_points_min"), mn)
+    _C.call("cnr_points_min", points, n, _C.workspace(lib.cnr_points_min_workspace_bytes(n), dev, "cnr_points_min"), mn)
     keys = torch.empty(n, device=dev, dtype=torch.int64)
     _C.call("cnr_voxel_keys", points, n, mn, float(voxel_size), keys)
     skeys, perm = torch.sort(keys, stable=True)
-    ws = _workspace(lib.cnr_voxel_segments_workspace_bytes(n), dev, "cnr_voxel_segments")
+    ws = _C.workspace(lib.cnr_voxel_segments_workspace_bytes(n), dev, "cnr_voxel_segments")
     cnt = torch.empty(2, device=dev, dtype=torch.int64)
     _C.call("cnr_voxel_segments_count", skeys, n, ws, cnt[:1])
     cnt[1] = skeys[0]
@@ -277,7 +269,7 @@ def _unproject_frames(frames, inst_ids, intrinsic, dev, return_counts=False):
         W, H = d.shape
         if m.shape != (W, H) or im.shape != (W, H, 3):
             raise ValueError("depth (W,H), obj_mask (W,H) and image (W,H,3) of one frame")
-        ws = _workspace(lib.cnr_unproject_workspace_bytes(W, H), dev, "cnr_unproject")
+        ws = _C.workspace(lib.cnr_unproject_workspace_bytes(W, H), dev, "cnr_unproject")
         _C.call("cnr_unproject_count", d, m, W, H, int(inst_id), ws, counts[k:k + 1])
         T = torch.from_numpy(np.ascontiguousarray(np.asarray(T_WC, np.float64).reshape(4, 4))).to(dev)
         staged.append((d, m, im, W, H, int(inst_id), T, ws))
@@ -445,7 +437,7 @@ class TSDFVolume:
         U, dev = len(self.units), self.device
         if U == 0:
             return torch.zeros(0, 3, device=dev, dtype=torch.float64), torch.zeros(0, 3, device=dev, dtype=torch.float64)
-        ws = _workspace(_C.load().cnr_tsdf_extract_workspace_bytes(U), dev, "cnr_tsdf_extract")
+        ws = _C.workspace(_C.load().cnr_tsdf_extract_workspace_bytes(U), dev, "cnr_tsdf_extract")
         cnt = torch.zeros(1, device=dev, dtype=torch.int64)
         _C.call("cnr_tsdf_extract_count", self.tsdf, self.weight, self.neighbours, U, ws, cnt)
         n = int(cnt.item())

@@ -178,7 +178,7 @@ class SceneRenderer:
                 self._mark("start")
                 dirs = dirs_all[p0:p0 + int(chunk)]
                 P = dirs.shape[0]
-                ws = torch.empty(max(int(_C.load().cnr_view_segments_workspace_bytes(P, E)), 16), device=dev, dtype=torch.uint8)
+                ws = _C.workspace(_C.load().cnr_view_segments_workspace_bytes(P, E), dev, "cnr_view_segments")
                 ent_off = torch.empty(E + 1, device=dev, dtype=torch.int64)
                 counts = torch.empty(2, device=dev, dtype=torch.int64)
                 _C.call("cnr_view_segments_count", T, dirs, to_box, P, E, self.zmin, self.zmax, ws, ent_off, counts[0:1], counts[1:2])

@@ -266,10 +266,7 @@ def marching_cubes_raw(volume, level=0.5, ascent=True):
     if volume.dim() != 3 or tuple(volume.shape) != (D, D, D):
         raise ValueError(f"marching_cubes wants a (D,D,D) volume, got {tuple(volume.shape)}")
     vol = volume.float().contiguous()
-    nbytes = int(_C.load().cnr_mc_workspace_bytes(int(D)))
-    if nbytes < 0:
-        raise _C.CnrError(f"marching_cubes: D = {D} outside [2, 512]")
-    ws = torch.empty(nbytes, device=vol.device, dtype=torch.uint8)
+    ws = _C.workspace(_C.load().cnr_mc_workspace_bytes(int(D)), vol.device, f"marching_cubes (D = {D}, which must lie in [2, 512])")
     counts = torch.empty(2, device=vol.device, dtype=torch.int64)
     _C.call("cnr_mc_count", vol, int(D), float(level), ws, counts)
     V, F = (int(x) for x in counts.cpu())

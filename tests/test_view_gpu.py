@@ -114,6 +114,20 @@ def test_segments_and_points(cnr, dev, name):
         check(pts[:N].cpu(), torch.from_numpy(p64), torch.from_numpy(p32), f"pts S={S}")
 
 
+def test_segments_scan_with_more_counts_than_scanning_threads(cnr, dev):
+    """The scenes above have 432 pixels: 7 waves x at most 5 entities = 35 counts, one per thread of the one-workgroup scan.
+    Scene A's pose and boxes at 160 x 120 give 300 waves x 5 entities = 1500 counts, so two per scanning thread: the scan's
+    run loops, before and after its block scan.  Every integer output exact against the fp64 restatement."""
+    T, _, to_box = VS.scene_a()
+    dirs = V.pinhole_dirs(160, 120, 20 * 160 / 24, 79.5, 59.5)
+    assert dirs.shape[0] == 19200 and (dirs.shape[0] + 63) // 64 * to_box.shape[0] == 1500
+    N = 27388                                                       # of the restatement; _compare_segments asserts it
+    got = gpu_segments(cnr, dev, T, dirs, to_box, N + 5)
+    s64, _ = _compare_segments(got, T, dirs, to_box)
+    assert got["N"] == s64["N"] == N and got["overflow"] == 0
+    assert (got["pix_segs"][:, 0] >= 0).all()                       # no empty pixel
+
+
 def test_overflow_keeps_the_nearest_eight(cnr, dev):
     T, dirs, to_box = VS.scene_nested(9)
     s64 = V.segments(T.astype(np.float32), dirs, to_box.astype(np.float32), VS.ZMIN, VS.ZMAX, np.float64)

@@ -95,7 +95,7 @@ def main():
         r["extract_fpfh_call_ms"] = round(_wall_ms(lambda: CR.extract_fpfh_device(tgt, voxel), a.reps), 3)
         index = torch.empty(len(f_s), device=dev, dtype=torch.int32)
         dist = torch.empty(len(f_s), device=dev, dtype=torch.float32)
-        ws = U._workspace(_C.load().cnr_feature_nn_workspace_bytes(len(f_s), len(f_t)), dev, "cnr_feature_nn")
+        ws = _C.workspace(_C.load().cnr_feature_nn_workspace_bytes(len(f_s), len(f_t)), dev, "cnr_feature_nn")
         r["feature_nn_ms"] = round(_event_ms(lambda: _C.call("cnr_feature_nn", f_s, len(f_s), f_t, len(f_t), 33, index, dist, ws), a.reps), 4)
         r["feature_nn_pairs_per_s"] = float("%.3g" % (len(f_s) * len(f_t) / (r["feature_nn_ms"] * 1e-3)))
         i0, _ = CR.mutual_correspondences(f_s, f_t)
