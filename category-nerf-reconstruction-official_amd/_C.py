@@ -143,6 +143,15 @@ SIGNATURES = {
     "cnr_view_segments_emit": [_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "cnr_view_points": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp],
     "cnr_view_composite": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cnr_geoseg_maps": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "cnr_geoseg_edge_map": [_vp, _vp, _vp, _i, _i, _vp, _vp],
+    "cnr_ccl": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "cnr_label_counts": [_vp, _i, _i, _i, _vp, _vp],
+    "cnr_geoseg_grow": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "cnr_fill_holes_workspace_bytes": [_i, _i, _i],
+    "cnr_fill_holes": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "cnr_refine_vote": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "cnr_refine_apply": [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp],
 }
 # The three launches of the fused trainer's step take ONE versioned struct (include/cnr_hip.h: struct_size and abi_version
 # first, then these fields in this order).  call_struct() wants every field by NAME: a missing, misspelt or surplus argument
@@ -207,7 +216,7 @@ _RESTYPE64 = {"cnr_pack_bytes", "cnr_pack_lo_bytes", "cnr_field_bwd_workspace_by
               "cnr_unproject_workspace_bytes", "cnr_points_min_workspace_bytes", "cnr_voxel_segments_workspace_bytes",
               "cnr_nn_index_workspace_bytes", "cnr_icp_workspace_bytes", "cnr_clique_workspace_bytes",
               "cnr_tsdf_touch_slots", "cnr_tsdf_extract_workspace_bytes", "cnr_feature_nn_workspace_bytes",
-              "cnr_view_segments_workspace_bytes"}
+              "cnr_view_segments_workspace_bytes", "cnr_fill_holes_workspace_bytes"}
 
 _lib = None
 _double = None

@@ -7,7 +7,9 @@ arrays in the reference's (W, H) layout.  The per-instance decisions are host lo
 order and dtypes, quirks included.  The loaders read the cached registration result
 ``<dataset_dir>/inst_dict.pkl`` (``registration.load_registration_result``) with a restricted unpickler; without one,
 ``get_dataset(cfg, register=True)`` runs category registration for Replica (category_registration.py), and
-``get_dataset(cfg, register=True, tsdf=True)`` for ScanNet sequences whose refined masks are on disk."""
+``get_dataset(cfg, register=True, tsdf=True)`` for ScanNet sequences.  A ScanNet frame without a refined
+mask is refined on request, ``get_dataset(cfg, refine=True)``: geometry segmentation and the overlap vote on the device
+(utils.refine_frame, csrc/geoseg.hip), written to ``instance-refined/`` and ``inst_to_cls/`` as the reference does."""
 import glob
 import io
 import os
@@ -26,14 +28,16 @@ BATCH = 16                  # frames per upload
 DECODE_WORKERS = 16
 
 
-def get_dataset(cfg, register=False, tsdf=False):
+def get_dataset(cfg, register=False, tsdf=False, refine=False):
     """register=True: a Replica dataset without a usable cache runs category registration (category_registration.
     register_dataset) and writes <dataset_dir>/inst_dict.pkl; the default raises NotImplementedError there, as before.
-    A ScanNet dataset does so only with tsdf=True as well (its background cloud is a TSDF fusion)."""
+    A ScanNet dataset does so only with tsdf=True as well (its background cloud is a TSDF fusion).
+    refine=True: a ScanNet frame that wants a refined mask (use_refined_mask) and has none on disk gets one computed and written
+    (src/dataset.py:358-366); the default raises NotImplementedError there, as before."""
     if cfg.dataset_format == "Replica":
         return Replica(cfg, register=register)
     if cfg.dataset_format == "ScanNet":
-        return ScanNet(cfg, register=register, tsdf=tsdf)
+        return ScanNet(cfg, register=register, tsdf=tsdf, refine=refine)
     raise ValueError("Dataset format {} not found".format(cfg.dataset_format))
 
 
@@ -325,9 +329,9 @@ def _sorted_by_stem(pattern):
 
 
 class ScanNet(_Base):
-    def __init__(self, cfg, register=False, tsdf=False):
+    def __init__(self, cfg, register=False, tsdf=False, refine=False):
         self.name = "scannet"
-        self.register, self.tsdf = register, tsdf
+        self.register, self.tsdf, self.refine = register, tsdf, refine
         # the objects' clouds are gathered frame by frame (src/dataset.py:385-400) only when registration is going to run
         self._accumulate = bool(register and tsdf) and not _has_cache(cfg.dataset_dir, cfg)
         self._frame_objects = {}
@@ -366,12 +370,22 @@ class ScanNet(_Base):
     def _refined(self, index):
         inst_path = self.inst_paths[index] if len(self.inst_paths) > index else ""
         sem_path = self.sem_paths[index] if len(self.sem_paths) > index else ""
+        if self.refine and self.load_refined_mask:
+            # by name, where the computed masks are written: the reference's sorted lists pair frame k with the k-th file, which
+            # shifts every later frame when one in the middle is missing
+            stem = os.path.basename(self.raw_inst_paths[index])[:-4]
+            inst_path = os.path.join(self.root_dir, "instance-refined", stem + ".npy")
+            sem_path = os.path.join(self.root_dir, "inst_to_cls", stem + ".pkl")
         if self.load_refined_mask and os.path.exists(inst_path) and os.path.exists(sem_path):
             return inst_path, sem_path
-        if self.use_refined_mask:
+        if self.use_refined_mask and not self.refine:
             raise NotImplementedError(f"frame {index}: no refined mask; refining ScanNet's raw masks (open3d "
                                       "geometry_segmentation, src/dataset.py:359-366) is not part of this package")
         return None
+
+    def _wants_refinement(self, index):
+        """a frame read from the raw labels that gets its refined mask computed and written (refine=True)"""
+        return bool(self.use_refined_mask and self.refine) and self._refined(index) is None
 
     def _decode(self, index):
         rgb = _read_rgb(self.color_paths[index])
@@ -383,8 +397,9 @@ class ScanNet(_Base):
                 raise ValueError(f"{ref[0]}: instance ids outside [0, {ID_BOUND})")
             with open(ref[1], "rb") as f:
                 inst_to_cls = pickle.load(f)
-            return rgb, depth, inst.astype(np.int32), None, inst_to_cls
-        return rgb, depth, _read_png16(self.raw_inst_paths[index]), _read_png16(self.raw_sem_paths[index]), None
+            return rgb, depth, inst.astype(np.int32), None, inst_to_cls, False
+        return (rgb, depth, _read_png16(self.raw_inst_paths[index]), _read_png16(self.raw_sem_paths[index]), None,
+                self._wants_refinement(index))
 
     def get_all_frames(self):
         self.inst_dict, self.sample_dict = {}, {}
@@ -398,7 +413,7 @@ class ScanNet(_Base):
                 # a batch holds frames of one label kind (refined or raw) and one set of image sizes
                 frames = list(pool.map(self._decode, valid[b0:b0 + BATCH]))
                 n = 1
-                key = lambda fr: (fr[4] is None, fr[0].shape, fr[1].shape, fr[2].shape)
+                key = lambda fr: (fr[4] is None, fr[5], fr[0].shape, fr[1].shape, fr[2].shape)
                 while n < len(frames) and key(frames[n]) == key(frames[0]):
                     n += 1
                 idxs, frames = valid[b0:b0 + n], frames[:n]
@@ -412,17 +427,13 @@ class ScanNet(_Base):
         Hd, Wd = depth.shape[1:]
         if rgb.shape[1:3] != (Hd, Wd):
             rgb = resize_linear(rgb, Hd, Wd)                     # src/dataset.py:304
+        if frames[0][5]:
+            frames = self._refine_batch(idxs, frames, depth, rgb, dev, e)
         refined = frames[0][4] is not None
-        inst = _pinned([fr[2] for fr in frames]).to(dev, non_blocking=True)
         if refined:
-            table, shift, label_edge = FrameTable(inst), 0, 0
+            table, shift, label_edge = FrameTable(_pinned([fr[2] for fr in frames]).to(dev, non_blocking=True)), 0, 0
         else:
-            sem = _pinned([fr[3] for fr in frames]).to(dev, non_blocking=True)
-            if inst.shape[1:] != (Hd, Wd):
-                inst = resize_nearest(inst, Hd, Wd)              # src/dataset.py:330-332
-            if sem.shape[1:] != (Hd, Wd):
-                sem = resize_nearest(sem, Hd, Wd)
-            table, shift, label_edge = FrameTable(inst, sem, edge=e, id_shift=1), 1, e
+            table, shift, label_edge = self._raw_label_table(frames, dev, Hd, Wd, e), 1, e
         W, H = Wd - 2 * e, Hd - 2 * e
         if (table.H, table.W) != (H, W):
             raise ValueError(f"label frames are {table.H} x {table.W} after the crop, depth {H} x {W}")
@@ -437,6 +448,49 @@ class ScanNet(_Base):
             self.sample_dict[r] = {"image": img[f], "depth": dep[f], "obj_mask": obj_mask[f], "T": self.poses[index], "frame_id": r}
             if self._accumulate:
                 self._accumulate_objects(r, dev)
+
+    def _raw_label_table(self, frames, dev, Hd, Wd, e):
+        """the raw path's instance table (src/dataset.py:327-338): nearest resize to the depth's size, edge crop, ids + 1"""
+        inst = _pinned([fr[2] for fr in frames]).to(dev, non_blocking=True)
+        sem = _pinned([fr[3] for fr in frames]).to(dev, non_blocking=True)
+        if inst.shape[1:] != (Hd, Wd):
+            inst = resize_nearest(inst, Hd, Wd)                  # src/dataset.py:330-332
+        if sem.shape[1:] != (Hd, Wd):
+            sem = resize_nearest(sem, Hd, Wd)
+        return FrameTable(inst, sem, edge=e, id_shift=1)
+
+    def _refine_batch(self, idxs, frames, depth, rgb, dev, e):
+        """src/dataset.py:327-366 for frames without a refined mask: the raw instance map (background classes -> 0), geometry
+        segmentation and the vote on the frame the loader hands on (cropped, metres, max_depth), instance-refined/<n>.npy and
+        inst_to_cls/<n>.pkl written -> the frames as refined frames"""
+        from .utils import refine_frame
+        Hd, Wd = depth.shape[1:]
+        table = self._raw_label_table(frames, dev, Hd, Wd, e)
+        keep = np.zeros(len(table.ids), dtype=bool)
+        maps = []
+        for f in range(len(idxs)):
+            ids, stats = table.frame(f)
+            inst_to_cls = {0: 0}
+            for k in range(len(ids)):
+                assert stats[k, 5] == stats[k, 6]             # sem_cls.shape[0] == 1
+                sem_cls = np.uint16(stats[k, 5])
+                if sem_cls in self.background_cls_list:
+                    continue
+                keep[table.offsets[f] + k] = True
+                inst_to_cls[np.int32(ids[k])] = sem_cls
+            maps.append(inst_to_cls)
+        obj, dep, _ = table.finish(keep, depth, rgb, e, self.depth_scale, self.max_depth)       # (F,W,H): the reference's layout
+        for sub in ("instance-refined", "inst_to_cls"):
+            os.makedirs(os.path.join(self.root_dir, sub), exist_ok=True)
+        out = []
+        for f, index in enumerate(idxs):
+            refined = refine_frame(dep[f].t().contiguous(), obj[f].t().contiguous(), self.intrinsic_open3d).cpu().numpy()
+            stem = os.path.basename(self.raw_inst_paths[index])[:-4]
+            np.save(os.path.join(self.root_dir, "instance-refined", stem + ".npy"), refined)
+            with open(os.path.join(self.root_dir, "inst_to_cls", stem + ".pkl"), "wb") as fh:
+                pickle.dump(maps[f], fh)
+            out.append((frames[f][0], frames[f][1], refined, None, maps[f], False))
+        return out
 
     def _accumulate_objects(self, frame, dev):
         """src/dataset.py:385-400: every kept object's pixels of this frame, unprojected, added to its 'pcs'"""

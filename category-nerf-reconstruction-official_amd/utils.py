@@ -634,3 +634,279 @@ def get_possible_transform_from_bbox():
             transform[:3, :3] = np.vstack([x_axis, y_axis, np.cross(x_axis, y_axis)]).T
             transform_list.append(transform)
     return transform_list
+
+
+# ---- ScanNet mask refinement (src/utils.py:561-727) ----------------------------------------------------------------------
+# geometry_segmentation and refine_inst_data on the kernels of csrc/geoseg.hip; the point map and the normals
+# on those of csrc/pointcloud.hip and csrc/fpfh.hip.  The reference's cv2 contour stage is restated on connected components
+# (equality with cv2 and open3d is unverified).
+GEOSEG_NORMAL_RADIUS, GEOSEG_NORMAL_MAX_NN = 0.1, 100
+FILL_CHUNK_BYTES = 256 << 20          # what one cnr_fill_holes call's stack (masks, labels, flags) may take
+
+
+class Segment():
+    def __init__(self):
+        self.points = None
+        self.normals = None
+        self.rgbs = None
+
+
+def label_colormap(n_label=256):
+    """imgviz.label_colormap(): the PASCAL-VOC colormap, (n_label, 3) uint8 -- bit b of (id >> 3 j) becomes bit 7 - j of
+    channel b, for j = 0..7"""
+    ids = np.arange(n_label, dtype=np.int64)
+    cmap = np.zeros((n_label, 3), np.uint8)
+    for j in range(8):
+        for ch in range(3):
+            cmap[:, ch] |= ((((ids >> (3 * j)) >> ch) & 1) << (7 - j)).astype(np.uint8)
+    return cmap
+
+
+def _device_mask(mask):
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        from . import _C
+        raise _C.CnrError("a device tensor is expected; there is no CPU path")
+    return (mask != 0).to(torch.uint8).contiguous()
+
+
+def _raise_if_set(err, what):
+    if int(err.item()):
+        from . import _C
+        raise _C.CnrError(f"{what}: a union/find loop ran out of its bound (the label array is corrupt)")
+
+
+def connected_components(mask, connectivity=8, check=True):
+    """(H,W) or (F,H,W) device mask (non-zero = set) -> int32 labels of the same shape (cnr_ccl): the smallest raster index
+    v W + u, within its frame, of the pixel's 4- or 8-connected component, -1 outside the mask"""
+    from . import _C
+    m = _device_mask(mask)
+    if m.dim() not in (2, 3):
+        raise ValueError("mask (H,W) or (F,H,W)")
+    F = 1 if m.dim() == 2 else m.shape[0]
+    H, W = m.shape[-2:]
+    labels = torch.empty(m.shape, device=m.device, dtype=torch.int32)
+    if F == 0:
+        return labels
+    err = torch.zeros(1, device=m.device, dtype=torch.int32)
+    _C.call("cnr_ccl", m, F, H, W, int(connectivity), labels, err)
+    if check:
+        _raise_if_set(err, "cnr_ccl")
+    return labels
+
+
+def label_counts(labels):
+    """(H,W) or (F,H,W) int32 device labels -> int32 counts of the same shape: counts[f].ravel()[l] = pixels of frame f labelled l"""
+    from . import _C
+    labels = labels.contiguous()
+    F = 1 if labels.dim() == 2 else labels.shape[0]
+    counts = torch.empty(labels.shape, device=labels.device, dtype=torch.int32)
+    if F:
+        _C.call("cnr_label_counts", labels, F, labels.shape[-2], labels.shape[-1], counts)
+    return counts
+
+
+def _fill_holes_stack(labels, seg_ids, masks, K, H, W, dev):
+    """cnr_fill_holes in chunks over K -> (K,H,W) uint8"""
+    from . import _C
+    lib = _C.load()
+    filled = torch.empty(K, H, W, device=dev, dtype=torch.uint8)
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    chunk = max(1, min(K, 65535, FILL_CHUNK_BYTES // (6 * H * W)))
+    for k0 in range(0, K, chunk):
+        k = min(chunk, K - k0)
+        ws = _C.workspace(lib.cnr_fill_holes_workspace_bytes(k, H, W), dev, "cnr_fill_holes")
+        _C.call("cnr_fill_holes", labels, seg_ids[k0:k0 + k] if seg_ids is not None else None,
+                masks[k0:k0 + k] if masks is not None else None, k, H, W, ws, filled[k0:k0 + k], err)
+    return filled, err
+
+
+def fill_holes(mask):
+    """scipy.ndimage.binary_fill_holes (default structure) of an (H,W) or (K,H,W) device mask -> bool tensor (cnr_fill_holes)"""
+    m = _device_mask(mask)
+    if m.dim() not in (2, 3):
+        raise ValueError("mask (H,W) or (K,H,W)")
+    stack = m.reshape((-1,) + tuple(m.shape[-2:]))
+    filled, err = _fill_holes_stack(None, None, stack, stack.shape[0], m.shape[-2], m.shape[-1], m.device)
+    _raise_if_set(err, "cnr_fill_holes")
+    return filled.reshape(m.shape).bool()
+
+
+def _geoseg_point_map(depth, intrinsic):
+    """depth (H,W) f32 device -> (P (H,W,3) f32: the camera-frame point of every valid pixel, zero elsewhere; valid (H,W) bool)"""
+    H, W = depth.shape
+    dev = depth.device
+    d_t = depth.t().contiguous()                               # the unprojection kernel walks (W,H) frames, u major
+    cloud, counts = _unproject_frames([(torch.zeros(W, H, 3, dtype=torch.uint8, device=dev), d_t,
+                                        torch.ones(W, H, dtype=torch.int32, device=dev), np.eye(4))], [1], intrinsic, dev,
+                                      return_counts=True)
+    valid = depth > 0
+    if int(counts[0]) != int(valid.sum()):
+        raise ValueError("geometry_segmentation: depth values beyond 8 m (or not finite); the loaders zero them")
+    P_t = torch.zeros(W, H, 3, device=dev, dtype=torch.float32)
+    P_t[valid.t()] = cloud.points_device
+    return P_t.permute(1, 0, 2).contiguous(), valid
+
+
+def _geoseg_points_normals(depth, intrinsic):
+    """-> (P, N (H,W,3) f32: the normals of the valid pixels, estimated on them in raster order and negated where n_z > 0)"""
+    P, valid = _geoseg_point_map(depth, intrinsic)
+    N = torch.zeros(P.shape, device=P.device, dtype=torch.float32)
+    if bool(valid.any()):
+        n = estimate_normals_device(P[valid], GEOSEG_NORMAL_RADIUS, GEOSEG_NORMAL_MAX_NN)
+        n = torch.where(n[:, 2:] > 0, -n, n)                   # src/utils.py:571
+        N[valid] = n.to(torch.float32)
+    return P, N
+
+
+def geoseg_maps(P, N, depth):
+    """cnr_geoseg_maps on device tensors -> (disc, conv) (H,W) uint8"""
+    from . import _C
+    H, W = depth.shape
+    disc = torch.empty(H, W, device=depth.device, dtype=torch.uint8)
+    conv = torch.empty(H, W, device=depth.device, dtype=torch.uint8)
+    _C.call("cnr_geoseg_maps", P.contiguous(), N.contiguous(), depth.contiguous(), H, W, disc, conv)
+    return disc, conv
+
+
+def geoseg_edge_map(disc, conv, depth):
+    """cnr_geoseg_edge_map -> (H,W) uint8, 1 = region pixel"""
+    from . import _C
+    H, W = depth.shape
+    edge = torch.empty(H, W, device=depth.device, dtype=torch.uint8)
+    _C.call("cnr_geoseg_edge_map", disc.contiguous(), conv.contiguous(), depth.contiguous(), H, W, edge)
+    return edge
+
+
+def geoseg_grow(P, depth, edge, labels, counts=None, min_area=0):
+    """cnr_geoseg_grow -> the second label image (H,W) int32"""
+    from . import _C
+    H, W = depth.shape
+    out = torch.empty(H, W, device=depth.device, dtype=torch.int32)
+    _C.call("cnr_geoseg_grow", P.contiguous(), depth.contiguous(), edge.contiguous(), labels.contiguous(),
+            counts.contiguous() if counts is not None else None, int(min_area), H, W, out)
+    return out
+
+
+def _segment_frame(depth, intrinsic, min_area, min_pixels, points_normals=None):
+    """2.1 - 2.5 on one (H,W) f32 device depth frame -> dict(P, N, disc, conv, edge, labels, grown, seg_ids (K,) int32 device)"""
+    P, N = points_normals if points_normals is not None else _geoseg_points_normals(depth, intrinsic)
+    disc, conv = geoseg_maps(P, N, depth)
+    edge = geoseg_edge_map(disc, conv, depth)
+    err = torch.zeros(1, device=depth.device, dtype=torch.int32)
+    from . import _C
+    H, W = depth.shape
+    labels = torch.empty(H, W, device=depth.device, dtype=torch.int32)
+    _C.call("cnr_ccl", edge, 1, H, W, 8, labels, err)
+    grown = geoseg_grow(P, depth, edge, labels, label_counts(labels), min_area)
+    seg_ids = torch.nonzero(label_counts(grown).reshape(-1) >= int(min_pixels)).reshape(-1).to(torch.int32)
+    _raise_if_set(err, "cnr_ccl")
+    return dict(P=P, N=N, disc=disc, conv=conv, edge=edge, labels=labels, grown=grown, seg_ids=seg_ids)
+
+
+def _as_device_depth(depth, device):
+    dev = depth.device if torch.is_tensor(depth) and depth.is_cuda else _cuda_device(device)
+    d = depth if torch.is_tensor(depth) else torch.from_numpy(np.ascontiguousarray(depth, dtype=np.float32))
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    if d.dim() != 2 or d.shape[0] < 3 or d.shape[1] < 3:
+        raise ValueError("depth (H,W) with H, W >= 3")
+    return d
+
+
+def geometry_segmentation(rgb, depth, intrinsic_open3d, min_area=500, min_pixels=500, device=None, normal_image=None):
+    """src/utils.py:561-694 on the device: rgb (H,W,3) uint8, depth (H,W) f32 in metres with 0 = invalid ->
+    (normal_image (H,W,3) f32, output (H,W,3) uint8 label colouring, segment_masks [(H,W) bool], segments [Segment]).
+    Regions are the 8-connected components of the edge map with at least min_area pixels, grown onto the edge pixels; those with
+    at least min_pixels pixels are the segments, in ascending label (= first pixel in raster order).  `normal_image`: normals to
+    use in place of the estimated ones (the tests' hook)."""
+    d = _as_device_depth(depth, device)
+    dev = d.device
+    H, W = d.shape
+    rgb = np.asarray(rgb.cpu() if torch.is_tensor(rgb) else rgb)
+    if rgb.shape != (H, W, 3):
+        raise ValueError("rgb (H,W,3) of the depth's size")
+    pn = None
+    if normal_image is not None:
+        pn = (_geoseg_point_map(d, intrinsic_open3d)[0],
+              torch.from_numpy(np.ascontiguousarray(normal_image, dtype=np.float32)).to(dev))
+    s = _segment_frame(d, intrinsic_open3d, min_area, min_pixels, pn)
+    grown, seg_ids = s["grown"], s["seg_ids"]
+    K = len(seg_ids)
+    rank = torch.full((H * W + 1,), -1, device=dev, dtype=torch.int64)
+    rank[seg_ids.long()] = torch.arange(K, device=dev)
+    rank_img = rank[grown.long().clamp(min=-1)]                # -1 indexes the spare last entry, which stays -1
+    cmap = torch.from_numpy(label_colormap()).to(dev)
+    output = torch.where((rank_img >= 0)[..., None], cmap[rank_img.clamp(min=0) % 256], torch.zeros(3, dtype=torch.uint8, device=dev))
+    rank_np, P_np, N_np = rank_img.cpu().numpy(), s["P"].cpu().numpy(), s["N"].cpu().numpy()
+    segment_masks, segments = [], []
+    for k in range(K):
+        m = rank_np == k
+        seg = Segment()
+        seg.points, seg.normals, seg.rgbs = P_np[m], N_np[m], rgb[m]
+        segment_masks.append(m)
+        segments.append(seg)
+    return N_np, output.cpu().numpy(), segment_masks, segments
+
+
+def _vote(inst, filled, threshold):
+    """inst (H,W) int32 device, filled (K,H,W) uint8 device -> refined (H,W) int32 device (cnr_refine_vote, cnr_refine_apply)"""
+    from . import _C
+    H, W = inst.shape
+    dev, K = inst.device, filled.shape[0]
+    ids = torch.unique(inst)
+    ids = ids[(ids != 0) & (ids != -1)].to(torch.int32).contiguous()
+    O = len(ids)
+    refined = torch.zeros(H, W, device=dev, dtype=torch.int32)
+    if O == 0 or K == 0:
+        return refined                                         # "this frame has no foreground objects"
+    counts = torch.empty(K, O + 1, device=dev, dtype=torch.int32)
+    chosen = torch.empty(K, device=dev, dtype=torch.int32)
+    _C.call("cnr_refine_vote", filled, inst, ids, K, O, H, W, counts)
+    _C.call("cnr_refine_apply", filled, counts, ids, K, O, H, W, float(threshold), chosen, refined)
+    return refined
+
+
+def _inst_to_device(inst_data, dev):
+    inst = inst_data if torch.is_tensor(inst_data) else torch.from_numpy(np.ascontiguousarray(inst_data))
+    if inst.dim() != 2 or inst.dtype.is_floating_point:
+        raise ValueError("inst_data: an (H,W) integer array")
+    wide = inst.to(torch.int64)
+    if inst.numel() and (int(wide.min()) < -(1 << 31) or int(wide.max()) >= (1 << 31)):
+        raise ValueError("inst_data: ids outside int32")
+    return wide.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def refine_inst_data(inst_data, segment_masks, threshold=0.7, device=None):
+    """src/utils.py:696-721 on the device: every segment mask with its holes filled votes for the object id (the distinct values
+    of inst_data without 0 and -1) that covers the largest share of it; a share > threshold assigns the id to the filled mask,
+    later segments over earlier ones -> (H,W) array of inst_data's dtype"""
+    dev = inst_data.device if torch.is_tensor(inst_data) and inst_data.is_cuda else _cuda_device(device)
+    inst = _inst_to_device(inst_data, dev)
+    H, W = inst.shape
+    out_dtype = inst_data.dtype
+    K = len(segment_masks)
+    if K:
+        masks = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(m) != 0 for m in segment_masks]), dtype=np.uint8)).to(dev)
+        if masks.shape[1:] != (H, W):
+            raise ValueError("segment masks of inst_data's size")
+        filled, err = _fill_holes_stack(None, None, masks, K, H, W, dev)
+        refined = _vote(inst, filled, threshold)
+        _raise_if_set(err, "cnr_fill_holes")
+    else:
+        refined = torch.zeros(H, W, device=dev, dtype=torch.int32)
+    if torch.is_tensor(inst_data):
+        return refined.to(out_dtype)
+    return refined.cpu().numpy().astype(out_dtype)
+
+
+def refine_frame(depth, inst, intrinsic, min_area=500, min_pixels=500, threshold=0.7):
+    """geometry_segmentation and refine_inst_data of one frame without leaving the device (the loaders' path): depth (H,W) f32,
+    inst (H,W) int32 device tensors -> refined (H,W) int32 device tensor"""
+    s = _segment_frame(depth, intrinsic, min_area, min_pixels)
+    K = len(s["seg_ids"])
+    H, W = depth.shape
+    if K == 0:
+        return torch.zeros(H, W, device=depth.device, dtype=torch.int32)
+    filled, err = _fill_holes_stack(s["grown"], s["seg_ids"].contiguous(), None, K, H, W, depth.device)
+    refined = _vote(inst.contiguous(), filled, threshold)
+    _raise_if_set(err, "cnr_fill_holes")
+    return refined

@@ -1020,6 +1020,56 @@ int cnr_view_composite(const float* sigma, const float* color, const float* z, c
                        const int* entity_inst, int64_t P, int S, float opacity_threshold, float* rgb, float* depth,
                        float* opacity, float* var, float* mass, int* instance, void* stream);
 
+/* ---- ScanNet mask refinement (src/utils.py: geometry_segmentation, refine_inst_data).  The contracts
+ * above hold: caller-allocated outputs, an explicit stream, argument errors as return codes before the device is touched, no
+ * host sync, no float atomics, every loop bounded, results identical run to run.  Every fp32 product, sum, quotient and square
+ * root is rounded on its own.  Images are (H,W) row-major, pixel (v,u) at v W + u; H W < 2^31 - 1 (else CNR_E_SHAPE).
+ * Equality with cv2 is unverified (DESIGN.md says which stages are pinned to what).
+ *
+ * cnr_geoseg_maps: P (H,W,3) f32 the camera-frame point map (zero at invalid pixels), N (H,W,3) f32 the normals, depth (H,W) f32
+ * with 0 = invalid -> disc, conv (H,W) u8.  ero / dil = min / max of depth over the 3x3 window, pixels outside the image
+ * ignored, zeros taking part as zeros; ratio = max(depth - ero, dil - depth) / depth where depth > 0, else 0; disc = ratio >
+ * 0.01f.  conv: over the 24 offsets of the 5x5 window without its centre, neighbour indices reflected without repeating the
+ * edge (-1 -> 1, H -> H - 2): d = P[n] - P[c], dot = ((d_x (-N_x) + d_y (-N_y)) + d_z (-N_z)) with N at the centre, proj =
+ * ((N_x N'_x + N_y N'_y) + N_z N'_z) with N' at the neighbour, term = 1 if dot > -0.0005f else proj; conv = (min of the terms
+ * and 10) > 0.9f.  H, W >= 3 (else CNR_E_SHAPE). */
+int cnr_geoseg_maps(const float* P, const float* N, const float* depth, int H, int W, uint8_t* disc, uint8_t* conv, void* stream);
+/* edge (H,W) u8 = open3(conv) & ~close3(disc) & (depth > 0): open3 = dilate(erode(.)), close3 = erode(dilate(.)), 3x3, pixels
+ * outside the image ignored in each pass.  1 marks a region pixel (the reference's edge_map_uint8). */
+int cnr_geoseg_edge_map(const uint8_t* disc, const uint8_t* conv, const float* depth, int H, int W, uint8_t* edge, void* stream);
+/* Connected components of F stacked masks (F,H,W) u8 (non-zero = set), connectivity 4 or 8 (else CNR_E_SHAPE), 1 <= F <= 65535:
+ * labels (F,H,W) i32 = the smallest raster index v W + u, within its frame, among the pixels of the pixel's component; -1 where
+ * the mask is 0.  Tile-local labelling in LDS, unions across the tile borders, then flattening, all on the device; the result is
+ * defined by the mask alone.  Every union/find loop is bounded by H W steps; one that runs out sets err (1,) i32, which the
+ * caller zeroes beforehand and reads when it next synchronises (it never happens on a valid label array).
+ * cnr_label_counts: counts (F,H,W) i32, counts[f][l] = the pixels of frame f with label l (labels outside [0, H W) are skipped). */
+int cnr_ccl(const uint8_t* mask, int F, int H, int W, int connectivity, int* labels, int* err, void* stream);
+int cnr_label_counts(const int* labels, int F, int H, int W, int* counts, void* stream);
+/* The 9x9 label growth.  labels (H,W) i32 of cnr_ccl on edge; with counts (H,W) i32 (may be NULL) a label with counts[label] <
+ * min_area counts as -1.  labels_out = that label where edge != 0.  An edge pixel (edge == 0 and depth > 0) walks the offsets i
+ * = -4..4 in x (outer loop) and j = -4..4 in y (inner loop) without (0,0); a neighbour qualifies when it lies inside the image,
+ * has edge != 0 and a label >= 0; its distance is sqrtf((dx dx + dy dy) + dz dz) of the two rows of P; the pixel takes the label
+ * of the neighbour with the smallest distance < 0.05f, the first in loop order among equals, else -1.  depth == 0: -1. */
+int cnr_geoseg_grow(const float* P, const float* depth, const uint8_t* edge, const int* labels, const int* counts, int min_area,
+                    int H, int W, int* labels_out, void* stream);
+/* scipy's binary_fill_holes (default structure) of K masks: filled (K,H,W) u8 = the mask plus every pixel outside it whose
+ * 4-connected component of the complement does not touch the image border.  The masks are either labels (H,W) i32 == seg_ids[k]
+ * (seg_ids (K,) i32; masks NULL) or masks (K,H,W) u8 (labels and seg_ids NULL): exactly one of the two, else CNR_E_ARG.
+ * 0 <= K <= 65535 (else CNR_E_SHAPE; K = 0 does nothing); workspace >= cnr_fill_holes_workspace_bytes(K, H, W); err as for
+ * cnr_ccl. */
+int64_t cnr_fill_holes_workspace_bytes(int K, int H, int W);
+int cnr_fill_holes(const int* labels, const int* seg_ids, const uint8_t* masks, int K, int H, int W, void* workspace,
+                   uint8_t* filled, int* err, void* stream);
+/* The overlap vote.  inst (H,W) i32 the raw instance map, obj_ids (O,) i32 ascending and distinct, 0 <= O <= 2048 (else
+ * CNR_E_SHAPE).  cnr_refine_vote: counts (K, O + 1) i32, [k][o] = |filled_k & inst == obj_ids[o]|, [k][O] = |filled_k|.
+ * cnr_refine_apply: chosen (K,) i32 = the first o that attains the largest fp64 quotient counts[k][o] / counts[k][O] when that
+ * quotient is > threshold, else -1 (also for an empty mask); refined (H,W) i32 = obj_ids[chosen[k]] of the last k whose filled
+ * mask holds the pixel and that has chosen, else 0. */
+int cnr_refine_vote(const uint8_t* filled, const int* inst, const int* obj_ids, int K, int O, int H, int W, int* counts,
+                    void* stream);
+int cnr_refine_apply(const uint8_t* filled, const int* counts, const int* obj_ids, int K, int O, int H, int W, double threshold,
+                     int* chosen, int* refined, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
