@@ -9,9 +9,11 @@ cursor live on the device (the sampler reads the cursor, cnr_step_advance moves 
 step.  Gradients of background and categories are disjoint (separate parameters, train.py:54-64), so running the two
 backward passes one after the other inside the graph is the same step as the reference's single ``batch_loss.backward()``.
 """
+import os
+
 import torch
 
-from . import _C, loss as loss_mod, ops, trainer as trainer_mod
+from . import _C, loss as loss_mod, ops, stepgraph, trainer as trainer_mod
 
 
 class BackgroundStep:
@@ -49,7 +51,7 @@ class BackgroundStep:
         self._perm_gen = torch.Generator(device=dev)
         self._perm_gen.manual_seed(0xB6 + 7919 * int(seed))
         # epoch shuffle: cnr_epoch_perm (one launch) unless CNR_EPOCH_PERM=torch asks for torch.randperm (a dozen launches)
-        self._torch_perm = __import__("os").environ.get("CNR_EPOCH_PERM", "kernel") == "torch"
+        self._torch_perm = os.environ.get("CNR_EPOCH_PERM", "kernel") == "torch"
         self._perm_seed, self._epoch = 0xB6 + 7919 * int(seed), 0
         self.d_state = torch.zeros(3, device=dev, dtype=torch.int64)
         self._zero = torch.zeros(1, device=dev, dtype=torch.int64)
@@ -78,11 +80,11 @@ class BackgroundStep:
             self._init_fused(n)
         self.bufs = {}
         if precision != "fused":
-            self.loss = torch.zeros((), device=dev)
-            self.losses = torch.zeros(3, device=dev)
+            self._loss = torch.zeros((), device=dev)
+            self.losses = torch.zeros(3, device=dev)       # depth / colour / opacity terms of the last step (src/loss.py:18-74)
         self.cursor = 0
         self.steps_done = 0
-        self.graph = None
+        self._sched = stepgraph.StepGraphs([self], 3)
         self._reshuffle()
 
     def _reshuffle(self):
@@ -104,8 +106,9 @@ class BackgroundStep:
             if self.sample_in_tail:
                 self._sample()      # the epoch's first batch; every later one is drawn by the previous step's last launch
 
-    def _body(self):
-        """sample -> PE -> OccupancyMap -> composite + losses -> backward -> AdamW -> advance (all stream-ordered)."""
+    def record(self, slot=None, par=0):
+        """sample -> PE -> OccupancyMap -> composite + losses -> backward -> AdamW -> advance (all stream-ordered).  (One state
+        copy and no loss history: the slot and the parity of stepgraph's branch interface mean nothing here.)"""
         if self.precision == "fused":
             return self._body_fused()
         cfg, t = self.cfg, self.trainer
@@ -119,7 +122,7 @@ class BackgroundStep:
         loss.backward()
         ops.adamw_step(self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, cfg.learning_rate, (0.9, 0.999), 1e-8,
                        cfg.weight_decay, 0, 1.0, d_state=self.d_state)          # step = d_state[2] + 1, advanced below
-        self.loss.copy_(loss.detach())
+        self._loss.copy_(loss.detach())
         self.losses.copy_(torch.stack([ld["depth"][0], ld["color"][0], ld["opacity"][0]]).detach())
         _C.call("cnr_step_advance", self.d_state, self.R)
 
@@ -140,13 +143,13 @@ class BackgroundStep:
         M = self.M = self.R * self.S
         # composite / losses inside the backward launch (cnr_bg_backward_render: a ray on one wave, S <= 64); CNR_BG_FUSE_RENDER=0:
         # the separate cnr_render_loss launch
-        self.fuse_render = self.S <= 64 and __import__('os').environ.get('CNR_BG_FUSE_RENDER', '1') != '0'
+        self.fuse_render = self.S <= 64 and os.environ.get('CNR_BG_FUSE_RENDER', '1') != '0'
         # the NEXT step's rays sampled by extra blocks of this step's last launch (cnr_bg_tail_sample): the step then starts with the
         # forward; CNR_BG_SAMPLE_IN_TAIL=0: cnr_sample_rays as every step's first launch
-        self.sample_in_tail = __import__('os').environ.get('CNR_BG_SAMPLE_IN_TAIL', '1') != '0'
+        self.sample_in_tail = os.environ.get('CNR_BG_SAMPLE_IN_TAIL', '1') != '0'
         # samples per weight-gradient workgroup: 384 -> 5 layers x 44 chunks = 220 workgroups, one round on 256 CUs (measured 17.5 us;
         # 256: 20.2, 512: 21.2)
-        self.dw_chunk = int(__import__('os').environ.get('CNR_BG_DW_CHUNK', '384'))
+        self.dw_chunk = int(os.environ.get('CNR_BG_DW_CHUNK', '384'))
         self.nblk, self.nchunk = int(lib.cnr_bg_blocks(M)), int(lib.cnr_bg_dw_chunks(M, self.dw_chunk))
         self.gscale = float(2 ** round(math.log2(max(self.R, 2))))      # power-of-two loss scale of the f16 gradient chain
         self.n_slices = self.pool_rows // self.R
@@ -162,27 +165,18 @@ class BackgroundStep:
                        rl_ws=torch.zeros(max(_C.render_loss_workspace_bytes(1, self.R),
                                              int(lib.cnr_bg_backward_render_workspace_bytes(M))), device=dev, dtype=torch.uint8),
                        losses=torch.zeros(3, 1, device=dev), flags=torch.zeros(1, device=dev, dtype=torch.int32))
-
-    @property
-    def losses(self):
-        """(3,) depth / colour / opacity terms of the last step (src/loss.py:18-74)"""
-        return self.fb["losses"][:, 0] if self.precision == "fused" else self._losses
-
-    @losses.setter
-    def losses(self, v):
-        self._losses = v
+        self.losses = self.fb["losses"][:, 0]              # a view of what the step's last launch writes: no torch kernel in the step
 
     @property
     def loss(self):
         """the step's scalar loss: depth + 5 colour + 10 opacity (formed on demand in the fused tier: nobody reads it per step)"""
-        if self.precision == "fused":
-            l = self.fb["losses"][:, 0]
-            return l[0] + 5.0 * l[1] + 10.0 * l[2]
-        return self._loss
+        l = self.losses
+        return l[0] + 5.0 * l[1] + 10.0 * l[2] if self.precision == "fused" else self._loss
 
-    @loss.setter
-    def loss(self, v):
-        self._loss = v
+    @property
+    def graph(self):
+        """the captured step (None until the fourth step)"""
+        return self._sched.graphs.get(0)
 
     def _body_fused(self):
         """forward -> composite + losses + their gradient + backward -> weight gradients -> reduce + AdamW + fragment refresh + loss
@@ -224,7 +218,6 @@ class BackgroundStep:
             _C.call("cnr_bg_tail", self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, o["partials"], self.nchunk, o["records"],
                     self.nblk, self.gscale, cfg.learning_rate, 0.9, 0.999, 1e-8, cfg.weight_decay, self.d_state, -1, o["packed"],
                     o["rl_ws"], 0 if self.fuse_render else self.R, o["losses"], o["flags"])
-        # (self.losses / self.loss are views of / derived from o["losses"]: see the properties -- no torch kernel in the step)
 
     def _sample(self):
         """a2-a6 for the step at the device cursor (cnr_sample_rays, world frame, per-epoch max-depth table) into self.bufs"""
@@ -247,52 +240,50 @@ class BackgroundStep:
         self.exp_avg_sq.zero_()
         self.d_state[2:3].zero_()
 
-    def pre_step(self):
+    # ---- the branch interface of stepgraph.StepGraphs (with ``record`` above and ``steps_done``) ------------------------------
+    parity = 0                # one state copy: a captured step depends on nothing the host changes
+
+    def before_step(self):
         if self.precision == "fused" and (self._packed_for is None or self._packed_for != self.flat._version):
             self.repack()
         if self.cursor >= self.pool_rows - self.R:
             self._reshuffle()
+        return -(-(self.pool_rows - self.R - self.cursor) // self.R)       # steps before the next reshuffle
 
-    def post_step(self):
-        self.cursor += self.R
-        self.steps_done += 1
+    def advance(self, U=1):
+        self.cursor += U * self.R
+        self.steps_done += U
         if self.precision == "fused":
-            self._packed_for = self.flat._version     # (the step's own update: kernels do not bump torch's version counter)
+            self._packed_for = self.flat._version     # (the steps' own updates: kernels do not bump torch's version counter)
 
     def step(self, use_graph=True):
-        """One background step; after three eager steps it is captured and replayed."""
-        self.pre_step()
-        if not use_graph or self.steps_done < 3:
-            self._body()
-        else:
-            if self.graph is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._body()
-                self.graph = g
-            self.graph.replay()
-        self.post_step()
+        """One background step; after three eager steps it is captured and replayed (stepgraph.StepGraphs)."""
+        self._sched.step(use_graph)
 
 
 class FullStepTrainer:
     """train.py:113-184 in one replay: the background step and the fused category step captured into ONE hipGraph per
     state parity of the category trainer (its parameters / step state ping-pong between two copies)."""
 
-    def __init__(self, categories, background, concurrent=None):
+    def __init__(self, categories, background, concurrent=None, free_chains=None):
         """concurrent: capture the background step on a second stream (forked from / joined to the capturing stream), so that
         the graph holds two independent chains -- the two branches share no parameter and no buffer.  Default: on.
         ``background`` may be None (a scene without a background model, train.py:113 ``if scene_bg is not None``): the iteration is
         then the category step alone and ``run`` / ``step`` are the category trainer's."""
-        import os
         self.obj, self.bg = categories, background
         assert not self.obj.grad_exchange, "ray-sharded category steps run a collective between their two graphs"
-        self.graphs = {}
-        self.steps_done = 0
         self.concurrent = bool(int(os.environ.get("CNR_FULLSTEP_CONCURRENT", "1"))) if concurrent is None else bool(concurrent)
         self.concurrent = self.concurrent and background is not None
-        self._side = torch.cuda.Stream(device=self.obj.device) if self.concurrent else None
         # run(): fork once per graph (True) or once per iteration (False: every iteration ends with a join of the two chains)
-        self.free_chains = os.environ.get("CNR_FULLSTEP_FREE", "1") != "0"
+        self.free_chains = os.environ.get("CNR_FULLSTEP_FREE", "1") != "0" if free_chains is None else bool(free_chains)
+        if background is None:
+            self._sched = self.obj._sched
+        else:       # (three eager iterations; the category trainer's `unroll` bounds a group: it has unroll - 1 history slots)
+            self._sched = stepgraph.StepGraphs(
+                [self.obj, self.bg], 3, self.obj.unroll,
+                layout="single" if not self.concurrent else "free" if self.free_chains else "iter",
+                side=torch.cuda.Stream(device=self.obj.device) if self.concurrent else None)
+        self.graphs = self._sched.graphs
         self.categories, self.scene_bg = None, None        # the reference-side objects (from_scene)
 
     # ---- behind the reference's objects (train.py:33-96 builds them, :98-201 is what this class replaces) -----------------------
@@ -388,103 +379,18 @@ class FullStepTrainer:
             d["background"] = {"depth": b[0:1], "color": b[1:2], "opacity": b[2:3]}
         return d
 
-    def _both(self):
-        """background + categories, on one stream or forked onto two"""
-        if self.bg is None:
-            return self.obj._step_body()
-        if not self.concurrent:
-            self.bg._body()
-            self.obj._step_body()
-            return
-        cur = torch.cuda.current_stream()
-        self._side.wait_stream(cur)
-        with torch.cuda.stream(self._side):
-            self.bg._body()
-        self.obj._step_body()
-        cur.wait_stream(self._side)
-
     def run(self, n, unroll=8):
         """``n`` iterations, the same arithmetic as ``n`` calls of ``step()`` (bitwise: tests/test_bg_fused_gpu.py), with groups of up
         to ``unroll`` iterations captured as ONE hipGraph -- both branches keep cursor, RNG step and optimiser step on the device, so
         a group replays unchanged; it never crosses an epoch end of either pool (the reshuffles are host-launched).  Between two
-        graph launches the GPU idles ~8 us: 5 % of a 0.15 ms iteration."""
-        o, b = self.obj, self.bg
-        if b is None:
-            self.steps_done += n
-            return o.run(n, unroll)
-        # even group sizes only, like FusedCategoryTrainer.run: a group leaves the parameter / state ping-pong where it found it
-        unroll = max(2, int(unroll) // 2 * 2)
-        while n > 0:
-            o._pre_step()
-            b.pre_step()
-            left = min(-(-(o.pool_rows - o.Rg - o.cursor) // o.Rg), -(-(b.pool_rows - b.R - b.cursor) // b.R))
-            U = 0
-            if self.steps_done >= 3 and o.use_graph:
-                for u in o._group_sizes(min(unroll, o.unroll)):
-                    if u <= n and u <= left:
-                        U = u
-                        break
-            if not U:
-                self.step()
-                n -= 1
-                continue
-            key = (o.parity, U)
-            if key not in self.graphs:
-                par0 = o.parity
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    if self.concurrent and self.free_chains:
-                        # the two chains of all U iterations as two branches that meet only at the end of the graph: iteration
-                        # i + 1 of one chain waits for nothing of the other (they share no parameter and no buffer)
-                        cur = torch.cuda.current_stream()
-                        self._side.wait_stream(cur)
-                        with torch.cuda.stream(self._side):
-                            for i in range(U):
-                                self.bg._body()
-                        for i in range(U):
-                            o._out_slot = i if i < U - 1 else None
-                            o._step_body()
-                            o.parity ^= 1
-                        cur.wait_stream(self._side)
-                    else:
-                        for i in range(U):
-                            o._out_slot = i if i < U - 1 else None
-                            self._both()
-                            o.parity ^= 1
-                o._out_slot, o.parity = None, par0
-                self.graphs[key] = g
-            assert U % 2 == 0
-            self.graphs[key].replay()
-            before = o.steps_done
-            o._last_multi = U - 1
-            o.cursor += U * o.Rg
-            o.steps_done += U                     # (U is even: the state parity is where it was)
-            b.cursor += U * b.R
-            b.steps_done += U
-            if b.precision == "fused":
-                b._packed_for = b.flat._version
-            self.steps_done += U
-            n -= U
-            if o.check_every and o.steps_done // o.check_every != before // o.check_every:
-                o.check_flags()
+        graph launches the GPU idles ~8 us: 5 % of a 0.15 ms iteration.  Eager throughout if the category trainer was built with
+        ``use_graph=False``."""
+        self._sched.run(n, unroll, self.obj.use_graph)
 
     def step(self):
-        o, b = self.obj, self.bg
-        if b is None:
-            self.steps_done += 1
-            return o.step()
-        o._pre_step()
-        b.pre_step()
-        par = o.parity
-        if self.steps_done < 3:
-            self._both()
-        else:
-            if par not in self.graphs:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._both()
-                self.graphs[par] = g
-            self.graphs[par].replay()
-        o._post_step()
-        b.post_step()
-        self.steps_done += 1
+        self._sched.step(self.obj.use_graph)
+
+    @property
+    def steps_done(self):
+        """iterations sent out so far"""
+        return self._sched.steps_done

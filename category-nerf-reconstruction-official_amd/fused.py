@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import _C, ops, parallel
+from . import _C, ops, parallel, stepgraph
 from .embedding import UNIDIRS
 from .ops import LATENT_LAYERS, TRUNK_LAYERS, TRUNK_PARAMS
 
@@ -277,8 +277,10 @@ class FusedCategoryTrainer:
             self._nwg = self._ft_blocks
         self.use_graph = use_graph
         self.split_graph = bool(split_graph)     # the two-graph form of the distributed step, for single-GPU tests
-        self.graphs = {}                         # parity -> captured graph (or (front, back) pair)
         self.steps_done = 0
+        split = self.grad_exchange or self.split_graph
+        self._sched = stepgraph.StepGraphs([self], 2, self.unroll, groups=not split, single=self._split_step if split else None)
+        self.graphs = self._sched.graphs         # parity -> graph (or (front, back) pair), (parity, U) -> graph of U steps
         self._reshuffle()
 
     # ---- one step, eager (also the body that gets captured) ------------------------------------------
@@ -411,41 +413,24 @@ class FusedCategoryTrainer:
         """One train step.  Returns nothing; ``self.losses`` (3,C) / ``self.flags`` (C,) hold the device-side
         loss terms (depth, colour, opacity) and flags of the step just run.
 
-        After two eager steps the step is captured, once per state parity: one hipGraph on a single GPU; with a
-        process group TWO graphs around the all-reduce (front graph, eager RCCL call, back graph) -- three host
-        calls per step, and no collective inside a capture."""
-        self._pre_step()
-        split = self.grad_exchange or self.split_graph
+        After two eager steps the step is captured, once per state parity (stepgraph.StepGraphs): one hipGraph on a
+        single GPU, two around a gradient all-reduce (``_split_step``)."""
+        self._sched.step(self.use_graph)
+
+    def _split_step(self, graph):
+        """The step with a process group: TWO graphs around the all-reduce (front graph, eager RCCL call, back graph sharing
+        the front graph's pool) -- three host calls per step, and no collective inside a capture."""
         par = self.parity
-        if not self.use_graph or self.steps_done < 2:
-            self._step_body()
-        elif par not in self.graphs:
-            if split:
-                ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ga):
-                    self._step_front()
-                ga.replay()                  # capture only records: run the part it stands for
-                if self.grad_exchange and self.pg is not None:
-                    parallel.allreduce_sum_(self.grad, self.pg)
-                with torch.cuda.graph(gb, pool=ga.pool()):
-                    self._step_back()
-                gb.replay()
-                self.graphs[par] = (ga, gb)
-            else:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._step_body()
-                g.replay()
-                self.graphs[par] = g
-        elif split:
-            self.graphs[par][0].replay()
-            if self.grad_exchange and self.pg is not None:
-                parallel.allreduce_sum_(self.grad, self.pg)
-            self.graphs[par][1].replay()
-        else:
-            self.graphs[par].replay()
-        self._last_multi = 0
-        self._post_step()
+        if not graph:
+            return self._step_body()
+        if par not in self.graphs:
+            front = self._sched.capture(self._step_front)
+            self.graphs[par] = (front, self._sched.capture(self._step_back, pool=front.pool()))
+        front, back = self.graphs[par]
+        front.replay()
+        if self.grad_exchange and self.pg is not None:
+            parallel.allreduce_sum_(self.grad, self.pg)
+        back.replay()
 
     def run(self, n, unroll=None):
         """``n`` train steps, the same arithmetic as ``n`` calls of ``step()`` (bitwise: tests/test_trainer_gpu.py), with
@@ -456,92 +441,40 @@ class FusedCategoryTrainer:
         and is not used around a gradient all-reduce; those steps go out one by one.  ``self.losses`` / ``self.flags``
         hold the LAST step's values, ``loss_history()`` the values of every step of the last launch; ``check_flags``
         looks at all of them."""
-        U0 = self.unroll if unroll is None else max(2, int(unroll) // 2 * 2)
-        U0 = min(U0, self.unroll)
-        multi_ok = self.use_graph and not (self.grad_exchange or self.split_graph)
-        while n > 0:
-            if self.cursor >= self.pool_rows - self.Rg:
-                self._reshuffle()
-            left = -(-(self.pool_rows - self.Rg - self.cursor) // self.Rg)     # steps before the next reshuffle
-            # the largest even group that fits what is left of the request and of the epoch (each launch boundary idles the GPU ~8 us)
-            U = 0
-            if multi_ok and self.steps_done >= 2:
-                for u in self._group_sizes(U0):
-                    if u <= n and u <= left:
-                        U = u
-                        break
-            if not U:
-                self.step()
-                n -= 1
-                continue
-            key = (self.parity, U)
-            if key not in self.graphs:
-                self._capture_multi(self.parity, U)
-            self.graphs[key].replay()
-            self._last_multi = U - 1
-            before = self.steps_done
-            self.cursor += U * self.Rg
-            self.steps_done += U
-            n -= U
-            if self.check_every and self.steps_done // self.check_every != before // self.check_every:
-                self.check_flags()
+        self._sched.run(n, unroll, self.use_graph)
 
-    @staticmethod
-    def _group_sizes(U0):
-        """group sizes of the multi-step graphs, largest first: EVERY even size U0, U0 - 2, .., 2.  (A halving ladder -- U0,
-        U0 / 2, .. -- sent the 7 steps in front of an epoch end and the 13 behind it out as 4 + 2 + 1 and 10 + 2 + 1: six graph
-        launches and the reshuffle's three kernels in a row, ~400 us of host work against ~400 us of GPU work queued: a 20-step
-        region with an epoch end inside ran 82 us per step.  With every even size it is 6 + 1 and 12 + 1.)"""
-        return list(range(int(U0) // 2 * 2, 1, -2))
-
-    def _capture_multi(self, par, U):
-        """Record (not run) U steps starting at state parity ``par`` as one graph."""
-        par0 = self.parity
-        self.parity = par
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for i in range(U):
-                self._out_slot = i if i < U - 1 else None
-                self._step_body()
-                self.parity ^= 1
-        self._out_slot, self.parity = None, par0
-        self.graphs[(par, U)] = g
+    _group_sizes = staticmethod(stepgraph.group_sizes)
 
     def prepare_graphs(self, unroll=None):
-        """Capture every graph ``step()`` / ``run()`` can need -- one step and ``unroll`` steps, from either state parity --
-        without running them, so that no capture (a millisecond of host work) lands inside a timed or latency-sensitive
-        region later.  Needs two steps done (the buffers exist); a no-op without graphs or around a gradient all-reduce."""
-        if not self.use_graph or self.grad_exchange or self.split_graph or self.steps_done < 2:
-            return
-        U = min(self.unroll if unroll is None else max(2, int(unroll) // 2 * 2), self.unroll)
-        par0 = self.parity
-        for par in (0, 1):
-            if par not in self.graphs:
-                self.parity = par
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._step_body()
-                self.graphs[par] = g
-            self.parity = par0
-            for u in self._group_sizes(U):
-                if (par, u) not in self.graphs:
-                    self._capture_multi(par, u)
-        self.parity = par0
+        """Capture every graph ``step()`` / ``run()`` can need without running them (stepgraph.StepGraphs.prepare).  Needs two
+        steps done (the buffers exist); a no-op without graphs or around a gradient all-reduce."""
+        self._sched.prepare(unroll, self.use_graph)
 
     def loss_history(self):
         """(k, 3, C): the loss terms of the k steps of the last launch (k = 1 after ``step()``), oldest first."""
         return torch.cat([self._loss_hist[:self._last_multi], self.losses[None]])
 
-    def _pre_step(self):
+    # ---- the branch interface of stepgraph.StepGraphs (with ``parity`` and ``steps_done``) ------------------------------
+    def before_step(self):
         if self.cursor >= self.pool_rows - self.Rg:    # epoch end: reshuffle (i_batch >= N - n, scene_cateogries.py:439-449)
             self._reshuffle()
+        return -(-(self.pool_rows - self.Rg - self.cursor) // self.Rg)     # steps before the next reshuffle
 
-    def _post_step(self):
-        self.parity ^= 1
-        self.cursor += self.Rg
-        self.steps_done += 1
-        if self.check_every and self.steps_done % self.check_every == 0:
+    def record(self, slot, par):
+        keep, self.parity, self._out_slot = self.parity, par, slot
+        self._step_body()
+        self.parity, self._out_slot = keep, None
+
+    def advance(self, U=1):
+        before = self.steps_done
+        self.parity ^= U & 1
+        self.cursor += U * self.Rg
+        self.steps_done += U
+        self._last_multi = U - 1                       # steps of this launch that left their values in the history slots
+        if self.check_every and self.steps_done // self.check_every != before // self.check_every:
             self.check_flags()
+
+    _pre_step, _post_step = before_step, advance       # (the names the emulated ranks of tests/test_multigpu_gpu.py step by)
 
     def _rng_map(self):
         """(first global class, class stride, global rays per class, first ray of this rank): the Philox counter of a ray

@@ -240,6 +240,42 @@ def test_whole_iteration_run_in_multi_iteration_graphs_equals_single_steps(dev):
     assert torch.equal(a.bg.d_state, b.bg.d_state)
 
 
+@pytest.mark.parametrize("concurrent,free_chains", [(False, True), (True, False)])
+def test_single_stream_and_per_iteration_fork_layouts_equal_single_steps(dev, concurrent, free_chains):
+    """The two layouts of a two-branch group that the test above does not take -- everything on one stream, and a fork and a join
+    in every iteration: run(17, unroll=4) against 17 step() calls, bit for bit.  Category pools of 7 slices, a background pool of
+    6: groups of 4 and 2 from both state parities across epoch ends of both pools
+    (e e e 2@1 Sb g1@1 So 4@0 Sb 2@0 So 2@0 g1@0 Sb 2@1 in the notation of tests/test_step_schedule_host.py)."""
+    import cnr_amd as cnr
+
+    def make():
+        cfg = cnr.cfg.synthetic_config(device=str(dev), latent_dim=32, n_bins_cam2surface=4, n_bins=12)
+        gen = torch.Generator().manual_seed(21)
+        pools = [cnr.scene_cateogries.synthetic_pool(7 * 64, 4, gen, "cpu") for _ in range(2)]
+        tr = cnr.fused.FusedCategoryTrainer(cfg, 2, 4, pools, 64, dev, seed=1, generator=gen)
+        assert tr._ft_blocks > 0                                     # the one-launch step body
+        cfg_bg = cnr.cfg.synthetic_config(device=str(dev), latent_dim=32, n_bins_cam2surface=4, n_bins=9)
+        cfg_bg.hidden_feature_size_bg, cfg_bg.n_bins_cam2surface_bg = 128, 5
+        torch.manual_seed(31)                                        # module initialisation
+        bg = cnr.background.BackgroundStep(cfg_bg, cnr.scene_cateogries.synthetic_pool(6 * 40, 1, torch.Generator().manual_seed(12), "cpu"),
+                                           40, dev, seed=5, precision="fused")
+        full = cnr.background.FullStepTrainer(tr, bg, concurrent=concurrent, free_chains=free_chains)
+        assert full.concurrent == concurrent and full.free_chains == free_chains
+        return full
+    a, b = make(), make()
+    n = 17
+    a.run(n, unroll=4)
+    for _ in range(n):
+        b.step()
+    torch.cuda.synchronize()
+    assert any(isinstance(k, tuple) and k[1] == 4 for k in a.graphs), list(a.graphs)      # a group of four was used
+    assert a.steps_done == b.steps_done == a.obj.steps_done == b.obj.steps_done == a.bg.steps_done == b.bg.steps_done == n
+    assert a.obj.cursor == b.obj.cursor and a.bg.cursor == b.bg.cursor and a.obj.parity == b.obj.parity
+    assert torch.equal(a.obj.theta, b.obj.theta) and torch.equal(a.obj.losses, b.obj.losses)
+    assert torch.equal(a.bg.flat, b.bg.flat) and torch.equal(a.bg.losses, b.bg.losses)
+    assert torch.equal(a.bg.d_state, b.bg.d_state)
+
+
 def test_fused_background_forward_on_trained_weights(dev, monkeypatch):
     """The fused background forward against the fp32 oracle ON TRAINED WEIGHTS (the category kernel's occupancy left the 1e-3
     bar after training with plain f16 operands, tests/test_trained_parity_gpu.py; the background kernel has the three-product
