@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void param_prep_kernel(const float* __restrict
                                                          float* __restrict__ zl, float* __restrict__ biasrows,
                                                          float* __restrict__ zero_buf, int64_t zero_count, int nzero,
                                                          cnr_sample::SampleArgs sa, int nsample,
-                                                         unsigned char* __restrict__ packed_lo) {
+                                                         unsigned char* __restrict__ packed_lo, int sample_pool) {
   constexpr int NPACK = NKK_FWD + NKK_BWD + 1;
   const int c = blockIdx.y, C = gridDim.y;
   const float* th = theta + (int64_t)c * lay.stride;
@@ -140,7 +140,10 @@ __global__ __launch_bounds__(256) void param_prep_kernel(const float* __restrict
   b -= 4 * lay.n_obj;
   if (b >= nzero) {  // a2-a5: four rays of class c per block
     const int r = (b - nzero) * 4 + (threadIdx.x >> 6);
-    if (nsample > 0 && r < sa.R) cnr_sample::sample_ray(sa, (int64_t)c * sa.R + r, threadIdx.x & 63);
+    if (nsample > 0 && r < sa.R) {   // (sample_pool: the launch's rays qualify for the form with the draws under the loads)
+      if (sample_pool) cnr_sample::sample_ray_pool(sa, (int64_t)c * sa.R + r, threadIdx.x & 63);
+      else cnr_sample::sample_ray(sa, (int64_t)c * sa.R + r, threadIdx.x & 63);
+    }
     PREP_T1(3);
     return;
   }
@@ -669,7 +672,7 @@ extern "C" int cnr_param_prep(const float* theta, int64_t class_stride, int64_t 
   dim3 grid(fz::NKK_FWD + fz::NKK_BWD + 1 + 4 * n_obj + nzero, (unsigned)C);
   hipLaunchKernelGGL(param_prep_kernel, grid, dim3(256), 0, (hipStream_t)stream, theta, lay, off_trunk,
                      (unsigned char*)packed, zl, biasrows, zero_buf, zero_count, nzero, cnr_sample::SampleArgs{}, 0,
-                     (unsigned char*)nullptr);
+                     (unsigned char*)nullptr, 0);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }
@@ -708,7 +711,7 @@ extern "C" int cnr_step_prologue(const cnr_step_prologue_args* a, void* stream) 
   dim3 grid(fz::NKK_FWD + fz::NKK_BWD + 1 + (a->packed_lo ? fz::NKK_GEO : 0) + 4 * n_obj + nzero + nsample, (unsigned)C);
   hipLaunchKernelGGL(param_prep_kernel, grid, dim3(256), 0, (hipStream_t)stream, a->theta, lay, a->off_trunk,
                      (unsigned char*)a->packed, a->zl, a->biasrows, a->zero_buf, a->zero_count, nzero, sa, nsample,
-                     (unsigned char*)a->packed_lo);
+                     (unsigned char*)a->packed_lo, sample && cnr_sample::pool_form_ok(sa) ? 1 : 0);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }

@@ -1,4 +1,5 @@
-// Shared by sample.hip (cnr_sample_rays) and fused_fwd.hip (cnr_step_prologue): a2-a5 for ONE ray on one wavefront.
+// Shared by sample.hip (cnr_sample_rays), fused_fwd.hip (cnr_step_prologue) and bg_fused.hip (cnr_bg_tail_sample): a2-a5 for ONE ray
+// on one wavefront -- sample_ray, and sample_ray_pool: the same ray with its draws and its sort under its loads.
 // See sample.hip for what it restates (src/scene_cateogries.py:24-96, 453-546).
 #pragma once
 #include "cnr_common.h"
@@ -84,41 +85,14 @@ __device__ __forceinline__ void bitonic128(float& v0, float& v1, int lane) {
   }
 }
 
-// one wavefront, one ray (ray < C * R)
-__device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int lane) {
-  const uint8_t* __restrict__ rgbs = a.rgbs; const float* __restrict__ depth = a.depth;
-  const float* __restrict__ dirs_c = a.dirs_c; const float* __restrict__ T = a.T;
-  const float* __restrict__ u = a.u; const float* __restrict__ g = a.g;
-  const uint64_t seed = a.seed; uint64_t offset = a.offset;
-  const int64_t* __restrict__ d_state = a.d_state; const int64_t pool_rows = a.pool_rows;
-  const float* __restrict__ max_bound = a.max_bound; const int world_frame = a.world_frame;
-  const int C = a.C, R = a.R, n1 = a.n1, n2 = a.n2; const float eps = a.eps, stop_eps = a.stop_eps, min_bound = a.min_bound;
-  float* __restrict__ z = a.z; float* __restrict__ pts = a.pts; float* __restrict__ origins = a.origins;
-  float* __restrict__ dirs_o = a.dirs_o; float* __restrict__ gt_rgb = a.gt_rgb; float* __restrict__ gt_depth = a.gt_depth;
-  uint8_t* __restrict__ depth_mask = a.depth_mask; uint8_t* __restrict__ labels = a.labels;
-  const int64_t* __restrict__ pool_indices = a.pool_indices; const int n_obj = a.n_obj; int* __restrict__ ray_row = a.ray_row;
-  const int* __restrict__ perm = a.perm;
-  (void)C;
-  const int c = (int)(ray / R);
-  const int S = n1 + n2;
-  const uint64_t rng_ray = a.rng_R > 0 ? ((uint64_t)c * (uint64_t)(a.rng_cstride > 0 ? a.rng_cstride : 1) + (uint64_t)a.rng_c0) * (uint64_t)a.rng_R
-                                             + (uint64_t)a.rng_r0 + (uint64_t)(ray - (int64_t)c * R)
-                                       : (uint64_t)ray;
-  // pool row of this ray: either the slice itself (pool_rows == 0) or row cursor + r of a device-resident
-  // (C, pool_rows, ...) pool whose cursor lives on the device (hipGraph replay advances it, no host work)
-  int64_t prow = ray;
-  if (pool_rows > 0) {
-    prow = (int64_t)c * pool_rows + d_state[0] + (ray - (int64_t)c * R);
-    if (perm) prow = (int64_t)c * pool_rows + perm[prow];   // epoch shuffle = a new permutation, the pool stays put
-    offset += (uint64_t)d_state[1] * 4;
-  }
-
-  // ---- a2: origin / direction in object (or world) frame -----------------------------------
-  const float* Tm = T + prow * 16;
-  float m00 = Tm[0], m01 = Tm[1], m02 = Tm[2], t0 = Tm[3];
-  float m10 = Tm[4], m11 = Tm[5], m12 = Tm[6], t1 = Tm[7];
-  float m20 = Tm[8], m21 = Tm[9], m22 = Tm[10], t2 = Tm[11];
-  const float dx = dirs_c[prow * 3 + 0], dy = dirs_c[prow * 3 + 1], dz = dirs_c[prow * 3 + 2];
+// ---- the per-ray arithmetic, shared by sample_ray and sample_ray_pool (one text: the two agree bit for bit) ----------------------
+typedef float f4v __attribute__((ext_vector_type(4)));
+struct RayFrame { float ox, oy, oz, ex, ey, ez; };
+// a2: origin / direction in object (or world) frame from the first three rows m[0..11] of the ray's pose
+__device__ __forceinline__ RayFrame ray_frame(const float (&m)[12], float dx, float dy, float dz, int world_frame) {
+  const float m00 = m[0], m01 = m[1], m02 = m[2], t0 = m[3];
+  const float m10 = m[4], m11 = m[5], m12 = m[6], t1 = m[7];
+  const float m20 = m[8], m21 = m[9], m22 = m[10], t2 = m[11];
   float ox, oy, oz, ex, ey, ez;
   if (world_frame) {
     ox = t0; oy = t1; oz = t2;
@@ -142,52 +116,42 @@ __device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int
     ey = i10 * dx + i11 * dy + i12 * dz;
     ez = i20 * dx + i21 * dy + i22 * dz;
   }
-
-  const float d = depth[prow];
-  const uint8_t state = rgbs[prow * 4 + 3];
-  const bool invalid = d <= min_bound;
-  const bool this_obj = (state == 1) && !invalid;
-  if (lane == 0) {
-    if (origins) { origins[ray * 3 + 0] = ox; origins[ray * 3 + 1] = oy; origins[ray * 3 + 2] = oz; }
-    if (dirs_o) { dirs_o[ray * 3 + 0] = ex; dirs_o[ray * 3 + 1] = ey; dirs_o[ray * 3 + 2] = ez; }
-    depth_mask[ray] = invalid ? 0 : 1;
-    labels[ray] = state;
-    if (ray_row) ray_row[ray] = (int)pool_indices[prow] + c * n_obj;   // row of the class-major code tables
-  }
-  if (lane < 3) gt_rgb[ray * 3 + lane] = (float)rgbs[prow * 4 + lane] / 255.0f;
-  if (lane == 3 && gt_depth) gt_depth[ray] = d;
-
-  // ---- a4: sorted, clipped Gaussian offsets for "this object" rays --------------------------
-  float g0 = INFINITY, g1 = INFINITY;  // elements lane and lane+64 of the ray's n2 draws
-  if (this_obj) {
-    if (g) {
-      if (lane < n2) g0 = g[ray * n2 + lane];
-      if (lane + 64 < n2) g1 = g[ray * n2 + lane + 64];
-    } else {
-      uint32_t rnd[4];
-      philox4(seed, rng_ray * 64 + lane, offset ^ 0x9E3779B97F4A7C15ull, rnd);
-      const float sd = eps / 3.0f;
-      const float r0 = sqrtf(-2.0f * __logf(1.0f - u01(rnd[0]))), a0 = 6.28318530718f * u01(rnd[1]);
-      const float r1 = sqrtf(-2.0f * __logf(1.0f - u01(rnd[2]))), a1 = 6.28318530718f * u01(rnd[3]);
-      if (lane < n2) g0 = sd * r0 * __cosf(a0);
-      if (lane + 64 < n2) g1 = sd * r1 * __cosf(a1);
-    }
-    // (up to 64 draws: the second register is all +inf and stays the network's upper half -- the 64-lane network gives the same order)
-    if (n2 <= 64) bitonic64(g0, lane); else bitonic128(g0, g1, lane);
-    g0 = fminf(fmaxf(g0, -eps), eps);
-    g1 = fminf(fmaxf(g1, -eps), eps);
-  }
-
-  // ---- a3/a5: per-column z -------------------------------------------------------------------
-  float mb;
-  if (max_bound) mb = a.mb_slices > 1 ? max_bound[(int64_t)c * a.mb_slices + (int)(d_state[0] / R)] : max_bound[c];
-  else {  // max depth of this step's slice of class c, by this wave (same value as cnr_sample_maxdepth: max is exact)
-    float m = -INFINITY;
-    const int64_t base = pool_rows > 0 ? (int64_t)c * pool_rows + d_state[0] : (int64_t)c * R;
-    for (int r = lane; r < R; r += 64)
-      m = fmaxf(m, depth[perm ? (int64_t)c * pool_rows + perm[base + r] : base + r]);
-    mb = cnr::wave_max(m);
-  }
+  return RayFrame{ox, oy, oz, ex, ey, ez};
+}
+// a4: this lane's Gaussian draws of the ray with Philox index rng_ray: elements lane and lane + 64 of its n2 (+inf beyond n2)
+__device__ __forceinline__ void gauss_draws(uint64_t seed, uint64_t rng_ray, uint64_t offset, float eps, int n2, int lane,
+                                            float& g0, float& g1) {
+  uint32_t rnd[4];
+  philox4(seed, rng_ray * 64 + lane, offset ^ 0x9E3779B97F4A7C15ull, rnd);
+  const float sd = eps / 3.0f;
+  const float r0 = sqrtf(-2.0f * __logf(1.0f - u01(rnd[0]))), a0 = 6.28318530718f * u01(rnd[1]);
+  const float r1 = sqrtf(-2.0f * __logf(1.0f - u01(rnd[2]))), a1 = 6.28318530718f * u01(rnd[3]);
+  if (lane < n2) g0 = sd * r0 * __cosf(a0);
+  if (lane + 64 < n2) g1 = sd * r1 * __cosf(a1);
+}
+// ... sorted over the ray, clipped to +-eps
+__device__ __forceinline__ void sort_clip(float& g0, float& g1, int n2, float eps, int lane) {
+  // (up to 64 draws: the second register is all +inf and stays the network's upper half -- the 64-lane network gives the same order)
+  if (n2 <= 64) bitonic64(g0, lane); else bitonic128(g0, g1, lane);
+  g0 = fminf(fmaxf(g0, -eps), eps);
+  g1 = fminf(fmaxf(g1, -eps), eps);
+}
+// this lane's uniform draw of column s0 + lane
+__device__ __forceinline__ float uniform_draw(uint64_t seed, uint64_t rng_ray, uint64_t offset, int s0, int lane) {
+  uint32_t rnd[4];
+  philox4(seed, rng_ray * 64 + lane, offset + 1 + (s0 >> 6), rnd);
+  return u01(rnd[0]);
+}
+// a3/a5: per-column z and the sample points of one ray (depth d, slice maximum mb, sorted draws g0 / g1 of "this object" rays)
+// (have_uu0: uu0 is this lane's uniform draw of the first 64 columns, drawn by the caller ahead of its loads)
+__device__ __forceinline__ void write_samples(const SampleArgs& a, int64_t ray, int lane, const RayFrame& f, float d, bool invalid,
+                                              bool this_obj, float mb, float g0, float g1, uint64_t rng_ray, uint64_t offset,
+                                              bool have_uu0 = false, float uu0 = 0.0f) {
+  const float* __restrict__ u = a.u;
+  float* __restrict__ z = a.z; float* __restrict__ pts = a.pts;
+  const int n1 = a.n1, n2 = a.n2, S = n1 + n2;
+  const float eps = a.eps, stop_eps = a.stop_eps, min_bound = a.min_bound;
+  const float ox = f.ox, oy = f.oy, oz = f.oz, ex = f.ex, ey = f.ey, ez = f.ez;
   // (loop is wave-uniform: every lane takes part in the shuffles, only loads/stores are predicated)
   for (int s0 = 0; s0 < S; s0 += 64) {
     const int s = s0 + lane;
@@ -195,10 +159,10 @@ __device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int
     float uu = 0.0f;
     if (u) {
       if (live) uu = u[ray * S + s];
+    } else if (have_uu0 && s0 == 0) {
+      uu = uu0;
     } else {
-      uint32_t rnd[4];
-      philox4(seed, rng_ray * 64 + lane, offset + 1 + (s0 >> 6), rnd);
-      uu = u01(rnd[0]);
+      uu = uniform_draw(a.seed, rng_ray, offset, s0, lane);
     }
     const int i = s - n1;
     const int isrc = i < 0 ? 0 : i;
@@ -223,5 +187,134 @@ __device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int
       p[0] = ox + ex * zz; p[1] = oy + ey * zz; p[2] = oz + ez * zz;
     }
   }
+}
+// Philox index of ray r of local class c (SampleArgs::rng_*)
+__device__ __forceinline__ uint64_t rng_index(const SampleArgs& a, int c, int64_t ray) {
+  return a.rng_R > 0 ? ((uint64_t)c * (uint64_t)(a.rng_cstride > 0 ? a.rng_cstride : 1) + (uint64_t)a.rng_c0) * (uint64_t)a.rng_R
+                           + (uint64_t)a.rng_r0 + (uint64_t)(ray - (int64_t)c * a.R)
+                     : (uint64_t)ray;
+}
+
+// one wavefront, one ray (ray < C * R)
+__device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int lane) {
+  const uint8_t* __restrict__ rgbs = a.rgbs; const float* __restrict__ depth = a.depth;
+  const float* __restrict__ dirs_c = a.dirs_c; const float* __restrict__ T = a.T;
+  const float* __restrict__ g = a.g;
+  const uint64_t seed = a.seed; uint64_t offset = a.offset;
+  const int64_t* __restrict__ d_state = a.d_state; const int64_t pool_rows = a.pool_rows;
+  const float* __restrict__ max_bound = a.max_bound;
+  const int R = a.R, n2 = a.n2; const float eps = a.eps, min_bound = a.min_bound;
+  float* __restrict__ origins = a.origins;
+  float* __restrict__ dirs_o = a.dirs_o; float* __restrict__ gt_rgb = a.gt_rgb; float* __restrict__ gt_depth = a.gt_depth;
+  uint8_t* __restrict__ depth_mask = a.depth_mask; uint8_t* __restrict__ labels = a.labels;
+  const int64_t* __restrict__ pool_indices = a.pool_indices; const int n_obj = a.n_obj; int* __restrict__ ray_row = a.ray_row;
+  const int* __restrict__ perm = a.perm;
+  const int c = (int)(ray / R);
+  const uint64_t rng_ray = rng_index(a, c, ray);
+  // pool row of this ray: either the slice itself (pool_rows == 0) or row cursor + r of a device-resident
+  // (C, pool_rows, ...) pool whose cursor lives on the device (hipGraph replay advances it, no host work)
+  int64_t prow = ray;
+  if (pool_rows > 0) {
+    prow = (int64_t)c * pool_rows + d_state[0] + (ray - (int64_t)c * R);
+    if (perm) prow = (int64_t)c * pool_rows + perm[prow];   // epoch shuffle = a new permutation, the pool stays put
+    offset += (uint64_t)d_state[1] * 4;
+  }
+
+  const float* Tm = T + prow * 16;
+  const float m[12] = {Tm[0], Tm[1], Tm[2], Tm[3], Tm[4], Tm[5], Tm[6], Tm[7], Tm[8], Tm[9], Tm[10], Tm[11]};
+  const RayFrame f = ray_frame(m, dirs_c[prow * 3 + 0], dirs_c[prow * 3 + 1], dirs_c[prow * 3 + 2], a.world_frame);
+
+  const float d = depth[prow];
+  const uint8_t state = rgbs[prow * 4 + 3];
+  const bool invalid = d <= min_bound;
+  const bool this_obj = (state == 1) && !invalid;
+  if (lane == 0) {
+    if (origins) { origins[ray * 3 + 0] = f.ox; origins[ray * 3 + 1] = f.oy; origins[ray * 3 + 2] = f.oz; }
+    if (dirs_o) { dirs_o[ray * 3 + 0] = f.ex; dirs_o[ray * 3 + 1] = f.ey; dirs_o[ray * 3 + 2] = f.ez; }
+    depth_mask[ray] = invalid ? 0 : 1;
+    labels[ray] = state;
+    if (ray_row) ray_row[ray] = (int)pool_indices[prow] + c * n_obj;   // row of the class-major code tables
+  }
+  if (lane < 3) gt_rgb[ray * 3 + lane] = (float)rgbs[prow * 4 + lane] / 255.0f;
+  if (lane == 3 && gt_depth) gt_depth[ray] = d;
+
+  // ---- a4: sorted, clipped Gaussian offsets for "this object" rays --------------------------
+  float g0 = INFINITY, g1 = INFINITY;  // elements lane and lane+64 of the ray's n2 draws
+  if (this_obj) {
+    if (g) {
+      if (lane < n2) g0 = g[ray * n2 + lane];
+      if (lane + 64 < n2) g1 = g[ray * n2 + lane + 64];
+    } else {
+      gauss_draws(seed, rng_ray, offset, eps, n2, lane, g0, g1);
+    }
+    sort_clip(g0, g1, n2, eps, lane);
+  }
+
+  // ---- a3/a5: per-column z -------------------------------------------------------------------
+  float mb;
+  if (max_bound) mb = a.mb_slices > 1 ? max_bound[(int64_t)c * a.mb_slices + (int)(d_state[0] / R)] : max_bound[c];
+  else {  // max depth of this step's slice of class c, by this wave (same value as cnr_sample_maxdepth: max is exact)
+    float mx = -INFINITY;
+    const int64_t base = pool_rows > 0 ? (int64_t)c * pool_rows + d_state[0] : (int64_t)c * R;
+    for (int r = lane; r < R; r += 64)
+      mx = fmaxf(mx, depth[perm ? (int64_t)c * pool_rows + perm[base + r] : base + r]);
+    mb = cnr::wave_max(mx);
+  }
+  write_samples(a, ray, lane, f, d, invalid, this_obj, mb, g0, g1, rng_ray, offset);
+}
+
+// sample_ray for a ray of a device-resident pool (pool_rows > 0, max_bound given, Philox draws: u = g = NULL, T 16-byte and rgbs
+// 4-byte aligned: the caller checks), scheduled for the step's first launch, whose longest job it is.  sample_ray is three
+// dependent round trips (device cursor -> permutation entry -> pool row) and only then, because `this_obj` comes out of the pool
+// row, the Gaussian draws, the sort and the uniform draws: all of the arithmetic behind all of the waiting.  None of that
+// arithmetic needs a loaded value beyond the state -- this_obj only decides whether the sorted draws are USED -- so here the
+// Gaussian draws run while the permutation entry is on its way, and the sort and the first uniform draw while the pool row is
+// (a pose row as three 16-byte loads, a pixel as one word).  Same functions, same operands per ray: same bits.
+__device__ __forceinline__ void sample_ray_pool(const SampleArgs& a, int64_t ray, int lane) {
+  const int R = a.R, n2 = a.n2;
+  const int64_t pool_rows = a.pool_rows;
+  const int64_t cursor = a.d_state[0];
+  const uint64_t offset = a.offset + (uint64_t)a.d_state[1] * 4;
+  const int c = (int)(ray / R);
+  const uint64_t rng_ray = rng_index(a, c, ray);
+  // ---- round 2: permutation entry and slice maximum
+  int64_t prow = (int64_t)c * pool_rows + cursor + (ray - (int64_t)c * R);
+  const int pe = a.perm ? a.perm[prow] : 0;
+  const float mb = a.mb_slices > 1 ? a.max_bound[(int64_t)c * a.mb_slices + (int)(cursor / R)] : a.max_bound[c];
+  __builtin_amdgcn_sched_barrier(0);
+  float g0 = INFINITY, g1 = INFINITY;
+  gauss_draws(a.seed, rng_ray, offset, a.eps, n2, lane, g0, g1);   // behind the loads above
+  __builtin_amdgcn_sched_barrier(0);
+  // ---- round 3: the pool row
+  if (a.perm) prow = (int64_t)c * pool_rows + pe;
+  const f4v* Tm = reinterpret_cast<const f4v*>(a.T + prow * 16);
+  const f4v T0 = Tm[0], T1 = Tm[1], T2 = Tm[2];
+  const float dx = a.dirs_c[prow * 3 + 0], dy = a.dirs_c[prow * 3 + 1], dz = a.dirs_c[prow * 3 + 2];
+  const float d = a.depth[prow];
+  const uint32_t px = *reinterpret_cast<const uint32_t*>(a.rgbs + prow * 4);   // r, g, b, state
+  const int64_t pidx = a.ray_row ? a.pool_indices[prow] : 0;
+  __builtin_amdgcn_sched_barrier(0);
+  sort_clip(g0, g1, n2, a.eps, lane);                                           // behind the loads above
+  const float uu0 = uniform_draw(a.seed, rng_ray, offset, 0, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  const float m[12] = {T0[0], T0[1], T0[2], T0[3], T1[0], T1[1], T1[2], T1[3], T2[0], T2[1], T2[2], T2[3]};
+  const RayFrame f = ray_frame(m, dx, dy, dz, a.world_frame);
+  const uint8_t state = (uint8_t)(px >> 24);
+  const bool invalid = d <= a.min_bound;
+  const bool this_obj = (state == 1) && !invalid;
+  if (lane == 0) {
+    if (a.origins) { a.origins[ray * 3 + 0] = f.ox; a.origins[ray * 3 + 1] = f.oy; a.origins[ray * 3 + 2] = f.oz; }
+    if (a.dirs_o) { a.dirs_o[ray * 3 + 0] = f.ex; a.dirs_o[ray * 3 + 1] = f.ey; a.dirs_o[ray * 3 + 2] = f.ez; }
+    a.depth_mask[ray] = invalid ? 0 : 1;
+    a.labels[ray] = state;
+    if (a.ray_row) a.ray_row[ray] = (int)pidx + c * a.n_obj;
+  }
+  if (lane < 3) a.gt_rgb[ray * 3 + lane] = (float)(uint8_t)(px >> (8 * lane)) / 255.0f;
+  if (lane == 3 && a.gt_depth) a.gt_depth[ray] = d;
+  write_samples(a, ray, lane, f, d, invalid, this_obj, mb, g0, g1, rng_ray, offset, true, uu0);
+}
+// whether sample_ray_pool may take a launch's rays (decided on the host, per launch)
+inline bool pool_form_ok(const SampleArgs& a) {
+  return a.pool_rows > 0 && a.d_state && a.max_bound && !a.u && !a.g && ((uintptr_t)a.T & 15) == 0 && ((uintptr_t)a.rgbs & 3) == 0;
 }
 }  // namespace cnr_sample

@@ -1,5 +1,6 @@
 """A/B of two library builds on ONE box: CNR_HIP_LIB=<lib> python tools/ab_step.py [R S [C [n_obj]]] prints the one-launch kernel's
-back-to-back time and the graph step time (medians of 5 x 400 steps)."""
+back-to-back time, the graph step time of step() (medians of 5 x 400 steps) and the step time of run() in groups of tr.unroll
+(medians of 5 x 25 groups; only run() sends groups out: what a change does between the steps of one launch shows there only)."""
 import os
 import sys
 import time
@@ -32,5 +33,16 @@ for _ in range(5):
     torch.cuda.synchronize()
     ts.append((time.perf_counter() - t0) / 400)
 ts.sort()
+tr.prepare_graphs()
+tr.run(4 * tr.unroll)
+rs, n_run = [], 25 * tr.unroll
+for _ in range(5):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.run(n_run)
+    torch.cuda.synchronize()
+    rs.append((time.perf_counter() - t0) / n_run)
+rs.sort()
 print(os.environ.get("CNR_HIP_LIB", "default"), "R", R, "S", S, "C", C, "kernel_us %.2f (min %.2f)" % (ks[2] * 1e3, ks[0] * 1e3),
-      "step_us %.2f (min %.2f)" % (ts[2] * 1e6, ts[0] * 1e6), "Mrays/s %.2f" % (C * R / ts[2] / 1e6), "losses", [round(float(v), 5) for v in torch.as_tensor(tr.loss_values()).flatten().tolist()])
+      "step_us %.2f (min %.2f)" % (ts[2] * 1e6, ts[0] * 1e6), "run_us %.2f (min %.2f, groups of %d)" % (rs[2] * 1e6, rs[0] * 1e6, tr.unroll),
+      "Mrays/s %.2f" % (C * R / ts[2] / 1e6), "losses", [round(float(v), 5) for v in torch.as_tensor(tr.loss_values()).flatten().tolist()])
