@@ -1,5 +1,6 @@
-"""CPU: the C-ABI library loads without a GPU, exports every symbol include/cnr_hip.h declares, the ctypes
-signature table mirrors the header, and argument errors come back as codes (never exit(), never a crash)."""
+"""CPU: the C-ABI library loads without a GPU, exports every symbol include/cnr_hip.h declares, the ctypes tables the binding
+reads from the header are what this file's own reading of it (and the C compiler's) says, and argument errors come back as codes
+(never exit(), never a crash)."""
 import ctypes
 import os
 import re
@@ -22,12 +23,37 @@ def declared_functions():
     return out
 
 
-@pytest.fixture(scope="module")
-def lib():
+def declared_int64_returns():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return set(re.findall(r"\bint64_t\s+(cnr_\w+)\s*\(", src))
+
+
+DECLARED_CTYPES = {"float": ctypes.c_float, "double": ctypes.c_double, "int": ctypes.c_int, "int32_t": ctypes.c_int32,
+                   "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
+
+
+def assert_row_matches(name, row, decls):
+    """one row of _C.SIGNATURES against the parameter declarations declared_functions() read for that name: a pointer is
+    c_void_p, every other C type has exactly one ctypes type, and a type this test does not know fails it"""
+    assert len(row) == len(decls), (name, len(row), len(decls))
+    for ct, decl in zip(row, decls):
+        ctype = decl.replace("const ", "").split()[0]
+        assert "*" in decl or ctype in DECLARED_CTYPES, (name, decl)
+        assert ct is (ctypes.c_void_p if "*" in decl else DECLARED_CTYPES[ctype]), (name, decl, ct)
+
+
+def load_library():
+    """libcnr_hip.so as the binding loads it (argtypes / restype set from its tables), built first when it is not there"""
     if not os.path.exists(LIB):
         import __graft_entry__
         __graft_entry__.build()
-    return ctypes.CDLL(LIB)
+    import cnr_amd
+    return cnr_amd._C.load()
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_library()
 
 
 def test_header_declares_the_hot_path():
@@ -48,18 +74,18 @@ def test_ctypes_table_matches_header():
     import cnr_amd
     fns = declared_functions()
     sig = cnr_amd._C.SIGNATURES
-    assert set(sig) == set(fns), (set(sig) ^ set(fns))
+    assert set(sig) == set(fns) and len(fns) >= 129, (set(sig) ^ set(fns))
     for name, args in fns.items():
-        assert len(sig[name]) == len(args), (name, len(sig[name]), len(args))
-        for ct, decl in zip(sig[name], args):
-            if "*" in decl:
-                assert ct is ctypes.c_void_p, (name, decl)
-            elif decl.startswith("float"):
-                assert ct is ctypes.c_float, (name, decl)
-            elif decl.startswith(("int64_t", "uint64_t")):
-                assert ct in (ctypes.c_int64, ctypes.c_uint64), (name, decl)
-            elif decl.startswith("int"):
-                assert ct is ctypes.c_int, (name, decl)
+        assert_row_matches(name, sig[name], args)
+    seen = {decl.replace("const ", "").split()[0] for args in fns.values() for decl in args if "*" not in decl}
+    assert seen >= {"float", "double", "int", "int64_t", "uint64_t"}, seen          # what the loop above really compared
+
+
+def test_int64_returns_match_header():
+    import cnr_amd
+    want = declared_int64_returns()
+    assert cnr_amd._C._RESTYPE64 == want and len(want) >= 27 and want <= set(declared_functions())
+    assert {"cnr_pack_bytes", "cnr_clique_workspace_bytes", "cnr_tsdf_touch_slots"} <= want
 
 
 def declared_structs():
@@ -88,13 +114,14 @@ def test_argument_blocks_match_the_header():
     _C = cnr_amd._C
     structs = declared_structs()
     assert set(structs) == set(_C.STRUCTS) and len(structs) == 5
-    ctype_of = {"float": ctypes.c_float, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
-                "uint64_t": ctypes.c_uint64}
     for name, fields in structs.items():
         assert fields[0] == ("struct_size", "uint32_t") and fields[1] == ("abi_version", "uint32_t"), name
         assert [f for f, _ in fields[2:]] == [f for f, _ in _C.STRUCTS[name]], name
         for (f, typ), (_, ct) in zip(fields[2:], _C.STRUCTS[name]):
-            assert ct is (ctypes.c_void_p if "*" in typ else ctype_of[typ]), (name, f, typ)
+            assert "*" in typ or typ in DECLARED_CTYPES, (name, f, typ)
+            assert ct is (ctypes.c_void_p if "*" in typ else DECLARED_CTYPES[typ]), (name, f, typ)
+    scalars = {typ for fields in structs.values() for _, typ in fields if "*" not in typ}
+    assert scalars >= {"float", "int32_t", "uint32_t", "int64_t", "uint64_t"}, scalars
     src = '#include <stdio.h>\n#include "cnr_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %d", sizeof(cnr_step_prologue_args), ' \
           'sizeof(cnr_step_tail_args), sizeof(cnr_field_train_args), sizeof(cnr_bg_backward_render_args), ' \
           'sizeof(cnr_bg_tail_sample_args), CNR_ABI_VERSION);return 0;}'
@@ -113,7 +140,7 @@ def test_argument_blocks_of_another_revision_are_refused(lib):
     _C = cnr_amd._C
     for name in _C.STRUCTS:
         fn = getattr(lib, name)
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        assert fn.argtypes == [ctypes.c_void_p, ctypes.c_void_p] and fn.restype is ctypes.c_int, name
         st = _C.struct_type(name)()
         st.struct_size, st.abi_version = ctypes.sizeof(st) - 8, _C.ABI_VERSION
         assert fn(ctypes.byref(st), None) == -1, name
@@ -149,11 +176,6 @@ def test_binding_refuses_short_misspelt_and_surplus_arguments():
 
 def test_argument_errors_are_return_codes(lib):
     """NULL pointers / bad sizes -> CNR_E_ARG (-1) before anything touches the device."""
-    import cnr_amd
-    for name, argtypes in cnr_amd._C.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name in cnr_amd._C._RESTYPE64 else ctypes.c_int
     assert lib.cnr_version() >= 100
     assert lib.cnr_pack_bytes() == 62464
     assert lib.cnr_pe_fwd(None, None, None, 1, 10, 2.0, None) == -1
@@ -162,6 +184,68 @@ def test_argument_errors_are_return_codes(lib):
     assert lib.cnr_step_advance(None, 1, None) == -1
     rec_entries = (13892 + 126 + 15 * 128 + 255) // 256 * 256     # trunk | two dB halves | up to 15 object rows x 128
     assert lib.cnr_field_bwd_workspace_bytes(2, 0) == 2 * 256 * rec_entries * 2       # bf16 entries
+
+
+# ---- the binding's header reader on strings ------------------------------------------------------------------------------------
+HEADER_TAIL = "\n#define CNR_ABI_VERSION 3\n"
+
+
+def test_parse_header_pins_five_signatures():
+    """five rows written out by hand: every row of the type map, both return types and an empty parameter list"""
+    from cnr_amd import _C
+    vp, i, i64, u64, f, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
+    want = {"cnr_version": [],
+            "cnr_camera_rays": [vp, i, i, f, f, f, f, vp],
+            "cnr_sample_rays": [vp, vp, vp, vp, vp, vp, u64, u64, vp, i64, vp, i, i, i, i, i, f, f, f,
+                                vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, i, vp],
+            "cnr_unproject_emit": [vp, vp, vp, i, i, i, d, d, d, d, vp, vp, vp, vp, vp],
+            "cnr_nn_workspace_bytes": [i64, i64]}
+    sig, ret64, structs, version = _C.parse_header(open(HEADER).read())
+    for name, row in want.items():
+        assert len(sig[name]) == len(row) and all(a is b for a, b in zip(sig[name], row)), (name, sig[name])
+        assert (name in ret64) == (name == "cnr_nn_workspace_bytes"), name
+    assert version == 3 and len(structs) == 5
+    # ... and a text of its own: comments of both kinds, a block, the 32-bit types
+    text = """/* int cnr_in_a_comment(int a); */
+    int64_t cnr_a(void);   // int cnr_in_a_line_comment(size_t n);
+    int cnr_b(const uint8_t* p, int32_t a, uint32_t b, int64_t c, uint64_t d, float e, double f, int g,
+              void* stream);
+    typedef struct cnr_c_args {
+      uint32_t struct_size;
+      uint32_t abi_version;   /* first */
+      const float* x;
+      int32_t n;
+      uint64_t seed;
+    } cnr_c_args;
+    int cnr_c(const cnr_c_args* args, void* stream);
+    #define CNR_ABI_VERSION 7
+    """
+    sig, ret64, structs, version = _C.parse_header(text)
+    assert sig == {"cnr_a": [], "cnr_b": [vp, ctypes.c_int32, ctypes.c_uint32, i64, u64, f, d, i, vp], "cnr_c": [vp, vp]}
+    assert ret64 == {"cnr_a"} and version == 7
+    assert structs == {"cnr_c": [("x", vp), ("n", ctypes.c_int32), ("seed", u64)]}
+
+
+@pytest.mark.parametrize("text,match", [
+    ("int cnr_x(const float* p, size_t n, void* stream);", "size_t"),                               # a type outside the map
+    ("void cnr_x(const float* p, void* stream);", "returns 'void'"),                                # a third return type
+    ("int cnr_ok(int n);\nint cnr_x(void (*done)(int), void* stream);", r"prototype for \['cnr_x'\]"),     # not consumed
+    ("typedef struct cnr_x_args { const float* p; int32_t n; } cnr_x_args;\nint cnr_x(const cnr_x_args* a, void* stream);",
+     "must begin with uint32_t struct_size, abi_version"),
+], ids=["size_t_parameter", "void_return", "function_pointer_parameter", "block_without_its_head"])
+def test_parse_header_is_strict(text, match):
+    """what the reader cannot read exactly is an error that names it, never a guessed or a skipped row"""
+    from cnr_amd import _C
+    assert _C.parse_header("int cnr_ok(int n);" + HEADER_TAIL)[0] == {"cnr_ok": [ctypes.c_int]}       # the frame alone reads
+    with pytest.raises(_C.CnrError, match=match):
+        _C.parse_header(text + HEADER_TAIL)
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    from cnr_amd import _C
+    monkeypatch.setattr(_C, "HEADER_PATH", "/nonexistent/include/cnr_hip.h")
+    with pytest.raises(_C.CnrError, match="/nonexistent/include/cnr_hip.h"):
+        _C._read_header()
 
 
 def test_missing_library_fails_loudly(monkeypatch):

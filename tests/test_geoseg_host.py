@@ -11,7 +11,7 @@ import scipy.ndimage as ndi
 
 import geoseg_cpu as G
 from conftest import GOLDEN, ROOT
-from test_abi import LIB, declared_functions
+from test_abi import assert_row_matches, declared_functions, load_library
 
 NEW = ("cnr_geoseg_maps", "cnr_geoseg_edge_map", "cnr_ccl", "cnr_label_counts", "cnr_geoseg_grow", "cnr_fill_holes_workspace_bytes",
        "cnr_fill_holes", "cnr_refine_vote", "cnr_refine_apply")
@@ -25,15 +25,8 @@ def cnr():
 
 
 @pytest.fixture(scope="module")
-def lib(cnr):
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    lib = ctypes.CDLL(LIB)
-    for name in NEW:
-        getattr(lib, name).argtypes = cnr._C.SIGNATURES[name]
-        getattr(lib, name).restype = ctypes.c_int64 if name in cnr._C._RESTYPE64 else ctypes.c_int
-    return lib
+def lib():
+    return load_library()
 
 
 def same_partition(a, b):
@@ -166,10 +159,7 @@ def test_library_exports_the_new_symbols(cnr, lib):
     fns = declared_functions()
     for name in NEW:
         assert name in fns and hasattr(lib, name) and name in cnr._C.SIGNATURES, name
-        assert len(cnr._C.SIGNATURES[name]) == len(fns[name]), name
-        for ct, decl in zip(cnr._C.SIGNATURES[name], fns[name]):
-            want = ctypes.c_void_p if "*" in decl else ctypes.c_double if decl.startswith("double") else ctypes.c_int
-            assert ct is want, (name, decl)
+        assert_row_matches(name, cnr._C.SIGNATURES[name], fns[name])
     for name in ("geometry_segmentation", "refine_inst_data", "Segment", "connected_components", "fill_holes"):
         assert hasattr(cnr.utils, name), name
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import teaser_cpu as TC
-from test_abi import declared_functions
+from test_abi import assert_row_matches, declared_functions, declared_int64_returns
 
 SIGMA = 0.002          # the planted cases' noise per axis
 
@@ -123,14 +123,12 @@ def test_signatures_and_defaults(CR):
 
 
 def test_abi_rows_of_the_new_symbols():
-    import ctypes
     import cnr_amd
     fns, sig = declared_functions(), cnr_amd._C.SIGNATURES
     for name, n_args in (("cnr_teaser_graph", 7), ("cnr_clique_workspace_bytes", 2), ("cnr_clique_search", 9)):
         assert name in fns and name in sig and len(fns[name]) == len(sig[name]) == n_args, name
-        for ct, decl in zip(sig[name], fns[name]):
-            assert (ct is ctypes.c_void_p) == ("*" in decl), (name, decl)
-    assert "cnr_clique_workspace_bytes" in cnr_amd._C._RESTYPE64
+        assert_row_matches(name, sig[name], fns[name])
+    assert "cnr_clique_workspace_bytes" in cnr_amd._C._RESTYPE64 and "cnr_clique_workspace_bytes" in declared_int64_returns()
     lib = cnr_amd._C.load()
     assert lib.cnr_teaser_graph(None, None, 4, 0.02, None, None, None) == -1
     assert lib.cnr_clique_search(None, None, 4, 3, 10, None, None, None, None) == -1

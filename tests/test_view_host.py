@@ -2,7 +2,6 @@
 the edit transforms, the C-ABI of the cnr_view_* entry points, and tests/view_cpu.py against the existing composite
 restatement."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -11,7 +10,7 @@ import torch
 import mc_cpu as M
 import view_cpu as V
 import view_scene as VS
-from test_abi import LIB, declared_functions
+from test_abi import assert_row_matches, declared_functions, load_library
 
 NEW = ("cnr_view_segments_workspace_bytes", "cnr_view_segments_count", "cnr_view_segments_emit", "cnr_view_points",
        "cnr_view_composite")
@@ -24,15 +23,8 @@ def cnr():
 
 
 @pytest.fixture(scope="module")
-def lib(cnr):
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    lib = ctypes.CDLL(LIB)
-    for name in NEW:
-        getattr(lib, name).argtypes = cnr._C.SIGNATURES[name]
-        getattr(lib, name).restype = ctypes.c_int64 if name in cnr._C._RESTYPE64 else ctypes.c_int
-    return lib
+def lib():
+    return load_library()
 
 
 @pytest.fixture(scope="module")
@@ -124,11 +116,7 @@ def test_abi_checks_cover_the_view_entry_points(cnr, lib):
     fns = declared_functions()
     for name in NEW:
         assert name in fns and hasattr(lib, name) and name in cnr._C.SIGNATURES, name
-        assert len(cnr._C.SIGNATURES[name]) == len(fns[name]), name
-        for ct, decl in zip(cnr._C.SIGNATURES[name], fns[name]):
-            want = ctypes.c_void_p if "*" in decl else ctypes.c_float if decl.startswith("float") else \
-                ctypes.c_int64 if decl.startswith("int64_t") else ctypes.c_int
-            assert ct is want, (name, decl)
+        assert_row_matches(name, cnr._C.SIGNATURES[name], fns[name])
     assert cnr.view.KMAX == V.KMAX == 8 and cnr.view.SMAX == 128
     assert lib.cnr_view_segments_workspace_bytes(100, 3) >= (3 * 2) * (4 + 8) + 2 * 4
 
