@@ -136,7 +136,17 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
                 K8_SMALL_BYTES = k8_small(WIDE);
   constexpr bool BROWS_LDS = brows_in_lds8(WIDE, GEO);
   constexpr int SUMS_SCRATCH = 25 * HALF_SUMS_STRIDE * 4;   // per wave, behind the loop (half_sums_lds), in the dead operand fragments
-  static_assert((NCH + NDW) * SUMS_SCRATCH <= PK_BYTES, "scratch of the closing sums");
+  // The record image: behind the loop's last barrier the dW waves assemble the workgroup's record (bf16, REC_ENTRIES entries in
+  // parameter order) in the dead operand fragments behind the chain waves' scratch, and it leaves for memory in 16-byte chunks
+  // of 8 entries (the flush below).  The same place in every instantiation: the packed image is always there.  The dW waves' own
+  // closing sums (PEDW) use their partner's E1 image instead, behind the 63 floats they leave there.
+  constexpr int REC_IMG = NCH * SUMS_SCRATCH, REC_BYTES = REC_ENTRIES * (int)sizeof(rec_t), DW_SCRATCH = 256;
+  static_assert(REC_IMG % 16 == 0 && REC_IMG + REC_BYTES <= PK_BYTES, "record image behind the chain waves' scratch, inside the packed image");
+  static_assert(63 * 4 <= DW_SCRATCH && DW_SCRATCH + 17 * HALF_SUMS_STRIDE * 4 <= E1IMG8, "dW scratch of the closing sums in the E1 image");
+  // chunks that hold an entry produced behind the final barrier (d w_sigma, d b_sigma; the dB halves): stored there, not with the bulk
+  constexpr int LATE_A0 = OFF_SG_W / 8, LATE_NA = OFF_SG_B / 8 - LATE_A0 + 1, LATE_B0 = TRUNK / 8,
+                LATE_NB = (TRUNK + 125) / 8 - LATE_B0 + 1;
+  static_assert(LATE_A0 + LATE_NA <= LATE_B0 && LATE_NA + LATE_NB <= 64 && OFF_SG_W + 32 == OFF_SG_B, "late chunks: one lane of a wave each");
   // PEDW: the PE backward (66 cosines and ~300 multiply-adds per sample, pure VALU work on the critical chain wave) runs on the
   // chain wave's dW partner -- the wave that shares its SIMD and idles through the forward phase.  d e2 / d e1 travel lane to
   // lane as f16 through LDS that is free at that point (the E2 image after step VD, three slot images after step XYZ); the
@@ -245,6 +255,27 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
   const int slot_inv = (65536 + S - 1) / S;
   const int ntiles = KR > 0 ? (int)(((int64_t)R * SP + 31) / 32) : (N + 31) / 32;
   const int tile_step = gridDim.x * NCHW;
+  // The record leaves as 16-byte chunks of the LDS image: entries [0, TRUNK + 126 + the row sums the record carries), rounded up
+  // to a chunk.  Unwritten entries inside the span take what the image holds (every consumer skips them, rec_entry_written).
+  // Write-through buffer stores (aux 16 = sc1): the 29 KB of a workgroup are on their way to memory while the chain waves still run
+  // their closing sums, instead of lying dirty in the XCD's L2 until the end-of-kernel write-back with the step's last launch
+  // reading them from the other XCDs right behind it (measured, CHANGELOG: -0.65 us per step at 2048 x 64; plain 16-byte stores
+  // behind the final barrier were slower than the 255 two-byte stores this replaces).  The descriptor's range check drops
+  // anything past the record.
+  const int n_chunks = (TRUNK + 126 + (rows_per_class <= cnr_rec::ROWS_MAX ? rows_per_class * 128 : 0) + 7) / 8;
+  const auto rec_rsrc = __builtin_amdgcn_make_buffer_rsrc(records + ((size_t)c * gridDim.x + blockIdx.x) * REC_ENTRIES, 0, REC_BYTES, 0x00020000);
+  auto store_chunk = [&](int k) {
+    const u4v v = *reinterpret_cast<const u4v*>(smem + REC_IMG + 16 * k);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rec_rsrc, 16 * k, 0, 16);
+  };
+  auto stream_bulk = [&](int t, int nt) {   // thread t of nt: every chunk of the span but the late ones
+    const int n_bulk = n_chunks - (LATE_NA + LATE_NB);
+#pragma unroll 4
+    for (int j = t; j < n_bulk; j += nt) {
+      const int k = j < LATE_A0 ? j : j + LATE_NA;
+      store_chunk(k < LATE_B0 ? k : k + LATE_NB);
+    }
+  };
 
   // dW waves: up to 5 accumulator blocks each.  Chain waves never touch them; their own persistent per-lane partial
   // sums (dB 33 floats, d w_sigma 16, d b_sigma) are locals of the chain branch, so that branch pays for 50 registers,
@@ -918,6 +949,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       }
     }
     P8PHASE(6);
+    role_barrier();   // the dW waves' record image is complete: they stream it under the sums below
     {  // publish this wave's partial sums (the last barrier has passed: the dW waves no longer read the row table
        // this aliases): [0..31] d w_sigma, [32] d b_sigma, [64..126] dB.  The 50 half-wave sums go through LDS (half_sums_lds; the
        // operand fragments at the front of the LDS are dead behind the loop's last barrier: a wave's scratch lies there), in two
@@ -980,7 +1012,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     // Where this lane's column of each owned block goes in the record: every block kind is affine in the output row,
     // idx(o) = i0 + o * st (weights: st = the layer's row length; a bias column: st = 1), i0 < 0 = not a parameter.
     // Computed here, while the chain waves recompute the first forward: the flush then stores accumulators straight to
-    // the record (no LDS image, no index table, no gather loop: 7 k -> 2.5 k cycles of every workgroup's tail).
+    // their places in the record's LDS image (no index table, no gather loop: 7 k -> 2.5 k cycles of every workgroup's tail).
     // the dW wave shares its SIMD with a chain wave; when both have an instruction ready the dW wave goes first: it is
     // the consumer every layer step waits for (measured: -2 % at 2048 x 64, -5 % at 8192 x 128; the reverse: no effect)
     // (raised BEHIND the record-index setup below: those ~1 000 instructions run beside the chain waves' first forward and must
@@ -1012,8 +1044,10 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     constexpr int DWI = decltype(dwi_c)::value;
     const unsigned char* pcw = chain_base + DWI * K_BYTES;
     // the partner tile's sample position (same index arithmetic as the chain's fetch).  Requested one iteration ahead, right
-    // behind the iteration's last barrier: every barrier's release fence waits for the wave's outstanding loads, so a request
-    // in front of a layer-step barrier puts its round trip on the workgroup's critical path (~0.3 us per iteration, measured)
+    // behind the iteration's last barrier: a request in front of a layer-step barrier measured ~0.3 us per iteration slower.
+    // (Not because the barrier waits for it: role_barrier()'s workgroup-scope fences emit s_waitcnt lgkmcnt(0) only on gfx950 --
+    //  every wait in front of an s_barrier of the flagship instantiation is an lgkmcnt, none a vmcnt -- so outstanding global
+    //  loads cross the barrier.  What the 0.3 us were is not known.)
     auto pts_of = [&](int tile, float& q0, float& q1, float& q2) {
       const int tl = tile < ntiles ? tile : ntiles - 1, n0 = tl * 32;
       int64_t gs;
@@ -1219,15 +1253,15 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     else if (dwid == 2) dw_loop(IC<2>{});
     else dw_loop(IC<3>{});
     P8PHASE(3);
-    // ---- this wave's blocks -> the workgroup's record, straight from the accumulators -------------------------
-    rec_t* rec = records + ((size_t)c * gridDim.x + blockIdx.x) * REC_ENTRIES;
+    // ---- this wave's blocks -> the record image in LDS, straight from the accumulators (same indices as in the record) ----
+    rec_t* img = reinterpret_cast<rec_t*>(smem + REC_IMG);
 #define CNR_PSTORE8(KIND, NROWS)                                                               \
   if (owner8<NDW>(KIND) == dwid) {                                                             \
     constexpr int li = local8<NDW>(KIND);                                                      \
     if (bi0[li] >= 0) {                                                                        \
       _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) {                                   \
         const int o = acc_row(reg, h);                                                         \
-        if (o < (NROWS)) rec[bi0[li] + o * bst[li]] = rec_pack(Wacc[li][reg] * inv_gs);        \
+        if (o < (NROWS)) img[bi0[li] + o * bst[li]] = rec_pack(Wacc[li][reg] * inv_gs);        \
       }                                                                                        \
     }                                                                                          \
   }
@@ -1242,7 +1276,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int o = acc_row(reg, h) - 16;
-        if (o >= 0 && o < 3) rec[r2i0 + o * r2st] = rec_pack(Wacc[li][reg] * inv_gs);
+        if (o >= 0 && o < 3) img[r2i0 + o * r2st] = rec_pack(Wacc[li][reg] * inv_gs);
       }
     }
     if (dwid == owner8<NDW>(BK_RS)) {  // the row-sum block: [m][feature], m = rows_per_class * latent slot + object row | then the two biases
@@ -1252,12 +1286,12 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       for (int reg = 0; reg < 16; ++reg) {
         const int m = acc_row(reg, h);
         const float v = (blk ? Wacc[LI_RS2][reg] : Wacc[LI_RS][reg]) * inv_gs;
-        if (blk == 0 && m == nlat_rows) rec[OFF_ES_B + col] = rec_pack(v);
-        else if (blk == 0 && m == nlat_rows + 1) { if (col < 16) rec[OFF_R0_B + col] = rec_pack(v); }
+        if (blk == 0 && m == nlat_rows) img[OFF_ES_B + col] = rec_pack(v);
+        else if (blk == 0 && m == nlat_rows + 1) { if (col < 16) img[OFF_R0_B + col] = rec_pack(v); }
         else if (!ROWTILE && m < nlat_rows && m - ((m * rpc_inv) >> 16) * rs < rows_per_class) {   // (ROWTILE: flushed every iteration)
           const int slot = 2 * blk + ((m * rpc_inv) >> 16);
           const int i = (m - ((m * rpc_inv) >> 16) * rs) * 128 + slot * 32 + col;  // dbiasrows [row][latent slot][feature]
-          rec[TRUNK + 126 + i] = rec_pack(v);
+          img[TRUNK + 126 + i] = rec_pack(v);
           if (rows_fix)
             atomicAdd(reinterpret_cast<unsigned long long*>(
                           rows_fix + ((size_t)(blockIdx.x % cnr_rec::ROWS_FIX_COPIES) * gridDim.y + c) * rows_per_class * 128 + i),
@@ -1266,9 +1300,13 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       }
     }
     P8PHASE(6);
+    // the image is complete behind this barrier (the chain waves take it in front of their closing sums): the dW waves stream it
+    // while the chain waves sum
+    role_barrier();
+    stream_bulk(threadIdx.x - NCH * 64, NDW * 64);
     if constexpr (PEDW) {   // dB partial sums of the partner's tiles -> the partner's E1 image (free: the loop is over), 63 floats
       float* e1f = reinterpret_cast<float*>(chain_base + dwid * K_BYTES + K_E1);
-      float* scr = reinterpret_cast<float*>(smem + wv * SUMS_SCRATCH);
+      float* scr = e1f + DW_SCRATCH / 4;   // (the record image lies where the dW waves' share of the front scratch would be)
       auto put_db = [&](int i, int hh, float s) {
         const int d = i / 3;
         if (!(hh == 1 && d == 10)) e1f[(11 * hh + d) * 3 + (i - 3 * d)] = s;
@@ -1285,7 +1323,6 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
 
   // ========================================= flush ====================================================
   // (the dW waves have written their blocks above; what is left are the chain waves' partial sums)
-  rec_t* rec = records + ((size_t)c * gridDim.x + blockIdx.x) * REC_ENTRIES;
   P8PHASE(7);
   __syncthreads();
   P8PHASE(2);
@@ -1304,9 +1341,15 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       }
       return v;
     };
-    for (int i = threadIdx.x; i < 63; i += NTHR) { rec[TRUNK + i] = rec_pack((sum_chain(64 + i) + sum_dw(i)) * inv_gs); rec[TRUNK + 63 + i] = 0; }
-    for (int i = threadIdx.x; i < 32; i += NTHR) rec[OFF_SG_W + i] = rec_pack(sum_chain(i) * inv_gs);
-    if (threadIdx.x == 0) rec[OFF_SG_B] = rec_pack(sum_chain(32) * inv_gs);
+    if (wv == 0) {   // the late entries: patched into the image, then the chunks that hold one (LDS operations of a wave run in order)
+      rec_t* img = reinterpret_cast<rec_t*>(smem + REC_IMG);
+      for (int i = lane; i < 63; i += 64) { img[TRUNK + i] = rec_pack((sum_chain(64 + i) + sum_dw(i)) * inv_gs); img[TRUNK + 63 + i] = 0; }
+      for (int i = lane; i < 32; i += 64) img[OFF_SG_W + i] = rec_pack(sum_chain(i) * inv_gs);
+      if (lane == 0) img[OFF_SG_B] = rec_pack(sum_chain(32) * inv_gs);
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      if (lane < LATE_NA + LATE_NB) store_chunk(lane < LATE_NA ? LATE_A0 + lane : LATE_B0 + (lane - LATE_NA));
+    }
     if constexpr (KR > 0) {   // per-block loss partials + the class header, the format of cnr_field_fwd_render
       const int nb = gridDim.x, Cn = gridDim.y;
       if (threadIdx.x < 3) ta.partials[((size_t)c * nb + blockIdx.x) * 3 + threadIdx.x] = sum_chain(40 + threadIdx.x);
