@@ -29,6 +29,16 @@ __device__ __forceinline__ void stage_hs(unsigned char* img, const h8& f0, const
   *reinterpret_cast<h4*>(row + (((4 + h) ^ sw) << 3)) = f1.lo;
   *reinterpret_cast<h4*>(row + (((6 + h) ^ sw) << 3)) = f1.hi;
 }
+// the inverse of stage_hs: lane (col, h) takes back the two fragments that lane (col, h) staged -- four 8-byte reads at the
+// swizzled chunk addresses stage_hs wrote (an accumulator-layout pair out of another wave's image, as a B operand)
+__device__ __forceinline__ void unstage_hs(const unsigned char* img, h8& f0, h8& f1, int col, int h) {
+  const unsigned char* row = img + col * 64;
+  const int sw = (col >> 1) & 7;
+  f0.lo = *reinterpret_cast<const h4*>(row + (((0 + h) ^ sw) << 3));
+  f0.hi = *reinterpret_cast<const h4*>(row + (((2 + h) ^ sw) << 3));
+  f1.lo = *reinterpret_cast<const h4*>(row + (((4 + h) ^ sw) << 3));
+  f1.hi = *reinterpret_cast<const h4*>(row + (((6 + h) ^ sw) << 3));
+}
 __device__ __forceinline__ h8 tr_frag_hs(const unsigned char* img, int s, int lane) {
   const int i = lane & 15, g16 = lane >> 4, q = i >> 2, p = i & 3, hh = g16 >> 1;
   const int r = 16 * s + 8 * hh + q, chunk = 4 * (g16 & 1) + p;

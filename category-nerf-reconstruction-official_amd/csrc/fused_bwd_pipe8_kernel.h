@@ -142,16 +142,17 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
   // closing sums (PEDW) use their partner's E1 image instead, behind the 63 floats they leave there.
   constexpr int REC_IMG = NCH * SUMS_SCRATCH, REC_BYTES = REC_ENTRIES * (int)sizeof(rec_t), DW_SCRATCH = 256;
   static_assert(REC_IMG % 16 == 0 && REC_IMG + REC_BYTES <= PK_BYTES, "record image behind the chain waves' scratch, inside the packed image");
+  static_assert(REC_ENTRIES < 65535, "a record index and its stride share a register across the dW loop");
   static_assert(63 * 4 <= DW_SCRATCH && DW_SCRATCH + 17 * HALF_SUMS_STRIDE * 4 <= E1IMG8, "dW scratch of the closing sums in the E1 image");
   // chunks that hold an entry produced behind the final barrier (d w_sigma, d b_sigma; the dB halves): stored there, not with the bulk
   constexpr int LATE_A0 = OFF_SG_W / 8, LATE_NA = OFF_SG_B / 8 - LATE_A0 + 1, LATE_B0 = TRUNK / 8,
                 LATE_NB = (TRUNK + 125) / 8 - LATE_B0 + 1;
   static_assert(LATE_A0 + LATE_NA <= LATE_B0 && LATE_NA + LATE_NB <= 64 && OFF_SG_W + 32 == OFF_SG_B, "late chunks: one lane of a wave each");
   // PEDW: the PE backward (66 cosines and ~300 multiply-adds per sample, pure VALU work on the critical chain wave) runs on the
-  // chain wave's dW partner -- the wave that shares its SIMD and idles through the forward phase.  d e2 / d e1 travel lane to
-  // lane as f16 through LDS that is free at that point (the E2 image after step VD, three slot images after step XYZ); the
-  // partner needs a barrier between its reads and the chain wave's next writes there, which the composite exchange of rays
-  // that span tiles (KR > 1) provides.  Measured bound (PE backward deleted): 40.4 -> 36.9 us at 2048 x 64, 259 -> 228 at 8192 x 128.
+  // chain wave's dW partner -- the wave that shares its SIMD and idles through the forward phase -- and so do the products d e2 /
+  // d e1 that feed it (de_products): the partner takes the three dPre pairs they are formed from out of the chain wave's dPre
+  // images during the layer steps and does the rest behind the iteration's last barrier.  Rays that span tiles only (KR > 1).
+  // Measured bound (PE backward deleted): 40.4 -> 36.9 us at 2048 x 64, 259 -> 228 at 8192 x 128.
   constexpr bool PEDW = KR > 1;
   constexpr int SP = TWO ? 16 : (KR > 0 ? 32 * KR : 32);   // padded sample slots per ray (one-launch form)
   constexpr int NCHW = NCH, NTHR = (NCH + NDW) * 64, NACC = 5, LI_RS = local8<NDW>(BK_RS), LI_RS2 = local8<NDW>(BK_RS2);
@@ -283,8 +284,8 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
   f16v Wacc[NACC];
 #pragma unroll
   for (int b = 0; b < NACC; ++b) Wacc[b] = zero16();
-  // PEDW: the PE backward from the f16 copies of d e1 / d e2 a chain wave left in LDS (dq[2 b + reg / 8][reg % 8] = de[b][reg],
-  // dq[6 ..] likewise for d e2), for the lane's own sample at (t0x, t1x, t2x); both roles run it (the dW partner for every tile
+  // PEDW: the PE backward from the f16 roundings of d e1 / d e2 (dq[2 b + reg / 8][reg % 8] = de[b][reg], dq[6 ..] likewise for
+  // d e2; de_products below), for the lane's own sample at (t0x, t1x, t2x); both roles run it (the dW partner for every tile
   // but a workgroup's last, the chain wave itself for that one, while the dW waves write the record)
   auto pe_backward_h = [&](const h8 (&dq)[9], float t0x, float t1x, float t2x, float (&dbacc)[33]) {
     const float* Blh = reinterpret_cast<const float*>(smem + L8_BL) + 33 * h;
@@ -315,6 +316,45 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       dbacc[3 * d + 1] = fmaf(gpa[d], t1x, dbacc[3 * d + 1]);
       dbacc[3 * d + 2] = fmaf(gpa[d], t2x, dbacc[3 * d + 2]);
     }
+  };
+  // PEDW: d e2 = W_vd[e2]^T dPre(viewdir) and d e1 = W_cat[e1]^T dPre(cat) + W_xyz^T dPre(xyz) of one tile from its three dPre
+  // pairs P = {viewdir, cat, xyz} x {features 0..15, 16..31} (B operands, as the layer steps staged them), rounded to f16 into the
+  // dq of pe_backward_h.  Nothing of the chain depends on these 16 products, so they are not on the chain wave: the dW partner
+  // forms them in its filler phase (16 of the chain wave's 30 backward MFMAs, 72 of its 96 conversions and the five MFMA times
+  // at a stretch during which an in-order wave can issue nothing else).  frag(kt, i): transposed fragment kt, number i of the
+  // 16 counted VD_E 0..3, CAT_E 0..5, XYZ_E 0..5 (the partner reads it from LDS; the chain wave, behind the loop, holds all 16 in registers).
+  auto de_products = [&](const h8 (&P)[6], auto&& frag, h8 (&dq)[9]) {
+    // three rounds -- d e2, the cat half of d e1, its xyz half -- each with its fragments requested together and its blocks as
+    // independent accumulator chains: one LDS round trip and two MFMA latencies per round (block by block, which holds 16
+    // accumulator registers instead of 48, the partner came late to the exchange barrier).  Per accumulator the order of the
+    // products is the chain wave's old one (d e1: the cat pair, then the xyz pair): the same roundings, the same records bit for bit.
+    h8 wE[6];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wE[k] = frag(KT_VD_E + k, k);
+    f16v de2[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      de2[b] = MFMA(wE[2 * b + 0], P[0], zero16());
+      de2[b] = MFMA(wE[2 * b + 1], P[1], de2[b]);
+    }
+    dq[6] = pack8(de2[0], 0, false); dq[7] = pack8(de2[0], 1, false); dq[8] = pack8(de2[1], 0, false);   // (slots 48..63: no features)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wE[k] = frag(KT_CAT_E + k, 4 + k);
+    f16v de[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      de[b] = MFMA(wE[2 * b + 0], P[2], zero16());
+      de[b] = MFMA(wE[2 * b + 1], P[3], de[b]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wE[k] = frag(KT_XYZ_E + k, 10 + k);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      de[b] = MFMA(wE[2 * b + 0], P[4], de[b]);
+      de[b] = MFMA(wE[2 * b + 1], P[5], de[b]);
+    }
+#pragma unroll
+    for (int b = 0; b < 3; ++b) { dq[2 * b] = pack8(de[b], 0, false); dq[2 * b + 1] = pack8(de[b], 1, false); }
   };
 #define DBACC(i) c_dbacc[i]
 #define DWS(i) c_dws[i]
@@ -434,6 +474,9 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     float* xch = reinterpret_cast<float*>(smem + l8_xch(NCH, WIDE, GEO));   // [4][8]
     bool any_iter = false;
     float l0x = 0.f, l1x = 0.f, l2x = 0.f;   // PEDW: the last tile's sample position (its PE backward runs here, behind the loop)
+    h8 lP[6];   // PEDW: and its three dPre pairs (viewdir, cat, xyz), what d e1 / d e2 are formed from: 24 registers, live from their step
+#pragma unroll                                                           // to the end of the iteration only
+    for (int k = 0; k < 6; ++k) lP[k] = zero8();
     for (int tile = blockIdx.x * NCHW + wv, t0 = blockIdx.x * NCHW; t0 < ntiles; t0 += tile_step, tile += tile_step) {
       asm volatile("" ::: "memory");
       P8STAMP_RESET();
@@ -823,20 +866,27 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       stage_hs(Dimg0, D0, D1, col, h);
       stage_hs(Ximg0, A5a, A5b, col, h);
       P8SYNC();                   // A(T1)
-      // (the extra fragments of a step -- d e2 here, d e1 in steps CAT and S1 -- are requested at the TOP of the step, under the
-      //  packing of dPre: read in front of their products, each product waited out part of an LDS round trip)
+      // (!PEDW; PEDW: de_products, on the dW partner.  The extra fragments of a step -- d e2 here, d e1 in steps CAT and S1 -- are
+      //  requested at the TOP of the step, under the packing of dPre: read in front of their products, each product waited out
+      //  part of an LDS round trip)
       h8 wE[6];
+      if constexpr (!PEDW) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) wE[k] = lds_frag(bwf, KT_VD_E + k, lane);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 4; ++k) wE[k] = lds_frag(bwf, KT_VD_E + k, lane);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       D0 = pack8_and(acc, 0, Mn0); D1 = pack8_and(acc, 1, Mn1);
       acc = MFMA(Wn0, D0, zero16());
       acc = MFMA(Wn1, D1, acc);  // d y4 from the colour branch
       f16v de2[3];  // d e2 (two 16-slot blocks)
+      if constexpr (PEDW) {
+        lP[0] = D0; lP[1] = D1;
+      } else {
 #pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        de2[b] = MFMA(wE[2 * b + 0], D0, zero16());
-        de2[b] = MFMA(wE[2 * b + 1], D1, de2[b]);
+        for (int b = 0; b < 2; ++b) {
+          de2[b] = MFMA(wE[2 * b + 0], D0, zero16());
+          de2[b] = MFMA(wE[2 * b + 1], D1, de2[b]);
+        }
       }
       Wn0 = lds_frag(bwf, KT_ES + 0, lane); Wn1 = lds_frag(bwf, KT_ES + 1, lane);
       // ---- step VD : inputs [y4 | e2]
@@ -853,22 +903,14 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       acc = MFMA(Wn0, D0, zero16());
       acc = MFMA(Wn1, D1, acc);  // d a3
       Wn0 = lds_frag(bwf, KT_S2 + 0, lane); Wn1 = lds_frag(bwf, KT_S2 + 1, lane);
-      de2[2] = de2[1];
-      h8 de2h[3];   // PEDW: d e2 as f16, parked until the E2 image is free (after A(ES))
-      if constexpr (PEDW) {
-        de2h[0] = pack8(de2[0], 0, false); de2h[1] = pack8(de2[0], 1, false); de2h[2] = pack8(de2[1], 0, false);
-      } else {
+      if constexpr (!PEDW) {
+        de2[2] = de2[1];
         pe_backward(de2, 2, 4, 22);  // bands 4 and 5 -> dB
       }
       // ---- step ES (no activation)
       stage_hs(Dimg0, D0, D1, col, h);
       stage_hs(Ximg0, A3a, A3b, col, h);
       P8SYNC();                   // A(ES)
-      if constexpr (PEDW) {   // the dW waves have read the E2 image (step VD): it now carries d e2 to the partner, lane to lane
-        unsigned char* eq = E2img + lane * 16;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *reinterpret_cast<h8*>(eq + k * 1024) = de2h[k];
-      }
       D0 = pack8_and(acc, 0, Mn0); D1 = pack8_and(acc, 1, Mn1);
       Mn0 = relu_mask(A2a); Mn1 = relu_mask(A2b);
       acc = MFMA(Wn0, D0, zero16());
@@ -884,67 +926,72 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       acc = MFMA(Wn1, D1, acc);  // d a1
       Wn0 = lds_frag(bwf, KT_S1 + 0, lane); Wn1 = lds_frag(bwf, KT_S1 + 1, lane);
       const h8 Dc0 = D0, Dc1 = D1;  // dPre(cat): its d e1 part is formed together with encoding_xyz's
+      if constexpr (PEDW) { lP[2] = D0; lP[3] = D1; }
       nxt = fetch(tile + tile_step);  // next iteration's inputs: their latency hides under the last three steps
       // ---- step CAT : inputs [a1 | e1]
       stage_hs(Dimg0, D0, D1, col, h);
       stage_hs(Ximg0, A1a, A1b, col, h);
       P8SYNC();                   // A(CAT)
+      if constexpr (!PEDW) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) wE[k] = lds_frag(bwf, KT_CAT_E + k, lane);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 6; ++k) wE[k] = lds_frag(bwf, KT_CAT_E + k, lane);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       D0 = pack8_and(acc, 0, Mn0); D1 = pack8_and(acc, 1, Mn1);
       Mn0 = relu_mask(A0a); Mn1 = relu_mask(A0b);
       acc = MFMA(Wn0, D0, zero16());
       acc = MFMA(Wn1, D1, acc);  // d a0
       f16v de[3];
+      if constexpr (!PEDW) {
 #pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        de[b] = MFMA(wE[2 * b + 0], Dc0, zero16());
-        de[b] = MFMA(wE[2 * b + 1], Dc1, de[b]);
+        for (int b = 0; b < 3; ++b) {
+          de[b] = MFMA(wE[2 * b + 0], Dc0, zero16());
+          de[b] = MFMA(wE[2 * b + 1], Dc1, de[b]);
+        }
       }
       // ---- step S1 : input a0
       stage_hs(Dimg1, D0, D1, col, h);
       stage_hs(Ximg1, A0a, A0b, col, h);
       P8SYNC();                   // A(S1)
+      if constexpr (!PEDW) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) wE[k] = lds_frag(bwf, KT_XYZ_E + k, lane);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 6; ++k) wE[k] = lds_frag(bwf, KT_XYZ_E + k, lane);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       D0 = pack8_and(acc, 0, Mn0); D1 = pack8_and(acc, 1, Mn1);
+      if constexpr (PEDW) {
+        lP[4] = D0; lP[5] = D1;
+      } else {
 #pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        de[b] = MFMA(wE[2 * b + 0], D0, de[b]);
-        de[b] = MFMA(wE[2 * b + 1], D1, de[b]);
+        for (int b = 0; b < 3; ++b) {
+          de[b] = MFMA(wE[2 * b + 0], D0, de[b]);
+          de[b] = MFMA(wE[2 * b + 1], D1, de[b]);
+        }
       }
       // ---- step XYZ : input e1 (its image)
       stage_hs(Dimg0, D0, D1, col, h);
       P8SYNC();                   // A(XYZ)
-      if constexpr (PEDW) {
-        // d e1 -> this wave's dW partner, lane to lane, through the three slot images no step uses any more (Ximg0, Dimg1, Ximg1:
-        // 6 KB = six 16-byte pieces per lane; the dW waves read step XYZ from Dimg0 and the E1 image).  The partner picks them
-        // up behind the iteration's last barrier and has finished with them before the composite-exchange barrier of the next
-        // iteration, in front of which this wave writes none of the three.
-        unsigned char* xq = cw + K_X + lane * 16;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          *reinterpret_cast<h8*>(xq + (2 * b) * 1024) = pack8(de[b], 0, false);
-          *reinterpret_cast<h8*>(xq + (2 * b + 1) * 1024) = pack8(de[b], 1, false);
-        }
-      } else {
-        pe_backward(de, 3, 0, 44);        // d e1 -> dB, bands 0..3
-      }
+      if constexpr (!PEDW) pe_backward(de, 3, 0, 44);        // d e1 -> dB, bands 0..3
       cur = nxt;
       any_iter = true;   // the barrier "dW waves are done with this tile's images" follows at the next iteration's image
     }                    // writes (below the PE arithmetic, which so runs beside the dW waves' last step), or here:
     P8PHASE(3);
+    // PEDW, the workgroup's last tile: its d e1 / d e2 and PE backward run here, beside the dW waves' record writing.  The record
+    // image lies over the transposed fragments (REC_IMG), and the dW waves start on it behind the barrier below: the 16 fragments
+    // are taken into registers in front of it (64 registers, free behind the loop; this wave waits there for step XYZ anyway).
+    h8 lW[PEDW ? 16 : 1];
+    if constexpr (PEDW) {
+      if (any_iter) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) lW[k] = lds_frag(bwf, k < 4 ? KT_VD_E + k : k < 10 ? KT_CAT_E + (k - 4) : KT_XYZ_E + (k - 10), lane);
+      }
+    }
     if (any_iter) role_barrier();
     P8PHASE(4);
     if constexpr (PEDW) {
-      if (any_iter) {   // the workgroup's last tile: its d e1 / d e2 are still where this wave put them
+      if (any_iter) {
         h8 dq[9];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dq[k] = *reinterpret_cast<const h8*>(cw + K_X + lane * 16 + k * 1024);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dq[6 + k] = *reinterpret_cast<const h8*>(E2img + lane * 16 + k * 1024);
+        de_products(lP, [&](int, int i) { return lW[i]; }, dq);
         pe_backward_h(dq, l0x, l1x, l2x, c_dbacc);
       }
     }
@@ -982,7 +1029,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     }
   } else {
     // ===================================================================================================
-    // dW role: 8 accumulator blocks per wave, six tiles per step
+    // dW role: at most 5 accumulator blocks per wave, four tiles per step
     // ===================================================================================================
     copy_operands([]() {});
     if constexpr (SPLIT_COPY) copy_transposed();
@@ -1017,21 +1064,23 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     // the consumer every layer step waits for (measured: -2 % at 2048 x 64, -5 % at 8192 x 128; the reverse: no effect)
     // (raised BEHIND the record-index setup below: those ~1 000 instructions run beside the chain waves' first forward and must
     //  not take issue slots from it)
-    int bi0[NACC], bst[NACC], r2i0 = -1, r2st = 0;
+    // (kept across the loop as ONE register per block, (i0 + 1) | st << 16 -- i0 + 1 <= REC_ENTRIES < 2^16, 0 <= st < 2^15: the
+    //  filler phase of the loop, with the d e1 / d e2 products, is where this role's registers run out)
+    int bix[NACC], r2ix = 0;
 #pragma unroll
-    for (int i = 0; i < NACC; ++i) { bi0[i] = -1; bst[i] = 0; }
+    for (int i = 0; i < NACC; ++i) bix[i] = 0;
+    auto pack_idx = [&](int kind) {
+      const int i0 = block_index(kind, 0, col);
+      return (i0 + 1) | ((block_index(kind, 1, col) - i0) << 16);
+    };
 #define CNR_PIDX8(KIND)                                                                        \
-  if (owner8<NDW>(KIND) == dwid) {                                                             \
-    constexpr int li = local8<NDW>(KIND);                                                      \
-    bi0[li] = block_index(KIND, 0, col);                                                       \
-    bst[li] = block_index(KIND, 1, col) - bi0[li];                                             \
-  }
+  if (owner8<NDW>(KIND) == dwid) bix[local8<NDW>(KIND)] = pack_idx(KIND);
     CNR_PIDX8(BK_R0) CNR_PIDX8(BK_T1) CNR_PIDX8(BK_VD_Y) CNR_PIDX8(BK_VD_E0) CNR_PIDX8(BK_VD_E1) CNR_PIDX8(BK_ES)
     CNR_PIDX8(BK_S2) CNR_PIDX8(BK_CAT_Y) CNR_PIDX8(BK_CAT_E0) CNR_PIDX8(BK_CAT_E1) CNR_PIDX8(BK_CAT_E2) CNR_PIDX8(BK_S1)
     CNR_PIDX8(BK_XYZ_E0) CNR_PIDX8(BK_XYZ_E1) CNR_PIDX8(BK_XYZ_E2)
 #undef CNR_PIDX8
-    if (owner8<NDW>(BK_R0) == dwid) { r2i0 = block_index(BK_R2, 0, col); r2st = block_index(BK_R2, 1, col) - r2i0; }
-    asm volatile("" : "+v"(r2i0));               // (keeps the raise below the setup)
+    if (owner8<NDW>(BK_R0) == dwid) r2ix = pack_idx(BK_R2);
+    asm volatile("" : "+v"(r2ix));               // (keeps the raise below the setup)
     __builtin_amdgcn_s_setprio(3);
     // The role branches on the dW wave's index ONCE, around the whole iteration loop: with the branch inside every layer step
     // the accumulator blocks met at a join after each step, and the compiler copied them between register ranges there (16
@@ -1078,9 +1127,10 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
       asm volatile("" ::: "memory");
       P8STAMP_RESET();
       P8STAMP();
-      // one layer step over the six tiles; KIND* = the block kinds of the step (X source: 0 = slot X image,
+      // one layer step over the four tiles; KIND* = the block kinds of the step (X source: 0 = slot X image,
       // 1 = E2 image, 2 = E1 image; col0 = first feature column), RS_GRP >= 0: row sums of the step (dW0)
-      auto consume = [&](auto dw_c, auto nx_c, auto k0_c, auto k1_c, auto k2_c, auto k3_c, auto grp_c, auto par_c) {
+      // (behind_reads(): further LDS reads of the step, issued behind the step's own and in front of its first MFMA)
+      auto consume = [&](auto dw_c, auto nx_c, auto k0_c, auto k1_c, auto k2_c, auto k3_c, auto grp_c, auto par_c, auto&& behind_reads) {
         constexpr int DW = decltype(dw_c)::value, NX = decltype(nx_c)::value, RS_GRP = decltype(grp_c)::value;
         constexpr int PAR = decltype(par_c)::value * K_PAR;   // which copy of the dPre / input images the step uses
         constexpr int K0 = decltype(k0_c)::value, K1 = decltype(k1_c)::value, K2 = decltype(k2_c)::value,
@@ -1091,7 +1141,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
                        OWN2 = NX > 2 && owner8<NDW>(K2) == DW, OWN3 = NX > 3 && owner8<NDW>(K3) == DW;
         constexpr int SL0 = 0, SL1 = OWN0, SL2 = OWN0 + OWN1, SL3 = OWN0 + OWN1 + OWN2;
         constexpr bool DO_RS = RS_GRP >= 0 && DW == owner8<NDW>(BK_RS);
-        if constexpr (!(OWN0 || OWN1 || OWN2 || OWN3 || DO_RS)) return;
+        if constexpr (!(OWN0 || OWN1 || OWN2 || OWN3 || DO_RS)) { behind_reads(); return; }
         // at most two owned blocks per wave and step; DEPTH tiles in flight (transposing reads are convergent: the
         // compiler keeps them in source order, so the lookahead is spelled out): all four, the registers are there
         constexpr int DEPTH = NCHW;
@@ -1110,6 +1160,11 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
           a_e2[pr] = p_e2 + PAIR_OFF[pr]; a_r[pr] = p_r + PAIR_OFF[pr];
           asm volatile("" : "+v"(a_lo[pr]), "+v"(a_hi[pr]), "+v"(a_e1[pr]), "+v"(a_e2[pr]), "+v"(a_r[pr]));
         }
+        // (likewise the lane's column for the ones rows of the per-tile row sums: from the plain lane index the 18 row masks of the
+        //  nine steps are loop invariants, and the compiler kept them in registers across the loop -- with the partner's dPre pairs
+        //  beside them the row-sum owner spilled 26 registers per iteration)
+        int col_step = col;
+        if constexpr (DO_RS && ROWTILE) asm volatile("" : "+v"(col_step));
         // (w: chain wave of the image, off: the image's offset inside that wave's region)
         auto rd_hs = [&](int w, int off, int sl) {   // = tr_frag_hs(image, sl, lane)
           typedef __attribute__((address_space(3))) s4v* lds_s4;
@@ -1165,6 +1220,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
         };
 #pragma unroll
         for (int w = 0; w < NCHW; ++w) load_tile(w);
+        behind_reads();
         // every read of the step is in flight before the first MFMA: left alone, the scheduler sinks the later tiles' reads
         // between the MFMAs (fewer live registers, which this role has to spare) and the wave then waits out one LDS
         // latency per tile instead of one per step
@@ -1178,7 +1234,7 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
           if constexpr (DO_RS && ROWTILE) {
             // the tile is one ray = one object: row 4 w + slot (latent layers) or 16 / 17 (plain biases) takes the column sum
             const int mrow = RS_GRP < 4 ? 4 * w + RS_GRP : 16 + (RS_GRP - 4);
-            const unsigned int on = col == mrow ? 0x3c003c00u : 0u;     // f16 ones
+            const unsigned int on = col_step == mrow ? 0x3c003c00u : 0u;     // f16 ones
             const h8 ones = __builtin_bit_cast(h8, (u4v){on, on, on, on});
             Wacc[LI_RS] = MFMA(ones, fD[w % DEPTH][0], Wacc[LI_RS]);
             Wacc[LI_RS] = MFMA(ones, fD[w % DEPTH][1], Wacc[LI_RS]);
@@ -1193,25 +1249,33 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
         }
       };
       if constexpr (KR > 1) { P8SYNC(); }   // the chain waves' composite exchange
-#define STEP8(PAR, NX, K0, K1, K2, K3, GRP)                                                                   \
+      // PEDW: the partner tile's three dPre pairs (viewdir, cat, xyz), taken back out of chain wave DWI's dPre image as the B operands
+      // the chain wave staged (unstage_hs): in steps VD and CAT, whether or not this wave owns a block of the step, and kept to the
+      // filler phase behind the iteration's last barrier, where d e1 / d e2 are formed from them (de_products); step XYZ's pair only
+      // there (its image outlives the iteration, and step XYZ is where this role's registers run out).  Each image is complete
+      // behind its step's barrier.  The chain wave rewrites Dimg1 (step VD's) only behind A(ES), and Dimg0 (steps CAT and XYZ) only
+      // behind A(S1) and again behind the next iteration's exchange barrier: this wave arrives at each of those barriers after its
+      // reads (a barrier here waits for the wave's outstanding LDS reads; the filler phase ends in front of the exchange barrier).
+      h8 pP[PEDW ? 6 : 1];
+      auto take_pair = [&](int img_off, int k) {
+        if constexpr (PEDW) unstage_hs(pcw + img_off, pP[PEDW ? k : 0], pP[PEDW ? k + 1 : 0], col, h);
+      };
+#define STEP8P(PAR, NX, K0, K1, K2, K3, GRP, BEHIND)                                                          \
   P8SYNC();                                                                                             \
-  consume(IC<DWI>{}, IC<NX>{}, IC<K0>{}, IC<K1>{}, IC<K2>{}, IC<K3>{}, IC<GRP>{}, IC<PAR>{});
+  consume(IC<DWI>{}, IC<NX>{}, IC<K0>{}, IC<K1>{}, IC<K2>{}, IC<K3>{}, IC<GRP>{}, IC<PAR>{}, BEHIND);
+#define STEP8(PAR, NX, K0, K1, K2, K3, GRP) STEP8P(PAR, NX, K0, K1, K2, K3, GRP, []() {})
       STEP8(0, 1, BK_R0, BK_R0, BK_R0, BK_R0, -1)                            // rgb.2 (rows 16..18 of rgb.0's block)
       STEP8(1, 1, BK_R0, BK_R0, BK_R0, BK_R0, 5)                             // rgb.0
       STEP8(0, 1, BK_T1, BK_T1, BK_T1, BK_T1, 3)                             // texture_layer_1
-      STEP8(1, 3, BK_VD_Y, BK_VD_E0, BK_VD_E1, BK_VD_E1, -1)                 // encoding_viewdir
+      STEP8P(1, 3, BK_VD_Y, BK_VD_E0, BK_VD_E1, BK_VD_E1, -1, [&]() { take_pair(K_D + K_PAR, 0); })   // encoding_viewdir
       STEP8(0, 1, BK_ES, BK_ES, BK_ES, BK_ES, 4)                             // encoding_shape
       STEP8(1, 1, BK_S2, BK_S2, BK_S2, BK_S2, 2)                             // shape_layer_2
-      STEP8(0, 4, BK_CAT_Y, BK_CAT_E0, BK_CAT_E1, BK_CAT_E2, 1)              // cat_layer
+      STEP8P(0, 4, BK_CAT_Y, BK_CAT_E0, BK_CAT_E1, BK_CAT_E2, 1, [&]() { take_pair(K_D, 2); })       // cat_layer
       STEP8(1, 1, BK_S1, BK_S1, BK_S1, BK_S1, 0)                             // shape_layer_1
       STEP8(0, 3, BK_XYZ_E0, BK_XYZ_E1, BK_XYZ_E2, BK_XYZ_E2, -1)            // encoding_xyz
-      h8 dq[PEDW ? 9 : 1];
-      if constexpr (PEDW) {   // d e2 (in the E2 image since step ES): picked up BEFORE the barrier behind which the partner writes the next tile's E2 features
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dq[6 + k] = *reinterpret_cast<const h8*>(pcw + K_E2 + lane * 16 + k * 1024);
-      }
       P8SYNC();   // done with this iteration's images (the chain waves wait for it before they write the next ones)
 #undef STEP8
+#undef STEP8P
       if constexpr (RS_FLUSH) {
         // rows 0..15 of the row-sum block = (chain wave, latent slot) column sums of THIS iteration's tiles -> the fixed-point table
         // at the tiles' object rows; this lane half holds rows 4 h + 0..3 (registers 0..3: chain wave h) and 8 + 4 h + 0..3
@@ -1231,16 +1295,17 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
         for (int w = 0; w < 4; ++w) orow[w] = nrow[w];
       }
       if constexpr (PEDW) {
-        // d e1 (written by the partner between step XYZ's barrier and the one above).  The workgroup's last tile is left to the
-        // chain wave: behind the loop this wave has the record to write (~10 k cycles, the longer pole) and the chain wave nothing
+        // The workgroup's last tile is left to the chain wave: behind the loop this wave has the record to write (~10 k cycles,
+        // the longer pole) and the chain wave nothing
         if (t0 + tile_step < ntiles) {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) dq[k] = *reinterpret_cast<const h8*>(pcw + K_X + lane * 16 + k * 1024);
           // filler work: below the chain wave (priority 1) while it lasts, so that it takes only issue slots the partner's forward
           // leaves empty (at the dW role's priority 3 it pushed the forward back: 40.4 -> 42.0 us at 2048 x 64)
           __builtin_amdgcn_s_setprio(0);
           float n0x = 0.f, n1x = 0.f, n2x = 0.f;
           pts_of(t0 + tile_step + DWI, n0x, n1x, n2x);
+          h8 dq[9];
+          take_pair(K_D, 4);
+          de_products(pP, [&](int kt, int) { return lds_frag(bwf, kt, lane); }, dq);
           pe_backward_h(dq, p0 * inv_scale, p1 * inv_scale, p2 * inv_scale, w_dbacc);
           p0 = n0x; p1 = n1x; p2 = n2x;
           __builtin_amdgcn_s_setprio(3);
@@ -1255,6 +1320,10 @@ __global__ __launch_bounds__((NCH + NDW) * 64, 1) void field_bwd_pipe8_kernel(
     P8PHASE(3);
     // ---- this wave's blocks -> the record image in LDS, straight from the accumulators (same indices as in the record) ----
     rec_t* img = reinterpret_cast<rec_t*>(smem + REC_IMG);
+    int bi0[NACC], bst[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) { bi0[i] = (bix[i] & 0xffff) - 1; bst[i] = bix[i] >> 16; }
+    const int r2i0 = (r2ix & 0xffff) - 1, r2st = r2ix >> 16;
 #define CNR_PSTORE8(KIND, NROWS)                                                               \
   if (owner8<NDW>(KIND) == dwid) {                                                             \
     constexpr int li = local8<NDW>(KIND);                                                      \
