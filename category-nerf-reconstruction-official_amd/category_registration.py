@@ -689,17 +689,42 @@ def write_registration_result(inst_dict, path):
         _RegistrationPickler.dump(inst_dict, f)
 
 
-def register_dataset(dataset, cfg, solver=None, tsdf=False):
+def pretrain_fields(dataset, cfg, iters, boxes, encoders, fields, rays_per_step=None, seed=0):
+    """The fields ``get_uncertainty_fields`` probes, trained here instead of loaded: every instance's OccupancyMap(32) +
+    UniDirsEmbed for ``iters`` steps (object_fields.ObjectFieldTrainer, all objects per launch), written under
+    ``cfg.weight_root/ckpt`` when that is set, and filled into the three dicts the way ``load_pretrained_fields`` fills them
+    (``bbox`` = the oriented box of the instance's cloud).  -> the trainer"""
+    from .object_fields import ObjectFieldTrainer
+    from .utils import get_bound
+    tr = ObjectFieldTrainer.from_dataset(dataset, cfg, rays_per_step=rays_per_step, seed=seed)
+    tr.run(int(iters))
+    for cls_id, entries in dataset.inst_dict.items():
+        if cls_id == 0:
+            continue
+        for obj_id, entry in entries.items():
+            pe, fc = tr.modules(obj_id)
+            boxes.setdefault(cls_id, {})[obj_id] = get_bound(entry["pcs"]) if entry.get("pcs") is not None else None
+            encoders.setdefault(cls_id, {})[obj_id] = pe.to(cfg.data_device)
+            fields.setdefault(cls_id, {})[obj_id] = fc.to(cfg.data_device)
+    if getattr(cfg, "weight_root", None):
+        tr.save_checkpoints(cfg.weight_root, {o: b for per_cls in boxes.values() for o, b in per_cls.items()})
+    return tr
+
+
+def register_dataset(dataset, cfg, solver=None, tsdf=False, pretrain=None, rays_per_step=None):
     """src/dataset.py:72-88 for a dataset whose frames are loaded: get_all_poses -> get_uncertainty_fields -> align_poses, the
     'pcs' entries deleted, the result written to <root_dir>/inst_dict.pkl.  A ScanNet dataset needs tsdf=True, here and when it
-    was loaded (get_dataset(cfg, register=True, tsdf=True): the loader gathers the objects' clouds only then)."""
+    was loaded (get_dataset(cfg, register=True, tsdf=True): the loader gathers the objects' clouds only then).
+    ``pretrain``: with registration.load_pretrained false, train the per-object fields for that many steps (``rays_per_step``
+    rays each, default cfg.n_per_optim) instead of loading them (pretrain_fields); without it that case raises, as before."""
     if dataset.name != "replica" and not tsdf:
         raise NotImplementedError("registration of ScanNet sequences (TSDF fusion of the background, objects from refined "
                                   "masks on disk) runs only on request: tsdf=True")
     if dataset.name != "replica" and not getattr(dataset, "_accumulate", False):
         raise ValueError("register_dataset(tsdf=True): the ScanNet dataset was loaded without the objects' clouds; load it with "
                          "get_dataset(cfg, register=True, tsdf=True)")
-    if not getattr(cfg, "load_pretrained", False):
+    load_pretrained = bool(getattr(cfg, "load_pretrained", False))
+    if not load_pretrained and pretrain is None:
         raise NotImplementedError("get_uncertainty_fields: registration.load_pretrained is false; only per-object checkpoints "
                                   "under registration.weight_root give the fields that rank a class's instances (the "
                                   "reference registers nothing in this case, without saying so)")
@@ -707,7 +732,9 @@ def register_dataset(dataset, cfg, solver=None, tsdf=False):
     boxes, counts, encoders, fields = {}, {}, {}, {}
     get_all_poses(inst_dict, dataset.sample_dict, dataset.intrinsic_open3d, name=dataset.name, depth_scale=cfg.depth_scale,
                   max_depth=cfg.max_depth, tsdf=tsdf)
-    get_uncertainty_fields(inst_dict, boxes, counts, encoders, fields, cfg, name=dataset.name, load_pretrained=True)
+    if not load_pretrained:
+        pretrain_fields(dataset, cfg, pretrain, boxes, encoders, fields, rays_per_step=rays_per_step)
+    get_uncertainty_fields(inst_dict, boxes, counts, encoders, fields, cfg, name=dataset.name, load_pretrained=load_pretrained)
     etas = {k: getattr(cfg, k) for k in ("eta1", "eta2", "eta3") if hasattr(cfg, k)}
     align_poses(inst_dict, boxes, counts, encoders, fields, name=dataset.name,
                 multi_init_pose=getattr(cfg, "multi_init_pose", True), device=dataset._parse_device(), solver=solver, **etas)

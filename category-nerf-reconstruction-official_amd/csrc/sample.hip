@@ -102,25 +102,9 @@ __global__ __launch_bounds__(256) void epoch_perm_kernel(int* __restrict__ perm,
   if (state_cursor && blockIdx.x == 0 && c == 0 && threadIdx.x == 0) state_cursor[0] = cursor0;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  uint32_t k0[4], k1[4];
-  const uint64_t gc = (uint64_t)(class_ids ? class_ids[c] : c);
-  cnr_sample::philox4(seed ^ 0x5851F42D4C957F2Dull, epoch, gc * 2 + 0, k0);
-  cnr_sample::philox4(seed ^ 0x5851F42D4C957F2Dull, epoch, gc * 2 + 1, k1);
-  const uint32_t key[6] = {k0[0], k0[1], k0[2], k0[3], k1[0], k1[1]};
-  const uint32_t mask = (1u << half_bits) - 1u;
-  uint32_t x = (uint32_t)i;
-  do {
-    uint32_t l = x >> half_bits, r = x & mask;
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      uint32_t f = (r ^ key[t]) * 0x9E3779B1u;
-      f ^= f >> 15; f *= 0x85EBCA77u; f ^= f >> 13;
-      const uint32_t nl = r;
-      r = (l ^ f) & mask;
-      l = nl;
-    }
-    x = (l << half_bits) | r;
-  } while ((int64_t)x >= n);
+  uint32_t key[6];
+  cnr_sample::epoch_perm_keys(seed, epoch, (uint64_t)(class_ids ? class_ids[c] : c), key);
+  const uint32_t x = cnr_sample::epoch_perm_at(key, (uint32_t)i, n, half_bits);
   perm[(size_t)c * n + i] = (int)x;
 }
 __global__ void advance_kernel(int64_t* state, int64_t add_rows) {
@@ -140,10 +124,8 @@ extern "C" int cnr_step_advance(int64_t* d_state, int64_t add_rows, void* stream
 extern "C" int cnr_epoch_perm(int* perm, int64_t pool_rows, int C, uint64_t seed, uint64_t epoch, const int* class_ids,
                               int64_t* state_cursor, int64_t cursor0, void* stream) {
   if (!perm || pool_rows <= 0 || pool_rows > (1ll << 30) || C <= 0) return CNR_E_ARG;
-  int bits = 2;
-  while ((1ll << bits) < pool_rows) bits += 2;           // even: two halves of bits / 2
   hipLaunchKernelGGL(epoch_perm_kernel, dim3((unsigned)((pool_rows + 255) / 256), (unsigned)C), dim3(256), 0, (hipStream_t)stream,
-                     perm, pool_rows, bits / 2, seed, epoch, class_ids, state_cursor, cursor0);
+                     perm, pool_rows, cnr_sample::epoch_perm_half_bits(pool_rows), seed, epoch, class_ids, state_cursor, cursor0);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }

@@ -142,8 +142,28 @@ __device__ __forceinline__ float uniform_draw(uint64_t seed, uint64_t rng_ray, u
   philox4(seed, rng_ray * 64 + lane, offset + 1 + (s0 >> 6), rnd);
   return u01(rnd[0]);
 }
+// Column s's z with every product and sum rounded on its own -- no fused multiply-add, except inside linspace01, where ATen's
+// linspace fuses too: the reference's CPU arithmetic (stratified_bins, normal_bins_sampling) bit for bit.  write_samples<true>
+// (cnr_obj_train, whose z is held to the reference's exactly); the default keeps the contracted expressions below, whose bits the
+// other launches are tested to share.
+__device__ __forceinline__ float z_unfused(int s, int S, int n1, int n2, float d, bool invalid, bool this_obj, float mb, float gsel,
+                                           float uu, float eps, float stop_eps, float min_bound) {
+#pragma clang fp contract(off)
+  if (invalid) {
+    const float range = mb - min_bound;
+    return (range * linspace01(s, S) + min_bound) + uu * (range / (float)S);
+  }
+  if (s < n1) {
+    const float range = (d - eps) - min_bound;
+    return (range * linspace01(s, n1) + min_bound) + uu * (range / (float)n1);
+  }
+  if (this_obj) return d + gsel;
+  const float lo = d - eps, range = (d + stop_eps) - lo;
+  return (range * linspace01(s - n1, n2) + lo) + uu * (range / (float)n2);
+}
 // a3/a5: per-column z and the sample points of one ray (depth d, slice maximum mb, sorted draws g0 / g1 of "this object" rays)
 // (have_uu0: uu0 is this lane's uniform draw of the first 64 columns, drawn by the caller ahead of its loads)
+template <bool UNFUSED = false>
 __device__ __forceinline__ void write_samples(const SampleArgs& a, int64_t ray, int lane, const RayFrame& f, float d, bool invalid,
                                               bool this_obj, float mb, float g0, float g1, uint64_t rng_ray, uint64_t offset,
                                               bool have_uu0 = false, float uu0 = 0.0f) {
@@ -168,7 +188,9 @@ __device__ __forceinline__ void write_samples(const SampleArgs& a, int64_t ray, 
     const int isrc = i < 0 ? 0 : i;
     const float ga = __shfl(g0, isrc & 63, 64), gb = __shfl(g1, isrc & 63, 64);
     float zz;
-    if (invalid) {
+    if constexpr (UNFUSED) {
+      zz = z_unfused(s, S, n1, n2, d, invalid, this_obj, mb, isrc < 64 ? ga : gb, uu, eps, stop_eps, min_bound);
+    } else if (invalid) {
       // stratified(min_bound, max_bound, n1+n2)
       const float range = mb - min_bound;
       zz = (range * linspace01(s, S) + min_bound) + uu * (range / (float)S);
@@ -195,30 +217,52 @@ __device__ __forceinline__ uint64_t rng_index(const SampleArgs& a, int c, int64_
                      : (uint64_t)ray;
 }
 
-// one wavefront, one ray (ray < C * R)
-__device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int lane) {
+// ---- the keyed bijection of the epoch shuffle (cnr_epoch_perm, and cnr_obj_train, which evaluates it per row in its kernel):
+// a 6-round balanced Feistel network on 2 * half_bits bits, round keys from Philox4x32 of (seed, epoch, id), cycle-walked back
+// into [0, n) (a value >= n is encrypted again: the domain is < 4 n, so at most four expected trips)
+__device__ __forceinline__ void epoch_perm_keys(uint64_t seed, uint64_t epoch, uint64_t id, uint32_t (&key)[6]) {
+  uint32_t k0[4], k1[4];
+  philox4(seed ^ 0x5851F42D4C957F2Dull, epoch, id * 2 + 0, k0);
+  philox4(seed ^ 0x5851F42D4C957F2Dull, epoch, id * 2 + 1, k1);
+  key[0] = k0[0]; key[1] = k0[1]; key[2] = k0[2]; key[3] = k0[3]; key[4] = k1[0]; key[5] = k1[1];
+}
+// half the bits of the next even power of two at or above n
+__host__ __device__ inline int epoch_perm_half_bits(int64_t n) {
+  int bits = 2;
+  while ((1ll << bits) < n) bits += 2;
+  return bits / 2;
+}
+__device__ __forceinline__ uint32_t epoch_perm_at(const uint32_t (&key)[6], uint32_t i, int64_t n, int half_bits) {
+  const uint32_t mask = (1u << half_bits) - 1u;
+  uint32_t x = i;
+  do {
+    uint32_t l = x >> half_bits, r = x & mask;
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      uint32_t f = (r ^ key[t]) * 0x9E3779B1u;
+      f ^= f >> 15; f *= 0x85EBCA77u; f ^= f >> 13;
+      const uint32_t nl = r;
+      r = (l ^ f) & mask;
+      l = nl;
+    }
+    x = (l << half_bits) | r;
+  } while ((int64_t)x >= n);
+  return x;
+}
+
+// one wavefront, one ray whose pool row, Philox index and offset, and slice maximum the caller has worked out: outputs at index
+// `ray`, inputs at row `prow` (c: the ray's class, for ray_row only)
+template <bool UNFUSED = false>
+__device__ __forceinline__ void sample_ray_at(const SampleArgs& a, int64_t ray, int64_t prow, int c, uint64_t rng_ray,
+                                              uint64_t offset, float mb, int lane) {
   const uint8_t* __restrict__ rgbs = a.rgbs; const float* __restrict__ depth = a.depth;
   const float* __restrict__ dirs_c = a.dirs_c; const float* __restrict__ T = a.T;
   const float* __restrict__ g = a.g;
-  const uint64_t seed = a.seed; uint64_t offset = a.offset;
-  const int64_t* __restrict__ d_state = a.d_state; const int64_t pool_rows = a.pool_rows;
-  const float* __restrict__ max_bound = a.max_bound;
-  const int R = a.R, n2 = a.n2; const float eps = a.eps, min_bound = a.min_bound;
+  const int n2 = a.n2; const float eps = a.eps, min_bound = a.min_bound;
   float* __restrict__ origins = a.origins;
   float* __restrict__ dirs_o = a.dirs_o; float* __restrict__ gt_rgb = a.gt_rgb; float* __restrict__ gt_depth = a.gt_depth;
   uint8_t* __restrict__ depth_mask = a.depth_mask; uint8_t* __restrict__ labels = a.labels;
   const int64_t* __restrict__ pool_indices = a.pool_indices; const int n_obj = a.n_obj; int* __restrict__ ray_row = a.ray_row;
-  const int* __restrict__ perm = a.perm;
-  const int c = (int)(ray / R);
-  const uint64_t rng_ray = rng_index(a, c, ray);
-  // pool row of this ray: either the slice itself (pool_rows == 0) or row cursor + r of a device-resident
-  // (C, pool_rows, ...) pool whose cursor lives on the device (hipGraph replay advances it, no host work)
-  int64_t prow = ray;
-  if (pool_rows > 0) {
-    prow = (int64_t)c * pool_rows + d_state[0] + (ray - (int64_t)c * R);
-    if (perm) prow = (int64_t)c * pool_rows + perm[prow];   // epoch shuffle = a new permutation, the pool stays put
-    offset += (uint64_t)d_state[1] * 4;
-  }
 
   const float* Tm = T + prow * 16;
   const float m[12] = {Tm[0], Tm[1], Tm[2], Tm[3], Tm[4], Tm[5], Tm[6], Tm[7], Tm[8], Tm[9], Tm[10], Tm[11]};
@@ -245,12 +289,32 @@ __device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int
       if (lane < n2) g0 = g[ray * n2 + lane];
       if (lane + 64 < n2) g1 = g[ray * n2 + lane + 64];
     } else {
-      gauss_draws(seed, rng_ray, offset, eps, n2, lane, g0, g1);
+      gauss_draws(a.seed, rng_ray, offset, eps, n2, lane, g0, g1);
     }
     sort_clip(g0, g1, n2, eps, lane);
   }
-
   // ---- a3/a5: per-column z -------------------------------------------------------------------
+  write_samples<UNFUSED>(a, ray, lane, f, d, invalid, this_obj, mb, g0, g1, rng_ray, offset);
+}
+
+// one wavefront, one ray (ray < C * R)
+__device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int lane) {
+  const float* __restrict__ depth = a.depth;
+  uint64_t offset = a.offset;
+  const int64_t* __restrict__ d_state = a.d_state; const int64_t pool_rows = a.pool_rows;
+  const float* __restrict__ max_bound = a.max_bound;
+  const int R = a.R;
+  const int* __restrict__ perm = a.perm;
+  const int c = (int)(ray / R);
+  const uint64_t rng_ray = rng_index(a, c, ray);
+  // pool row of this ray: either the slice itself (pool_rows == 0) or row cursor + r of a device-resident
+  // (C, pool_rows, ...) pool whose cursor lives on the device (hipGraph replay advances it, no host work)
+  int64_t prow = ray;
+  if (pool_rows > 0) {
+    prow = (int64_t)c * pool_rows + d_state[0] + (ray - (int64_t)c * R);
+    if (perm) prow = (int64_t)c * pool_rows + perm[prow];   // epoch shuffle = a new permutation, the pool stays put
+    offset += (uint64_t)d_state[1] * 4;
+  }
   float mb;
   if (max_bound) mb = a.mb_slices > 1 ? max_bound[(int64_t)c * a.mb_slices + (int)(d_state[0] / R)] : max_bound[c];
   else {  // max depth of this step's slice of class c, by this wave (same value as cnr_sample_maxdepth: max is exact)
@@ -260,7 +324,7 @@ __device__ __forceinline__ void sample_ray(const SampleArgs& a, int64_t ray, int
       mx = fmaxf(mx, depth[perm ? (int64_t)c * pool_rows + perm[base + r] : base + r]);
     mb = cnr::wave_max(mx);
   }
-  write_samples(a, ray, lane, f, d, invalid, this_obj, mb, g0, g1, rng_ray, offset);
+  sample_ray_at(a, ray, prow, c, rng_ray, offset, mb, lane);
 }
 
 // sample_ray for a ray of a device-resident pool (pool_rows > 0, max_bound given, Philox draws: u = g = NULL, T 16-byte and rgbs

@@ -28,16 +28,18 @@ BATCH = 16                  # frames per upload
 DECODE_WORKERS = 16
 
 
-def get_dataset(cfg, register=False, tsdf=False, refine=False):
+def get_dataset(cfg, register=False, tsdf=False, refine=False, pretrain=None, rays_per_step=None):
     """register=True: a Replica dataset without a usable cache runs category registration (category_registration.
     register_dataset) and writes <dataset_dir>/inst_dict.pkl; the default raises NotImplementedError there, as before.
     A ScanNet dataset does so only with tsdf=True as well (its background cloud is a TSDF fusion).
     refine=True: a ScanNet frame that wants a refined mask (use_refined_mask) and has none on disk gets one computed and written
-    (src/dataset.py:358-366); the default raises NotImplementedError there, as before."""
+    (src/dataset.py:358-366); the default raises NotImplementedError there, as before.
+    pretrain=ITERS: with registration.load_pretrained false, registration trains the per-object fields it probes for ITERS steps
+    of rays_per_step rays (default cfg.n_per_optim) instead of raising (object_fields.ObjectFieldTrainer)."""
     if cfg.dataset_format == "Replica":
-        return Replica(cfg, register=register)
+        return Replica(cfg, register=register, pretrain=pretrain, rays_per_step=rays_per_step)
     if cfg.dataset_format == "ScanNet":
-        return ScanNet(cfg, register=register, tsdf=tsdf, refine=refine)
+        return ScanNet(cfg, register=register, tsdf=tsdf, refine=refine, pretrain=pretrain, rays_per_step=rays_per_step)
     raise ValueError("Dataset format {} not found".format(cfg.dataset_format))
 
 
@@ -101,17 +103,20 @@ def _has_cache(root_dir, cfg):
 
 def _load_inst_dict(dataset, cfg):
     register = getattr(dataset, "register", False)
+    pre = {}                   # (only when asked for: a registration without pretrain is called exactly as before)
+    if getattr(dataset, "pretrain", None) is not None:
+        pre = dict(pretrain=dataset.pretrain, rays_per_step=getattr(dataset, "rays_per_step", None))
     result_file = os.path.join(dataset.root_dir, "inst_dict.pkl")
     if _has_cache(dataset.root_dir, cfg):
         dataset.inst_dict = load_registration_result(result_file)
         return
     if register and dataset.name == "replica":
         from . import category_registration
-        category_registration.register_dataset(dataset, cfg)
+        category_registration.register_dataset(dataset, cfg, **pre)
         return
     if register and getattr(dataset, "tsdf", False):
         from . import category_registration
-        category_registration.register_dataset(dataset, cfg, tsdf=True)
+        category_registration.register_dataset(dataset, cfg, tsdf=True, **pre)
         return
     if dataset.name == "replica":
         raise NotImplementedError(
@@ -253,9 +258,9 @@ class _Base:
 
 
 class Replica(_Base):
-    def __init__(self, cfg, register=False):
+    def __init__(self, cfg, register=False, pretrain=None, rays_per_step=None):
         self.name = "replica"
-        self.register = register
+        self.register, self.pretrain, self.rays_per_step = register, pretrain, rays_per_step
         self.device = cfg.data_device
         self.root_dir = cfg.dataset_dir
         self.Twc = np.loadtxt(os.path.join(self.root_dir, "traj_w_c.txt"), delimiter=" ").reshape([-1, 4, 4])
@@ -329,9 +334,10 @@ def _sorted_by_stem(pattern):
 
 
 class ScanNet(_Base):
-    def __init__(self, cfg, register=False, tsdf=False, refine=False):
+    def __init__(self, cfg, register=False, tsdf=False, refine=False, pretrain=None, rays_per_step=None):
         self.name = "scannet"
         self.register, self.tsdf, self.refine = register, tsdf, refine
+        self.pretrain, self.rays_per_step = pretrain, rays_per_step
         # the objects' clouds are gathered frame by frame (src/dataset.py:385-400) only when registration is going to run
         self._accumulate = bool(register and tsdf) and not _has_cache(cfg.dataset_dir, cfg)
         self._frame_objects = {}

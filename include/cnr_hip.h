@@ -1070,6 +1070,40 @@ int cnr_refine_vote(const uint8_t* filled, const int* inst, const int* obj_ids, 
 int cnr_refine_apply(const uint8_t* filled, const int* counts, const int* obj_ids, int K, int O, int H, int W, double threshold,
                      int* chosen, int* refined, void* stream);
 
+/* ---- registration's per-object fields: ONE launch = one train step of every object (csrc/obj_fused.hip) -------------------------
+ * N independent OccupancyMap(87, 42, hidden 32) + UniDirsEmbed models (src/model.py:86-155), each trained on its own ray pool by the
+ * reference's background step (train.py:113-121,172-184 with one class): R rays x S = n1 + n2 <= 64 samples, world-frame rays,
+ * depth-guided sampling, composite, the three loss terms (color_scaling, opacity_scaling), backward, AdamW.  One workgroup per
+ * object; exact fp32 arithmetic; no float atomics and no cross-workgroup reduction: two runs give the same bits, and an object's
+ * result does not depend on what else is in the launch.
+ *   theta, exp_avg, exp_avg_sq (N, P) f32, P = cnr_obj_param_count() = 11 363: per object
+ *     in_layer.0 W (32,87) b | mid1.0.0 W (32,32) b | cat_layer.0 W (32,119) b | mid2.0.0 W (32,32) b | out_alpha W (1,32) b |
+ *     color_linear.0 W (32,74) b | out_color W (3,32) b | B_layer.weight (21,3)        (the modules' registration order).
+ *   pools: the objects' rows concatenated -- rgbs (rows,4) u8 [r,g,b,state], depth (rows,), dirs_c (rows,3), T (rows,4,4) = T_wc --
+ *     object o owns rows [pool_off[o], pool_off[o+1]) (pool_off: N + 1 i64 on the device); min_pool_rows: the shortest segment,
+ *     which the host checks against R (an object whose segment is shorter all the same is skipped with flag 16).
+ *   d_state (N,4) i64 = {cursor, rng step, optimiser step, epoch} per object.  Row r of the step is
+ *     bijection(seed, id, epoch)(cursor + r) of the object's segment -- cnr_epoch_perm's keyed permutation evaluated in the kernel,
+ *     id = obj_ids[o] (device, N entries) or o when NULL; the Philox draws are keyed by (seed, id, rng step).  After the step
+ *     cursor += R, and cursor >= rows_o - R starts the object's next epoch (cursor 0, epoch + 1: src/scene_cateogries.py:439-449).
+ *   rows (N,R) i32 (segment-relative), u (N,R,S), g (N,R,n2): all three or none -- the step's rows and draws given (parity tests);
+ *     a row outside the segment is read as row 0 and sets flag 32.
+ *   max_bound and the mask counts of reduce_batch_loss are taken over the object's R rows; a zero count zeroes that term and its
+ *     gradient for that object only (render_rays.py:67-72) and sets flag 2 / 4 / 8 (depth / colour / opacity); flag 1: a term
+ *     above 100 000.  losses (3,N), flags (N).
+ *   Outputs skipped when NULL: grad (N,P) the step's gradient, sigma (N,R,S), rgb (N,R,S,3), z (N,R,S), rows_out (N,R) i32
+ *     (segment-relative).  workspace: cnr_obj_workspace_bytes(N, R, S) bytes, 16-byte aligned.
+ * CNR_E_ARG: a required pointer NULL, N <= 0, R <= 0, S > 64, min_pool_rows < R, a partial parity set, a short workspace. */
+int cnr_obj_param_count(void);
+int64_t cnr_obj_workspace_bytes(int N, int R, int S);
+int cnr_obj_train(const uint8_t* rgbs, const float* depth, const float* dirs_c, const float* T, const int64_t* pool_off,
+                  int64_t min_pool_rows, const int* obj_ids, int N, int R, int n1, int n2, float eps, float stop_eps,
+                  float min_bound, float scale, uint64_t seed, const int* rows, const float* u, const float* g,
+                  int64_t* d_state, float* theta, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                  float adam_eps, float weight_decay, float color_scaling, float opacity_scaling, float* losses,
+                  int32_t* flags, float* grad, float* sigma, float* rgb, float* z, int* rows_out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
