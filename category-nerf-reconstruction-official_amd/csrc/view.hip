@@ -1,7 +1,9 @@
 // Scene view rendering: which pixel rays meet which entity's volume and over what depth range
 // (cnr_view_segments_*), the sample points of every segment in its field's frame (cnr_view_points), and the per-pixel merge
 // of several fields' samples into one alpha composite with an instance label (cnr_view_composite).  The field values in
-// between come from the existing kernels (cnr_field_fwd, the background forward).
+// between come from the existing kernels (cnr_field_fwd, the background forward).  With empty-space skipping
+// cnr_view_active_count / _emit stand in for cnr_view_points: they list the samples that lie in set cells of their entity's
+// occupancy grid (viewgrid.hip), the fields run on that list alone, and cnr_view_scatter_active puts the values back.
 //
 // An entity is a box: to_box (3,4) maps a world point into [-1,1]^3.  Ray directions are (x, y, 1) in the camera frame (z-depth
 // convention, not normalised) and every transform is a similarity, so the parameter z of o + z d is the camera depth in every
@@ -173,6 +175,16 @@ __global__ __launch_bounds__(256) void segments_emit_kernel(const float* __restr
   }
 }
 
+// sample i of S of segment [zn, zf] on pixel ray p: z, and the point in the frame of the affine F (sums left to right)
+__device__ __forceinline__ float sample_world(const Cam& cam, const float* __restrict__ dirs, int64_t p, float zn, float zf, int i,
+                                              int S, float* w) {
+  const float z = zn + ((float)i + 0.5f) * (zf - zn) / (float)S;
+  const float cx = z * dirs[p * 3 + 0], cy = z * dirs[p * 3 + 1], cz = z * dirs[p * 3 + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) w[k] = cam.r[k * 3 + 0] * cx + cam.r[k * 3 + 1] * cy + cam.r[k * 3 + 2] * cz + cam.t[k];
+  return z;
+}
+
 __global__ __launch_bounds__(256) void points_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
                                                      const float* __restrict__ to_field, const int* __restrict__ seg_pixel,
                                                      const int* __restrict__ seg_entity, const float* __restrict__ seg_z,
@@ -185,15 +197,166 @@ __global__ __launch_bounds__(256) void points_kernel(const float* __restrict__ T
   const Cam cam = load_cam(T_wc);
   const int64_t p = seg_pixel[s];
   const float* F = to_field + (int64_t)seg_entity[s] * 12;
-  const float zn = seg_z[s * 2], zf = seg_z[s * 2 + 1];
-  const float z = zn + ((float)i + 0.5f) * (zf - zn) / (float)S;
-  const float cx = z * dirs[p * 3 + 0], cy = z * dirs[p * 3 + 1], cz = z * dirs[p * 3 + 2];
   float w[3], f[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) w[k] = cam.r[k * 3 + 0] * cx + cam.r[k * 3 + 1] * cy + cam.r[k * 3 + 2] * cz + cam.t[k];
+  const float z = sample_world(cam, dirs, p, seg_z[s * 2], seg_z[s * 2 + 1], i, S, w);
   affine_point(F, w[0], w[1], w[2], f);
   z_out[idx] = z;
   pts[idx * 3 + 0] = f[0]; pts[idx * 3 + 1] = f[1]; pts[idx * 3 + 2] = f[2];
+}
+
+// ---- active samples (empty-space skipping) ----------------------------------------------------------------------------------
+// Sample idx = n * S + i of the (N,S) samples is active iff the cell of its entity's occupancy grid that holds its box
+// coordinate is set, or the entity has no grid.  The compact list keeps the active samples in idx order (= entity, segment,
+// sample), every entity's run padded to whole blocks of 64.  Position of an active sample: active_offset[e] + (its rank among
+// all active samples) - (the rank of the entity's first sample).  The ranks come from one 64-bit mask per wave of 64
+// consecutive samples, the wave's offset inside its count block of ACT_WAVES waves, and one exclusive scan of the blocks'
+// counts; the emit launch reads the masks, so that it cannot disagree with the count launch.
+// workspace: mask (nw) u64 | wave_local (nw) i32 | blk_count (nb) i32 | blk_off (nb) i64 | first (E+1) i64 | padded (E) i64,
+// nb = ceil(nw / ACT_WAVES), each part 16-aligned
+constexpr int ACT_WAVES = 16;
+struct ActiveWs { uint64_t* mask; int* wave_local; int* blk_count; int64_t* blk_off; int64_t* first; int64_t* padded; int64_t bytes; };
+__host__ __device__ inline int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }
+__host__ __device__ inline int64_t n_count_blocks(int64_t NS) { return (n_waves(NS) + ACT_WAVES - 1) / ACT_WAVES; }
+__host__ __device__ inline ActiveWs active_ws(void* base, int64_t NS, int E) {
+  const int64_t nw = n_waves(NS), nb = n_count_blocks(NS);
+  char* b = static_cast<char*>(base);
+  ActiveWs w;
+  int64_t o = 0;
+  w.mask = reinterpret_cast<uint64_t*>(b + o); o += up16(nw * 8);
+  w.wave_local = reinterpret_cast<int*>(b + o); o += up16(nw * 4);
+  w.blk_count = reinterpret_cast<int*>(b + o); o += up16(nb * 4);
+  w.blk_off = reinterpret_cast<int64_t*>(b + o); o += up16(nb * 8);
+  w.first = reinterpret_cast<int64_t*>(b + o); o += up16(((int64_t)E + 1) * 8);
+  w.padded = reinterpret_cast<int64_t*>(b + o); o += up16((int64_t)E * 8);
+  w.bytes = o;
+  return w;
+}
+
+__device__ __forceinline__ int grid_axis(float b, int G) {
+  return min(G - 1, max(0, (int)floorf((b + 1.0f) * 0.5f * (float)G)));
+}
+
+__global__ __launch_bounds__(ACT_WAVES * 64) void active_count_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                           const float* __restrict__ to_box, const int* __restrict__ seg_pixel,
+                                                           const int* __restrict__ seg_entity, const float* __restrict__ seg_z,
+                                                           int64_t NS, int S, const int* __restrict__ grid_words,
+                                                           const int* __restrict__ entity_grid, int G,
+                                                           uint64_t* __restrict__ mask, int* __restrict__ wave_local,
+                                                           int* __restrict__ blk_count) {
+  __shared__ int s_wave[ACT_WAVES];
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = (int64_t)blockIdx.x * ACT_WAVES + (threadIdx.x >> 6);      // (a wave past the last one counts nothing)
+  const int64_t idx = wv * 64 + lane;
+  bool active = false;
+  if (idx < NS) {
+    const int64_t s = idx / S;
+    const int i = (int)(idx - s * S);
+    const int e = seg_entity[s];
+    const int g = entity_grid[e];
+    active = g < 0;
+    if (!active) {
+      const Cam cam = load_cam(T_wc);
+      float w[3], b[3];
+      sample_world(cam, dirs, seg_pixel[s], seg_z[s * 2], seg_z[s * 2 + 1], i, S, w);
+      affine_point(to_box + (int64_t)e * 12, w[0], w[1], w[2], b);
+      const int64_t cell = ((int64_t)grid_axis(b[0], G) * G + grid_axis(b[1], G)) * G + grid_axis(b[2], G);
+      const int64_t words = (int64_t)G * G * G / 32;
+      active = (grid_words[(int64_t)g * words + (cell >> 5)] >> (int)(cell & 31)) & 1;
+    }
+  }
+  const unsigned long long m = __ballot(active);
+  int block_total;
+  const int base = cnr::block_prefix_waves<ACT_WAVES>(0, __popcll(m), s_wave, &block_total);
+  if (lane == 0 && wv < n_waves(NS)) { mask[wv] = m; wave_local[wv] = base; }
+  if (threadIdx.x == 0) blk_count[blockIdx.x] = block_total;
+}
+
+// the number of active samples below sample idx (idx <= NS; the workspace as the count launch and the scan left it)
+__device__ __forceinline__ int64_t active_rank(const ActiveWs& w, int64_t idx, int64_t NS, int64_t total) {
+  if (idx >= NS) return total;
+  const int64_t wv = idx >> 6;
+  const int l = (int)(idx & 63);
+  return w.blk_off[wv / ACT_WAVES] + w.wave_local[wv] + __popcll(w.mask[wv] & ((1ull << l) - 1ull));
+}
+
+// one block: exclusive scan of the count blocks' counts; per entity the rank of its first sample and its run padded to 64; the
+// exclusive scan of those -> active_offset (E+1); the unpadded total
+__global__ __launch_bounds__(1024) void active_scan_kernel(ActiveWs w, const int64_t* __restrict__ entity_offset, int64_t NS,
+                                                           int S, int E, int64_t* __restrict__ active_offset,
+                                                           int64_t* __restrict__ total_out) {
+  __shared__ int64_t part[cnr::SCAN_THREADS];
+  __shared__ int64_t total;
+  const int t = threadIdx.x;
+  cnr::scan_block_counts<1>(w.blk_count, n_count_blocks(NS), w.blk_off, &total, part);
+  __syncthreads();
+  for (int e = t; e <= E; e += 1024) w.first[e] = active_rank(w, entity_offset[e] * S, NS, total);
+  __syncthreads();
+  for (int e = t; e < E; e += 1024) w.padded[e] = (w.first[e + 1] - w.first[e] + 63) / 64 * 64;
+  __syncthreads();
+  cnr::scan_block_counts<1>(w.padded, (int64_t)E, active_offset, active_offset + E, part);
+  if (t == 0) total_out[0] = total;
+}
+
+__global__ __launch_bounds__(256) void active_emit_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                          const float* __restrict__ to_field, const int* __restrict__ seg_pixel,
+                                                          const int* __restrict__ seg_entity, const float* __restrict__ seg_z,
+                                                          int64_t NS, int S, int E, const int* __restrict__ entity_row,
+                                                          ActiveWs w, const int64_t* __restrict__ active_offset, int64_t M,
+                                                          float* __restrict__ z_out, int64_t* __restrict__ active_idx,
+                                                          float* __restrict__ pts_c, int* __restrict__ block_row) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx < NS) {
+    const int64_t s = idx / S;
+    const int i = (int)(idx - s * S);
+    const int e = seg_entity[s];
+    const Cam cam = load_cam(T_wc);
+    float wp[3], f[3];
+    z_out[idx] = sample_world(cam, dirs, seg_pixel[s], seg_z[s * 2], seg_z[s * 2 + 1], i, S, wp);
+    if ((w.mask[idx >> 6] >> (idx & 63)) & 1ull) {
+      const int64_t pos = active_offset[e] + active_rank(w, idx, NS, 0) - w.first[e];
+      if (pos >= 0 && pos < M) {
+        affine_point(to_field + (int64_t)e * 12, wp[0], wp[1], wp[2], f);
+        active_idx[pos] = idx;
+        pts_c[pos * 3 + 0] = f[0]; pts_c[pos * 3 + 1] = f[1]; pts_c[pos * 3 + 2] = f[2];
+      }
+    }
+  }
+  // the padding behind every entity's run (fewer than 64 entries): lane l of the first E * 64 threads
+  if (idx < (int64_t)E * 64) {
+    const int e = (int)(idx >> 6);
+    const int64_t pos = active_offset[e] + (w.first[e + 1] - w.first[e]) + (idx & 63);
+    if (pos < active_offset[e + 1] && pos < M) {
+      active_idx[pos] = -1;
+      pts_c[pos * 3 + 0] = 0.f; pts_c[pos * 3 + 1] = 0.f; pts_c[pos * 3 + 2] = 0.f;
+    }
+  }
+  // the code-table row of every block of 64: the entity whose run holds it (runs of no block are passed over)
+  if (idx < M / 64) {
+    int lo = 0, hi = E;                      // the last e with active_offset[e] <= idx * 64
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (active_offset[mid] <= idx * 64) lo = mid; else hi = mid;
+    }
+    block_row[idx] = entity_row[lo];
+  }
+}
+
+__global__ __launch_bounds__(256) void fill_empty_kernel(int64_t NS, float* __restrict__ sigma, float* __restrict__ color) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= NS) return;
+  sigma[idx] = -INFINITY;
+  color[idx * 3 + 0] = 0.f; color[idx * 3 + 1] = 0.f; color[idx * 3 + 2] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void scatter_active_kernel(const float* __restrict__ sigma_c, const float* __restrict__ color_c,
+                                                             const int64_t* __restrict__ active_idx, int64_t M, int64_t NS,
+                                                             float* __restrict__ sigma, float* __restrict__ color) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= M) return;
+  const int64_t idx = active_idx[j];
+  if (idx < 0 || idx >= NS) return;
+  sigma[idx] = sigma_c[j];
+  color[idx * 3 + 0] = color_c[j * 3 + 0]; color[idx * 3 + 1] = color_c[j * 3 + 1]; color[idx * 3 + 2] = color_c[j * 3 + 2];
 }
 
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -385,5 +548,65 @@ extern "C" int cnr_view_composite(const float* sigma, const float* color, const 
   hipLaunchKernelGGL(composite_kernel, dim3((unsigned)P), dim3(64), lds, (hipStream_t)stream, sigma, color, z, pix_segs,
                      seg_entity, entity_inst, P, S, opacity_threshold, rgb, depth, opacity, var, mass, instance);
   CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int64_t cnr_view_active_workspace_bytes(int64_t N, int S, int E) {
+  if (N <= 0 || S < 1 || S > SMAX || E <= 0) return 0;
+  return active_ws(nullptr, N * S, E).bytes;
+}
+
+extern "C" int cnr_view_active_count(const float* T_wc, const float* dirs, const float* to_box, const int* seg_pixel,
+                                     const int* seg_entity, const float* seg_z, const int64_t* entity_offset, int64_t N, int S,
+                                     int E, const int* grid_words, const int* entity_grid, int G, void* workspace,
+                                     int64_t* active_offset, int64_t* count_out, void* stream) {
+  if (!T_wc || !dirs || !to_box || !seg_pixel || !seg_entity || !seg_z || !entity_offset || !grid_words || !entity_grid ||
+      !workspace || !active_offset || !count_out || N <= 0 || E <= 0)
+    return CNR_E_ARG;
+  if (S < 1 || S > SMAX || E > 32767 || G < 4 || G > 128 || G % 4 != 0) return CNR_E_SHAPE;
+  const int64_t NS = N * S, nb = n_count_blocks(NS);
+  if (nb >= (1ll << 31)) return CNR_E_SHAPE;
+  const ActiveWs w = active_ws(workspace, NS, E);
+  hipLaunchKernelGGL(active_count_kernel, dim3((unsigned)nb), dim3(ACT_WAVES * 64), 0, (hipStream_t)stream, T_wc, dirs, to_box,
+                     seg_pixel, seg_entity, seg_z, NS, S, grid_words, entity_grid, G, w.mask, w.wave_local, w.blk_count);
+  CNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(active_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, entity_offset, NS, S, E, active_offset,
+                     count_out);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_active_emit(const float* T_wc, const float* dirs, const float* to_field, const int* seg_pixel,
+                                    const int* seg_entity, const float* seg_z, int64_t N, int S, int E, const int* entity_row,
+                                    const void* workspace, const int64_t* active_offset, int64_t M, float* z,
+                                    int64_t* active_idx, float* pts_c, int* block_row, void* stream) {
+  if (!T_wc || !dirs || !to_field || !seg_pixel || !seg_entity || !seg_z || !entity_row || !workspace || !active_offset || !z ||
+      N <= 0 || E <= 0 || M < 0)
+    return CNR_E_ARG;
+  if (M > 0 && (!active_idx || !pts_c || !block_row)) return CNR_E_ARG;
+  if (S < 1 || S > SMAX || E > 32767 || M % 64 != 0) return CNR_E_SHAPE;
+  const int64_t NS = N * S;
+  const int64_t threads = NS > (int64_t)E * 64 ? NS : (int64_t)E * 64;
+  const int64_t blocks = (threads + 255) / 256;
+  if (blocks >= (1ll << 31)) return CNR_E_SHAPE;
+  const ActiveWs w = active_ws(const_cast<void*>(workspace), NS, E);
+  hipLaunchKernelGGL(active_emit_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T_wc, dirs, to_field,
+                     seg_pixel, seg_entity, seg_z, NS, S, E, entity_row, w, active_offset, M, z, active_idx, pts_c, block_row);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_scatter_active(const float* sigma_c, const float* color_c, const int64_t* active_idx, int64_t M,
+                                       int64_t NS, float* sigma, float* color, void* stream) {
+  if (!sigma || !color || NS <= 0 || M < 0) return CNR_E_ARG;
+  if (M > 0 && (!sigma_c || !color_c || !active_idx)) return CNR_E_ARG;
+  if ((NS + 255) / 256 >= (1ll << 31) || (M + 255) / 256 >= (1ll << 31)) return CNR_E_SHAPE;
+  hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((NS + 255) / 256)), dim3(256), 0, (hipStream_t)stream, NS, sigma, color);
+  CNR_LAUNCH_CHECK();
+  if (M > 0) {
+    hipLaunchKernelGGL(scatter_active_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sigma_c,
+                       color_c, active_idx, M, NS, sigma, color);
+    CNR_LAUNCH_CHECK();
+  }
   return CNR_OK;
 }

@@ -1019,6 +1019,43 @@ int cnr_view_points(const float* T_wc, const float* dirs, const float* to_field,
 int cnr_view_composite(const float* sigma, const float* color, const float* z, const int* pix_segs, const int* seg_entity,
                        const int* entity_inst, int64_t P, int S, float opacity_threshold, float* rgb, float* depth,
                        float* opacity, float* var, float* mass, int* instance, void* stream);
+/* Empty-space skipping.  An occupancy grid is one bit per cell of a G^3 grid over an entity's box [-1,1]^3, G a multiple of 4
+ * in 4 .. 128: cell (ix, iy, iz) has the linear index l = (ix G + iy) G + iz and is bit l & 31 of word l >> 5 of the grid's
+ * G^3 / 32 i32 words.
+ *
+ * cnr_view_grid_cells: occ (D,D,D) f32, D = G sub + 1, 1 <= sub <= 4, a lattice of occupancies over the box, first axis x
+ * -> words.  A cell owns the lattice indices [i sub, (i + 1) sub] of every axis, both faces included, and is set iff some
+ * owned value v satisfies !(v < tau): a value equal to tau sets it, and so does a NaN.
+ * cnr_view_grid_dilate: words_out = every cell within Chebyshev distance radius (0 .. 2) of a set cell of words_in, the
+ * neighbourhood clamped at the faces of the grid; out of place (words_in == words_out is CNR_E_ARG).
+ *
+ * Active samples: the count / emit pair that stands in for cnr_view_points.  Sample n S + i of the (N,S) samples of the
+ * segments (z_i and the world point as in cnr_view_points) is active iff entity_grid[seg_entity[n]] < 0 (no grid: all set) or
+ * the cell c of grid entity_grid[.] of grid_words (grids, G^3 / 32) is set, b = to_box[seg_entity[n]] . world point,
+ * c_k = min(G - 1, max(0, (int)floorf((b_k + 1) 0.5 G))).  cnr_view_active_count, with entity_offset as
+ * cnr_view_segments_count left it, writes active_offset (E+1,) i64 and count_out (1,) i64 = the number of active samples, and
+ * keeps its masks and ranks in workspace (>= cnr_view_active_workspace_bytes(N, S, E)).  The compact list holds the active
+ * samples in (entity, segment, sample) order, every entity's run padded to a multiple of 64 entries: entity e owns
+ * [active_offset[e], active_offset[e+1]), M = active_offset[E].  cnr_view_active_emit, after it on the same stream with the same
+ * workspace, writes z (N,S) of every sample, active_idx (M,) i64 = n S + i, or -1 at a padding entry, pts_c (M,3) =
+ * to_field . world point, bit for bit what cnr_view_points writes for that sample, the origin at a padding entry, and
+ * block_row (M/64,) i32 = entity_row[e] of the entity e whose run holds the block.  With M = 0 those three may be NULL. */
+int cnr_view_grid_cells(const float* occ, int G, int sub, float tau, int* words, void* stream);
+int cnr_view_grid_dilate(const int* words_in, int G, int radius, int* words_out, void* stream);
+int64_t cnr_view_active_workspace_bytes(int64_t N, int S, int E);
+int cnr_view_active_count(const float* T_wc, const float* dirs, const float* to_box, const int* seg_pixel,
+                          const int* seg_entity, const float* seg_z, const int64_t* entity_offset, int64_t N, int S, int E,
+                          const int* grid_words, const int* entity_grid, int G, void* workspace, int64_t* active_offset,
+                          int64_t* count_out, void* stream);
+int cnr_view_active_emit(const float* T_wc, const float* dirs, const float* to_field, const int* seg_pixel,
+                         const int* seg_entity, const float* seg_z, int64_t N, int S, int E, const int* entity_row,
+                         const void* workspace, const int64_t* active_offset, int64_t M, float* z, int64_t* active_idx,
+                         float* pts_c, int* block_row, void* stream);
+/* sigma (NS,) = -inf and color (NS,3) = 0 everywhere, then sigma[active_idx[j]] = sigma_c[j], color[active_idx[j]] = color_c[j]
+ * for the M entries of the compact list; an entry with active_idx < 0 (padding) writes nothing.  cnr_view_composite gives a
+ * sample of sigma -inf the occupancy 0 exactly, so it multiplies the transmittance by exactly 1. */
+int cnr_view_scatter_active(const float* sigma_c, const float* color_c, const int64_t* active_idx, int64_t M, int64_t NS,
+                            float* sigma, float* color, void* stream);
 
 /* ---- ScanNet mask refinement (src/utils.py: geometry_segmentation, refine_inst_data).  The contracts
  * above hold: caller-allocated outputs, an explicit stream, argument errors as return codes before the device is touched, no

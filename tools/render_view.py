@@ -1,10 +1,12 @@
 """Renders the trained scene from one of the dataset's camera poses: builds the categories as train.py does (cameraInfo,
 get_dataset, one sceneCategory per class), loads the newest checkpoint of each from --logdir, and writes rgb.png, depth.png
 (16 bit, millimetres) and instance.png (16 bit, 65535 = nothing) into --out.  Two edits, neither of which touches the trained
-state: --move INST tx ty tz translates an instance in world coordinates, --hide INST leaves it out.
+state: --move INST tx ty tz translates an instance in world coordinates, --hide INST leaves it out.  --skip-empty builds
+one occupancy grid per entity from the loaded weights (G^3 cells, a cell kept where the occupancy reaches --tau on meshing's
+lattice or in a neighbouring cell) and evaluates the fields only inside the kept cells.
 
     python tools/render_view.py --config configs/Replica/config_replica_room0.json --logdir logs/room0 --frame 0 --out view0
-        [--samples 64] [--move 12 0.3 0 0] [--hide 7]"""
+        [--samples 64] [--move 12 0.3 0 0] [--hide 7] [--skip-empty [--grid 64] [--tau 1e-3]]"""
 import argparse
 import glob
 import os
@@ -32,6 +34,9 @@ def main():
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--move", nargs=4, action="append", default=[], metavar=("INST", "TX", "TY", "TZ"))
     ap.add_argument("--hide", type=int, action="append", default=[], metavar="INST")
+    ap.add_argument("--skip-empty", action="store_true", help="skip the samples in empty cells of per-entity occupancy grids")
+    ap.add_argument("--grid", type=int, default=64, metavar="G", help="cells per axis of the occupancy grids (a multiple of 4, 4 .. 128)")
+    ap.add_argument("--tau", type=float, default=1e-3, metavar="T", help="a cell is kept where the occupancy reaches T")
     ap.add_argument("--allow-pickle", action="store_true", help="unpickle the checkpoints instead of the weights-only read: needed for a background's box object and for numpy "
                     "scalar ids (trusted files only)")
     a = ap.parse_args()
@@ -58,8 +63,13 @@ def main():
         E[:3, 3] = float(tx), float(ty), float(tz)
         transforms[int(inst)] = E
     T_wc = np.asarray(data.sample_dict[a.frame]["T"], np.float64)
+    if a.skip_empty:
+        renderer.build_grids(resolution=a.grid, threshold=a.tau)
     with torch.no_grad():
-        result = renderer.render(T_wc, n_samples=a.samples, transforms=transforms, hidden=set(a.hide))
+        result = renderer.render(T_wc, n_samples=a.samples, transforms=transforms, hidden=set(a.hide), skip_empty=a.skip_empty)
+    if a.skip_empty:
+        evaluated, total = renderer.active_samples
+        print("evaluated {} of {} samples ({:.1%})".format(evaluated, total, evaluated / max(total, 1)))
     cnr.view.render_to_files(result, a.out)
     shown = sorted(int(i) for i in torch.unique(result["instance"]).tolist())
     print("wrote rgb.png, depth.png, instance.png to {}; instances in view: {}".format(a.out, shown))
