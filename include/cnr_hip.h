@@ -1141,6 +1141,44 @@ int cnr_obj_train(const uint8_t* rgbs, const float* depth, const float* dirs_c, 
                   int32_t* flags, float* grad, float* sigma, float* rgb, float* z, int* rows_out, void* workspace,
                   int64_t workspace_bytes, void* stream);
 
+/* ---- fitting codes to a frozen category: ONE launch = one optimisation step of every candidate (csrc/code_fit.hip) --------------
+ * A candidate is one (instance, starting code) pair: a shape code and a texture code of a frozen CodeNeRF category, fitted to the
+ * instance's own ray pool by the reference's object step with a one-object class and the network held fixed (train.py:123-167,
+ * src/model.py:56-84, src/loss.py:5-74): rows, origin_dirs_O / origin_dirs_W, depth-guided sampling, UniDirsEmbed, CodeNeRF
+ * forward, composite, the three masked L1 terms, backward to the four latent outputs and through the latent layers to the two
+ * codes, the code-norm regulariser, AdamW on the codes.  One workgroup per candidate; exact fp32 arithmetic; no float atomics and
+ * no cross-workgroup reduction: two runs give the same bits, and a candidate's result does not depend on what else is in the launch.
+ *   theta: n_nets rows of class_stride floats, the frozen networks; inside a row the trunk (CNR_TRUNK_PARAMS floats, the blob
+ *     order above) at off_trunk, the latent matrices (4,32,L) at off_latW, their biases (4,32) at off_latb, B (21,3) at off_B --
+ *     fused.ParamLayout's row, so a live FusedCategoryTrainer buffer or a packed snapshot can both be passed.  Never written.
+ *   pools: P segments concatenated as for cnr_obj_train (rgbs, depth, dirs_c, T, pool_off (P + 1), min_pool_rows); pool_ids (P)
+ *     i32 or NULL (the segment index); pool_world_frame (P) i32: 0 = the T rows are T_CO (origin_dirs_O inverts them), else T_WC.
+ *   cand_net, cand_pool (K) i32: the network and the pool of every candidate.  Several candidates may share a pool: rows and
+ *     draws are keyed by (seed, pool id, epoch or rng step), not by the candidate, so candidates of one pool with equal state see
+ *     the same rays and draws and differ only in their codes.  An index out of range sets flag 64 and the candidate is skipped:
+ *     nothing of it is read and its five loss values are zero.
+ *   codes, exp_avg, exp_avg_sq (K,2,L) f32: shape code, then texture code.  d_state (K,4) i64 = {cursor, rng step, optimiser step,
+ *     epoch} with cnr_obj_train's rule.  update = 0: evaluation only -- losses, flags and the optional outputs are written; codes,
+ *     moments and state are untouched.
+ *   rows (K,R) i32 (segment-relative), u (K,R,S), g (K,R,n2): all three or none, as cnr_obj_train.
+ *   The regulariser adds reg_scaling * c / ||c|| to each code's gradient when reg_scaling > 0 (zero at ||c|| = 0, as torch's norm).
+ *   losses (5,K) = depth, colour, opacity, ||shape code||, ||texture code||; flags (K): cnr_obj_train's bits (1 a term above
+ *     100 000; 2 / 4 / 8 a zero depth / colour / opacity count, which zeroes that term and its gradient for that candidate only;
+ *     16 a pool shorter than R, skipped; 32 a given row out of range) and 64.  Outputs skipped when NULL: grad (K,2,L), sigma
+ *     (K,R,S), rgb (K,R,S,3), z (K,R,S), rows_out (K,R) i32.  workspace: cnr_code_fit_workspace_bytes(K, R, S), 16-byte aligned.
+ * CNR_E_ARG: a required pointer NULL, K <= 0, R <= 0, n_nets <= 0, P <= 0, S > 64, min_pool_rows < R, a partial parity set, a
+ * short workspace, a trunk / latent W / latent b / B block that would end past class_stride.  CNR_E_SHAPE: a code length L other than a divisor or a multiple of 256 (the latent kernels' rule). */
+int64_t cnr_code_fit_workspace_bytes(int K, int R, int S);
+int cnr_code_fit(const float* theta, int64_t class_stride, int64_t off_trunk, int64_t off_latW, int64_t off_latb, int64_t off_B,
+                 int n_nets, int L, const uint8_t* rgbs, const float* depth, const float* dirs_c, const float* T,
+                 const int64_t* pool_off, int64_t min_pool_rows, const int* pool_ids, const int* pool_world_frame, int P,
+                 const int* cand_net, const int* cand_pool, int K, int R, int n1, int n2, float eps, float stop_eps,
+                 float min_bound, float scale, uint64_t seed, const int* rows, const float* u, const float* g, int64_t* d_state,
+                 float* codes, float* exp_avg, float* exp_avg_sq, int update, float lr, float beta1, float beta2, float adam_eps,
+                 float weight_decay, float color_scaling, float opacity_scaling, float reg_scaling, float* losses, int32_t* flags,
+                 float* grad, float* sigma, float* rgb, float* z, int* rows_out, void* workspace, int64_t workspace_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
