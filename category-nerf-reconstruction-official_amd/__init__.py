@@ -8,6 +8,6 @@ multi-GPU sharding, ``category_registration`` the forward-only uncertainty probe
 cnr_amd.py at the repo root; the directory name carries a hyphen).
 """
 from . import _C, ops  # noqa: F401
-from . import cfg, embedding, model, render_rays, loss, trainer, utils, scene_cateogries, stepgraph, fused, parallel, background, category_registration, vis, metrics, dataset, teaser_utils, view, object_fields, code_fit  # noqa: F401
+from . import cfg, embedding, model, render_rays, loss, trainer, utils, scene_cateogries, stepgraph, fused, parallel, background, category_registration, vis, metrics, dataset, teaser_utils, view, pool_step, object_fields, code_fit  # noqa: F401
 
 __version__ = "0.1.0"

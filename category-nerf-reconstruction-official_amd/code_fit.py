@@ -13,9 +13,9 @@ import math
 import numpy as np
 import torch
 
-from . import _C, stepgraph
+from . import _C, pool_step
 from .fused import ParamLayout
-from .object_fields import next_state          # (the state rule is cnr_obj_train's)  # noqa: F401
+from .pool_step import next_state          # (the state rule: one definition for both kernels' trainers)  # noqa: F401
 from .ops import LATENT_LAYERS, TRUNK_LAYERS
 
 LOSS_NAMES = ("depth", "color", "opacity", "shape_norm", "texture_norm")
@@ -51,7 +51,7 @@ def pack_net(trainer, lay, out):
 
 def random_codes(m, L, seed, inst_id):
     """``m`` (2, L) starts from ``Trainer.load_codes``' distribution, randn / sqrt(L / 2), seeded by (seed, inst_id)"""
-    gen = torch.Generator().manual_seed((int(seed) * 7919 + 104729 * (int(inst_id) + 1)) & 0x7FFFFFFFFFFF)
+    gen = torch.Generator().manual_seed(pool_step.instance_seed(seed, inst_id))
     return torch.randn(m, 2, L, generator=gen) / math.sqrt(L / 2)
 
 
@@ -147,7 +147,7 @@ def load_category(cfg, ckpt_file, allow_pickle=False):
     return t
 
 
-class CodeFitter:
+class CodeFitter(pool_step.StepBranch):
     def __init__(self, cfg, nets, instances, starts="mean", rays_per_step=None, seed=0, reg_scaling=0.0005, device=None):
         """``nets``: {cls_id: Trainer} of CodeNeRF categories; their parameters are snapshotted into one flat buffer here
         (``refresh()`` snapshots again) and the modules are never written.  ``instances``: a list of dict(inst_id, cls_id,
@@ -192,11 +192,7 @@ class CodeFitter:
         self.inst_ids = [inst["inst_id"] for inst in instances]
         if len(set(self.inst_ids)) != len(self.inst_ids):
             raise ValueError("CodeFitter: an instance id occurs twice")
-        cat = lambda key, dt: torch.cat([inst["pool"][key].to(dev, dt) for inst in instances]).contiguous()
-        self.pool = dict(rgbs=cat("rgbs", torch.uint8), depth=cat("depth", torch.float32), dirs=cat("dirs", torch.float32),
-                         T=cat("T", torch.float32))
-        self.rows = [int(inst["pool"]["depth"].shape[0]) for inst in instances]
-        self.pool_off = torch.tensor(np.concatenate([[0], np.cumsum(self.rows)]), dtype=torch.int64, device=dev)
+        self.pool, self.rows, self.pool_off = pool_step.concat_pools([inst["pool"] for inst in instances], "T", dev)
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
         self.pool_ids = i32([int(i) for i in self.inst_ids])
         self.pool_world_frame = i32([1 if inst.get("world_frame", False) else 0 for inst in instances])
@@ -220,8 +216,7 @@ class CodeFitter:
         self._score_losses = torch.zeros(5, K, device=dev)
         self._score_flags = torch.zeros(K, device=dev, dtype=torch.int32)
         self.ws = _C.workspace(_C.load().cnr_code_fit_workspace_bytes(K, R, self.S), dev, "cnr_code_fit")
-        self.steps_done = 0
-        self._sched = stepgraph.StepGraphs([self], 3, 8)
+        self._init_steps()
 
     def refresh(self):
         """snapshot the categories' parameters again (after more joint training); captured graphs read the same buffer"""
@@ -242,26 +237,6 @@ class CodeFitter:
                 float(cfg.code_learning_rate), 0.9, 0.999, 1e-8, float(cfg.code_weight_decay), COLOR_SCALING, OPACITY_SCALING,
                 self.reg_scaling, self._losses if losses is None else losses, self.flags if flags is None else flags, grad, sigma,
                 rgb, z, rows_out, self.ws, self.ws.numel())
-
-    # ---- the branch interface of stepgraph.StepGraphs ----------------------------------------------------------------------------
-    parity = 0                # one state copy; a captured step depends on nothing the host changes
-
-    def record(self, slot=None, par=0):
-        self.launch()
-
-    def before_step(self):
-        return 1 << 30        # every candidate ends its epochs on the device: no step ever waits for the host
-
-    def advance(self, U=1):
-        self.steps_done += U
-
-    def step(self, use_graph=True):
-        """One step of every candidate; after three eager steps it is captured and replayed."""
-        self._sched.step(use_graph)
-
-    def run(self, n, unroll=8, use_graph=True):
-        """``n`` steps, the same arithmetic as ``n`` calls of ``step()``, in graphs of up to ``unroll`` steps."""
-        self._sched.run(n, unroll, use_graph)
 
     @property
     def losses(self):
@@ -290,10 +265,6 @@ class CodeFitter:
         a, b = self.slices[inst_id]
         return self._codes[a:b] if start is None else self._codes[a + int(start)]
 
-    def state(self):
-        """(K,4) host list of [cursor, rng step, optimiser step, epoch]; synchronises"""
-        return self.d_state.cpu().tolist()
-
     def attach(self, trainer, inst_id, extent=None):
         """The best codes of ``inst_id`` become new rows of ``trainer.shape_codes`` / ``trainer.texture_codes`` (``attach_codes``);
         ``extent`` (3,): the instance's box extent, which ``Trainer.meshing`` reads for a category of several instances."""
@@ -308,53 +279,14 @@ class CodeFitter:
         gather ``sceneCategory`` uses for a class of several instances (src/scene_cateogries.py:164-260): the crops of the instance's
         ``frame_info``, this / other / unknown pixel states, every row carrying T_CO = inv(T_wc) @ T_obj of its frame -- ONE
         cnr_gather_pool launch for all of them.  ``frames``: only crops of these frames (the partially observed case)."""
-        from .scene_cateogries import cameraInfo
         dev = torch.device(device or dataset._parse_device())
-        sample_dict = dataset.sample_dict
         keep = None if frames is None else set(frames)
-        per_inst = []
-        for cls_id, entries in dataset.inst_dict.items():
-            if cls_id == 0:
-                continue
-            for inst_id, info in entries.items():
-                if inst_id in poses:
-                    crops = [(fi["frame"],) + tuple(int(v) for v in fi["bbox"]) + (idx,) for idx, fi in enumerate(info["frame_info"])
-                             if keep is None or fi["frame"] in keep]
-                    per_inst.append((inst_id, crops))
+        per_inst = [(inst_id, [c + (idx,) for idx, c in enumerate(cr) if keep is None or c[0] in keep])
+                    for inst_id, cr in pool_step.crops_of(dataset.inst_dict) if inst_id in poses]
         missing = set(poses) - {i for i, _ in per_inst}
         if missing:
             raise ValueError(f"pools_from_dataset: no instance {sorted(missing)} in the dataset's inst_dict")
-        used = sorted({c[0] for _, crops in per_inst for c in crops})
-        if not used:
+        if not any(crops for _, crops in per_inst):
             raise ValueError("pools_from_dataset: no crop left in the given frames")
-        slot = {f: i for i, f in enumerate(used)}
-        stack = lambda key, dt: torch.from_numpy(np.stack([np.asarray(sample_dict[f][key]) for f in used])).to(dt)
-        images = stack("image", torch.uint8).to(dev).contiguous()
-        depths = stack("depth", torch.float32).to(dev).contiguous()
-        masks = stack("obj_mask", torch.int32).to(dev).contiguous()
-        T_wc = stack("T", torch.float32).to(dev)
-        W, H = images.shape[1:3]
-        rays = cameraInfo(cfg, device=dev).rays_dir_cache.contiguous()
-        crops_l, areas, T_crop, n_rows = [], [], [], []
-        for inst_id, cr in per_inst:
-            T_obj = torch.as_tensor(np.asarray(poses[inst_id]), dtype=torch.float32).to(dev)
-            n = 0
-            for frame, w0, w1, h0, h1, idx in cr:
-                crops_l.append([slot[frame], int(inst_id), 0, w0, w1, h0, h1, idx])
-                areas.append((w1 - w0) * (h1 - h0))
-                T_crop.append(torch.linalg.inv(T_wc[slot[frame]]) @ T_obj)
-                n += areas[-1]
-            n_rows.append(n)
-        N = int(sum(areas))
-        crops_t = torch.tensor(crops_l, dtype=torch.int32, device=dev)
-        off_t = torch.tensor(np.concatenate([[0], np.cumsum(areas)]), dtype=torch.int64, device=dev)
-        T_crop = torch.stack(T_crop).contiguous()
-        rgbs = torch.empty(N, 4, dtype=torch.uint8, device=dev)
-        depth, dirs, T_rows = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 4, 4, device=dev)
-        _C.call("cnr_gather_pool", images, depths, masks, rays, T_crop, crops_t, off_t, None, int(W), int(H), len(crops_l), N,
-                rgbs, depth, dirs, T_rows, None, None)
-        pools, at = {}, 0
-        for (inst_id, _), n in zip(per_inst, n_rows):
-            pools[inst_id] = dict(rgbs=rgbs[at:at + n], depth=depth[at:at + n], dirs=dirs[at:at + n], T=T_rows[at:at + n])
-            at += n
-        return pools
+        T_obj = {i: torch.as_tensor(np.asarray(poses[i]), dtype=torch.float32).to(dev) for i, _ in per_inst}
+        return pool_step.gather_pools(dataset, cfg, per_inst, lambda inst_id, T_wc: torch.linalg.inv(T_wc) @ T_obj[inst_id], "T", dev)

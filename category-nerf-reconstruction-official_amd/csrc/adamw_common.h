@@ -14,16 +14,26 @@ __device__ __forceinline__ void adam_coefficients(const AdamArgs& a, int64_t t, 
   step_size = (float)((double)a.lr / (1.0 - pow((double)a.b1, td)));
   inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, td)));
 }
+// one element's update, by value (loads and stores are the caller's): parameter p, moments m and v, gradient g;
+// decay = 1 - lr * weight decay
+struct AdamElement { float p, m, v; };
+__device__ __forceinline__ AdamElement adam_element(float p, float m, float v, float g, float decay, float step_size,
+                                                    float inv_bc2_sqrt, float b1, float b2, float eps) {
+  float pi = p * decay;
+  const float mi = m + (g - m) * (1.0f - b1);
+  const float vi = v * b2 + (1.0f - b2) * g * g;
+  const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
+  pi -= step_size * (mi / denom);
+  return {pi, mi, vi};
+}
 // grid-stride over the flat buffer: block `blk` of `nblk` 256-thread blocks
 __device__ __forceinline__ void adam_update(const AdamArgs& a, float step_size, float inv_bc2_sqrt, int blk, int nblk) {
   for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < a.n; i += (int64_t)nblk * 256) {
+    // (the gradient is read first: with p, m, v read ahead of it the compiler contracts the other product of v's sum into the
+    //  multiply-add, and v differs in the last place)
     const float gi = a.g[i] * a.gunscale;
-    float pi = a.p[i] * (1.0f - a.lr * a.wd);
-    const float mi = a.m[i] + (gi - a.m[i]) * (1.0f - a.b1);
-    const float vi = a.v[i] * a.b2 + (1.0f - a.b2) * gi * gi;
-    const float denom = sqrtf(vi) * inv_bc2_sqrt + a.eps;
-    pi -= step_size * (mi / denom);
-    a.p[i] = pi; a.m[i] = mi; a.v[i] = vi;
+    const AdamElement e = adam_element(a.p[i], a.m[i], a.v[i], gi, 1.0f - a.lr * a.wd, step_size, inv_bc2_sqrt, a.b1, a.b2, a.eps);
+    a.p[i] = e.p; a.m[i] = e.m; a.v[i] = e.v;
   }
 }
 }  // namespace cnr

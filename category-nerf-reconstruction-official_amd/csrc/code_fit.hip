@@ -1,8 +1,8 @@
 // cnr_code_fit: one launch = one optimisation step of EVERY candidate of a code fit.  A candidate is one (instance, starting
 // code) pair: a shape code and a texture code of a FROZEN CodeNeRF category (src/model.py:23-84), fitted to the instance's own ray
 // pool by the reference's object step with a one-object class (train.py:123-167, src/loss.py:5-74) and the network held fixed.
-// Candidates share nothing they write, so ONE WORKGROUP owns one candidate for the whole step, in the manner of cnr_obj_train
-// (obj_fused.hip): rows -> rays -> latent layers -> PE -> trunk -> composite + losses -> backward to the four latent outputs ->
+// Candidates share nothing they write, so ONE WORKGROUP owns one candidate for the whole step, on the step skeleton it shares with
+// cnr_obj_train (pool_step_common.h): rows -> rays -> latent layers -> PE -> trunk -> composite + losses -> backward to the four latent outputs ->
 // latent layers backward -> regulariser -> AdamW on the two codes.  No cross-workgroup reduction, no wait across workgroups and no
 // float atomic: every sum has one owner and a fixed order, so two runs give the same bits and a candidate's result does not depend
 // on what else is in the launch.
@@ -16,16 +16,12 @@
 // TRANSPOSED in LDS for the whole step (the same image serves the forward, by columns, and the backward, by rows), the activations
 // of one tile of whole rays beside them; the latent matrices (4 x 32 x L: 131 KB at L = 256) do not fit and are read from global
 // memory, once for the latent forward and once for the code gradient.  (DESIGN.md 3.14 has the LDS map.)
-#include "sample_common.h"
-#include "render_common.h"
-#include "adamw_common.h"
-#include "obj_args.h"
+#include "pool_step_common.h"
 
 namespace {
 using namespace cnr;
-constexpr int H = 32, NDIR = 21, H2 = 16;
-constexpr int THREADS = 512, WAVES = THREADS / 64, TS = 64;
-constexpr float PI_F = 3.14159265358979323846f;
+using namespace cnr_pool_step;      // the step skeleton shared with cnr_obj_train: THREADS, WAVES, TS, H, NDIR and the steps
+constexpr int H2 = 16;
 // rows of the transposed weight image WT[q][32]: WT[Q_l + k][j] = W_l[j][k] for the seven 32-wide layers
 constexpr int Q_XYZ = 0, Q_S1 = Q_XYZ + E1, Q_CAT = Q_S1 + H, Q_S2 = Q_CAT + H + E1, Q_ES = Q_S2 + H, Q_VD = Q_ES + H,
               Q_T1 = Q_VD + H + E2, QN = Q_T1 + H;
@@ -48,27 +44,11 @@ constexpr int LDS_BYTES = L_END * 4;
 static_assert((L_R0T & 3) == 0 && (L_D & 3) == 0 && (L_SP & 3) == 0, "16-byte accesses");
 static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU: 160 KB of LDS");
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct FitArgs {
+struct FitArgs : StepArgs {
   const float* theta; int64_t class_stride, off_trunk, off_latW, off_latb, off_B; int n_nets, L;
-  const uint8_t* rgbs; const float* depth; const float* dirs_c; const float* T; const int64_t* pool_off; const int* pool_ids;
-  const int* pool_world_frame; int P;
-  const int* cand_net; const int* cand_pool; int K, R, n1, n2; float eps, stop_eps, min_bound, scale; uint64_t seed;
-  const int* rows; const float* u; const float* g;
-  int64_t* d_state; float* codes; float* exp_avg; float* exp_avg_sq; int update;
-  float lr, b1, b2, adam_eps, wd, color_scaling, opacity_scaling, reg_scaling;
-  float* losses; int32_t* flags; float* grad; float* sigma; float* rgb; float* z; int* rows_out;
-  uint32_t* ws; int64_t ws_stride;
+  const int* pool_ids; const int* pool_world_frame; int P;
+  const int* cand_net; const int* cand_pool; int K; float* codes; int update; float reg_scaling;
 };
-
-// index of D[buffer][sample][j] (j a multiple of 4 for a 16-byte access): the four-float groups of a row are XOR-ed with the
-// sample's low bits, so that the 16-byte accesses of consecutive samples fall on different banks
-__device__ __forceinline__ int dix(int b, int s, int j) { return L_D + ((b * TS + s) << 5) + (j ^ ((s & 7) << 2)); }
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-__device__ __forceinline__ float dot4(f4 a, f4 b, float acc) {
-  acc = fmaf(a[0], b[0], acc); acc = fmaf(a[1], b[1], acc); acc = fmaf(a[2], b[2], acc); return fmaf(a[3], b[3], acc);
-}
 
 // one 32-wide layer for sample s, outputs 4 og .. 4 og + 3: inputs are ACT columns colA .. colA + nA - 1 PLUS the row zrow[0 .. nA)
 // (a latent row, or the zero row: nA <= 32), then ACT columns colB .. colB + nB - 1 (weight rows q0 ..); the result, after a ReLU when `relu`,
@@ -99,7 +79,7 @@ __device__ __forceinline__ void layer_fwd(float* __restrict__ lds, int s, int og
 __device__ __forceinline__ f4 layer_bwd(const float* __restrict__ lds, int s, int og, int src, int q0) {
   f4 drow[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) drow[i] = ld4(lds + dix(src, s, 4 * i));
+  for (int i = 0; i < 8; ++i) drow[i] = ld4(lds + L_D + dix(src, s, 4 * i));
   f4 o;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -117,7 +97,7 @@ __device__ __forceinline__ f4 relu_mask(const float* __restrict__ lds, int s, in
   return f4{a[0] > 0.f ? v[0] : 0.f, a[1] > 0.f ? v[1] : 0.f, a[2] > 0.f ? v[2] : 0.f, a[3] > 0.f ? v[3] : 0.f};
 }
 __device__ __forceinline__ void st4(float* __restrict__ lds, int b, int s, int og, f4 v) {
-  *reinterpret_cast<f4*>(lds + dix(b, s, 4 * og)) = v;
+  *reinterpret_cast<f4*>(lds + L_D + dix(b, s, 4 * og)) = v;
 }
 
 __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int s = lane, og = wv;                       // the per-sample phases: thread = (sample, 4 outputs)
-  const int K = a.K, R = a.R, S = a.n1 + a.n2, RS = R * S, L = a.L;
+  const int K = a.K, R = a.R, S = a.n1 + a.n2, L = a.L;
   const int net = a.cand_net[c], pool = a.cand_pool[c];
   // a candidate that names no network or no pool, or a pool shorter than a step, is skipped: nothing of it is read
   int skip = 0;
@@ -148,19 +128,7 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
   const float* latW = th + a.off_latW;
   const float* latb = th + a.off_latb;
   float* code = a.codes + (size_t)c * 2 * L;            // shape code, then texture code
-  // workspace of this candidate (4-byte words): z | pts | sigma | rgb | gt_rgb | gt_depth | rows | depth_mask, labels (bytes)
-  uint32_t* ws = a.ws + (size_t)c * a.ws_stride;
-  float* w_z = reinterpret_cast<float*>(ws);
-  float* w_pts = w_z + RS;
-  float* w_sig = w_pts + 3 * (size_t)RS;
-  float* w_rgb = w_sig + RS;
-  float* w_gtc = w_rgb + 3 * (size_t)RS;
-  float* w_gtd = w_gtc + 3 * R;
-  int* w_rows = reinterpret_cast<int*>(w_gtd + R);
-  uint8_t* w_dm = reinterpret_cast<uint8_t*>(w_rows + R);
-  uint8_t* w_lab = w_dm + R;
-  const uint8_t* rgbs = a.rgbs + seg0 * 4;
-  const float* depth = a.depth + seg0;
+  const Workspace ws = cnr_obj::carve(a.ws + (size_t)c * a.ws_stride, R, S);
 
   // ---- the frozen trunk into LDS: transposed weights, small parameters ------------------------------------------------------
   for (int i = tid; i < QN * H; i += THREADS) {
@@ -206,61 +174,9 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
     if (lane == 0) lds[L_SP + SP_NORM + wv] = sqrtf(ss);
   }
 
-  // ---- rows of the step, their max depth and mask counts (reduce_batch_loss's, over this candidate's R rows) ----------------
-  int flag = 0;
-  {
-    uint32_t key[6];
-    cnr_sample::epoch_perm_keys(a.seed, (uint64_t)epoch, gid, key);
-    const int hb = cnr_sample::epoch_perm_half_bits(rows_o);
-    float mx = -INFINITY;
-    int c_d = 0, c_o = 0, c_s = 0, bad = 0;
-    for (int r = tid; r < R; r += THREADS) {
-      int64_t row;
-      if (a.rows) {
-        row = a.rows[(size_t)c * R + r];
-        if (row < 0 || row >= rows_o) { row = 0; bad = 1; }
-      } else {
-        row = (int64_t)cnr_sample::epoch_perm_at(key, (uint32_t)(cursor + r), rows_o, hb);
-      }
-      w_rows[r] = (int)row;
-      const float d = depth[row];
-      const uint8_t lab = rgbs[row * 4 + 3];
-      mx = fmaxf(mx, d);
-      const bool mo = lab != 0, ms = lab != 2, md = d > a.min_bound;
-      c_d += (md && mo) ? 1 : 0; c_o += mo ? 1 : 0; c_s += ms ? 1 : 0;
-    }
-    mx = wave_max(mx);
-    for (int off = 32; off > 0; off >>= 1) {
-      c_d += __shfl_xor(c_d, off, 64); c_o += __shfl_xor(c_o, off, 64); c_s += __shfl_xor(c_s, off, 64); bad |= __shfl_xor(bad, off, 64);
-    }
-    if (lane == 0) {
-      lds[L_RED + wv] = mx; lds[L_RED + 8 + wv] = (float)c_d; lds[L_RED + 16 + wv] = (float)c_o; lds[L_RED + 24 + wv] = (float)c_s;
-      lds[L_RED + 32 + wv] = (float)bad;
-    }
-  }
-  __syncthreads();
-  float mb = lds[L_RED], n_d = 0.f, n_o = 0.f, n_s = 0.f, n_bad = 0.f;
-  for (int w = 0; w < WAVES; ++w) {   // (counts <= R: exact in fp32)
-    mb = fmaxf(mb, lds[L_RED + w]); n_d += lds[L_RED + 8 + w]; n_o += lds[L_RED + 16 + w]; n_s += lds[L_RED + 24 + w];
-    n_bad += lds[L_RED + 32 + w];
-  }
-  // a zero mask count zeroes that term and its gradient (render_rays.py:67-72 with one class), flags as cnr_obj_train's
-  const float wd = n_d == 0.f ? 0.f : 1.0f / (n_d + 1e-10f), wc = n_o == 0.f ? 0.f : 1.0f / (n_o + 1e-10f),
-              wo = n_s == 0.f ? 0.f : 1.0f / (n_s + 1e-10f);
-  flag = (n_d == 0.f ? 2 : 0) | (n_o == 0.f ? 4 : 0) | (n_s == 0.f ? 8 : 0) | (n_bad != 0.f ? 32 : 0);
-  __syncthreads();      // (RED is reused below)
-
-  // ---- a2-a5: one wave per ray (sample_common.h; z without fused multiply-adds: the reference's bits, as cnr_obj_train) -----
-  {
-    cnr_sample::SampleArgs sa{};
-    sa.rgbs = rgbs; sa.depth = depth; sa.dirs_c = a.dirs_c + seg0 * 3; sa.T = a.T + seg0 * 16;
-    sa.u = a.u ? a.u + (size_t)c * RS : nullptr; sa.g = a.g ? a.g + (size_t)c * R * a.n2 : nullptr;
-    sa.seed = a.seed; sa.world_frame = a.pool_world_frame ? (a.pool_world_frame[pool] != 0) : 0; sa.C = 1; sa.R = R; sa.n1 = a.n1;
-    sa.n2 = a.n2; sa.eps = a.eps; sa.stop_eps = a.stop_eps; sa.min_bound = a.min_bound;
-    sa.z = w_z; sa.pts = w_pts; sa.gt_rgb = w_gtc; sa.gt_depth = w_gtd; sa.depth_mask = w_dm; sa.labels = w_lab;
-    for (int r = wv; r < R; r += WAVES)
-      cnr_sample::sample_ray_at<true>(sa, r, w_rows[r], 0, gid * (uint64_t)R + (uint64_t)r, (uint64_t)rng_step * 4, mb, lane);
-  }
+  // ---- rows of the step, their max depth and mask counts; a2-a5, one wave per ray, in the pool's frame --------------------
+  const RowStats rs = select_rows(a, lds + L_RED, ws, c, seg0, rows_o, gid, cursor, epoch, tid, lane, wv);
+  sample_rays(a, ws, c, seg0, a.pool_world_frame ? (a.pool_world_frame[pool] != 0) : 0, gid, rng_step, rs.mb, lane, wv);
   __syncthreads();
 
   // d z_k[4 og + i] of this thread's samples (summed over the wave's lanes at the end); this wave's rays' loss terms
@@ -268,27 +184,12 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
   float l_d = 0.f, l_c = 0.f, l_o = 0.f;
 
   const int G = TS / S;                                  // whole rays per tile
-  const float scale = a.scale;
   for (int r0 = 0; r0 < R; r0 += G) {
     const int nrays = min(G, R - r0), ns = nrays * S;
     const size_t m0 = (size_t)r0 * S;                    // first sample of the tile
     const bool on = s < ns;
-    // ---- PE (cnr_pe_fwd's expressions): t = x / scale ; e = (t, sin(pi 2^f B_d . t))
-    float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-    if (on) {
-      const float* p = w_pts + (m0 + s) * 3;
-      t0 = p[0] / scale; t1 = p[1] / scale; t2 = p[2] / scale;
-    }
-    {
-      float* e = lds + L_ACT + s * AW;
-      if (og == 0) { e[0] = t0; e[1] = t1; e[2] = t2; }
-      for (int d = og; d < NDIR; d += WAVES) {
-        const float* Bd = lds + L_SP + SP_B + d * 3;
-        const float p = Bd[0] * t0 + Bd[1] * t1 + Bd[2] * t2;
-#pragma unroll
-        for (int f = 0; f < 6; ++f) e[3 + NDIR * f + d] = sinf((p * (float)(1 << f)) * PI_F);
-      }
-    }
+    float t0, t1, t2;
+    pe_forward(lds + L_ACT + s * AW, lds + L_SP + SP_B, on, ws.pts, m0 + s, a.scale, og, t0, t1, t2);
     __syncthreads();
     // ---- forward (src/model.py:56-84)
     layer_fwd(lds, s, og, Q_XYZ, B_XYZ, 0, 0, SP_ZERO, A_E, E1, A_P, true);               // encoding_xyz
@@ -323,33 +224,18 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
         const float* x = lds + L_ACT + s * AW + A_P;
         float v = lds[L_SP + SP_SG_B];
         for (int j = 0; j < H; ++j) v = fmaf(x[j], lds[L_SP + SP_SG_W + j], v);
-        w_sig[m0 + s] = v * 10.0f;
+        ws.sig[m0 + s] = v * 10.0f;
       } else {
         const float* x = lds + L_ACT + s * AW + A_A7;
         const float* w = lds + L_SP + SP_R2_W + (og - 1) * H2;
         float v = lds[L_SP + SP_R2_B + og - 1];
         for (int j = 0; j < H2; ++j) v = fmaf(x[j], w[j], v);
-        w_rgb[(m0 + s) * 3 + og - 1] = cnr_rl::sigmoid_exact(v);
+        ws.rgb[(m0 + s) * 3 + og - 1] = cnr_rl::sigmoid_exact(v);
       }
     }
     __syncthreads();
-    // ---- composite, loss terms and their gradient: one ray per wave (render_common.h)
-    for (int rr = wv; rr < nrays; rr += WAVES) {
-      const int ray = r0 + rr;
-      const size_t base = (size_t)ray * S;
-      const cnr_rl::RayOut q = cnr_rl::ray_small(w_sig, w_rgb, w_z, base, S, lane, w_gtd[ray], w_gtc[ray * 3 + 0], w_gtc[ray * 3 + 1],
-                                                 w_gtc[ray * 3 + 2], w_lab[ray], w_dm[ray], wd, wc, wo, a.color_scaling,
-                                                 a.opacity_scaling, 1.0f);
-      l_d += q.ld; l_c += q.lc; l_o += q.lo;
-      if (lane < S) {
-        const int sl = rr * S + lane;
-        const float c0 = w_rgb[(base + lane) * 3 + 0], c1 = w_rgb[(base + lane) * 3 + 1], c2 = w_rgb[(base + lane) * 3 + 2];
-        lds[L_DSIG + sl] = q.dsig * 10.0f;                                   // d of the raw logit
-        lds[L_DRGB + sl * 3 + 0] = q.dc0 * (c0 * (1.0f - c0));             // d of the pre-sigmoid colour
-        lds[L_DRGB + sl * 3 + 1] = q.dc1 * (c1 * (1.0f - c1));
-        lds[L_DRGB + sl * 3 + 2] = q.dc2 * (c2 * (1.0f - c2));
-      }
-    }
+    // ---- composite, loss terms and their gradient: one ray per wave
+    composite_tile(a, ws, rs, lds + L_DSIG, lds + L_DRGB, r0, nrays, S, lane, wv, l_d, l_c, l_o);
     __syncthreads();
     // ---- backward, down the activation path only: rgb.2 -> rgb.0 -> texture_layer_1 (d z3) -> encoding_viewdir + sigma.0 ->
     // encoding_shape -> shape_layer_2 (d z2) -> cat_layer (d z1) -> shape_layer_1 (d z0).  The buffers D0 / D1 alternate.
@@ -367,7 +253,7 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
     if (on) {                    // rgb.0 backward: d a6[j] = sum_{j' < 16} d a7[j'] W[j'][j], W[.][j] = row j of R0T
       f4 drow[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) drow[i] = ld4(lds + dix(0, s, 4 * i));
+      for (int i = 0; i < 4; ++i) drow[i] = ld4(lds + L_D + dix(0, s, 4 * i));
       f4 v;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -429,33 +315,22 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
       const int j = k * H + 4 * og + i;
       if (lane == 0) lds[L_SP + SP_DZ + j] = lds[L_SP + SP_ZL + j] > 0.f ? v : 0.f;
     }
-  if (lane == 0) { lds[L_RED + wv * 3 + 0] = l_d; lds[L_RED + wv * 3 + 1] = l_c; lds[L_RED + wv * 3 + 2] = l_o; }
+  stage_losses(lds + L_RED, l_d, l_c, l_o, lane, wv);
   __syncthreads();
 
-  // ---- loss values, flags and the step state (the waves' terms in a fixed order)
+  // ---- loss values, flags and the step state
   const float n_sh = lds[L_SP + SP_NORM + 0], n_tx = lds[L_SP + SP_NORM + 1];
   if (tid == 0) {
-    float sd = 0.f, sc = 0.f, so = 0.f;
-    for (int w = 0; w < WAVES; ++w) { sd += lds[L_RED + w * 3 + 0]; sc += lds[L_RED + w * 3 + 1]; so += lds[L_RED + w * 3 + 2]; }
-    sd *= wd; sc *= wc; so *= wo;
-    a.losses[c] = sd; a.losses[K + c] = sc; a.losses[2 * K + c] = so; a.losses[3 * K + c] = n_sh; a.losses[4 * K + c] = n_tx;
-    if (sd > 100000.f || sc > 100000.f || so > 100000.f) flag |= 1;
-    a.flags[c] = flag;
-    if (a.update) {              // cnr_obj_train's state rule (src/scene_cateogries.py:439-449)
-      int64_t cur = cursor + R, ep = epoch;
-      if (cur >= rows_o - R) { cur = 0; ep += 1; }
-      st[0] = cur; st[1] = rng_step + 1; st[2] = opt_step + 1; st[3] = ep;
-    }
+    const StepLoss sl = finish_losses(lds + L_RED, rs);
+    a.losses[c] = sl.d; a.losses[K + c] = sl.c; a.losses[2 * K + c] = sl.o; a.losses[3 * K + c] = n_sh; a.losses[4 * K + c] = n_tx;
+    a.flags[c] = sl.flag;
+    if (a.update) advance_state(st, cursor, rng_step, opt_step, epoch, R, rows_o);
   }
 
   // ---- latent layers backward to the codes, the code-norm regulariser (src/loss.py:5-15; zero at a zero code, as torch's norm),
-  // AdamW by each element's owner (torch.optim.AdamW, adamw_common.h's expressions)
+  // AdamW by each element's owner (torch.optim.AdamW)
   float step_size, inv_bc2_sqrt;
-  {
-    AdamArgs aa{};
-    aa.lr = a.lr; aa.b1 = a.b1; aa.b2 = a.b2;
-    adam_coefficients(aa, opt_step + 1, step_size, inv_bc2_sqrt);
-  }
+  adam_coefficients(a, opt_step + 1, step_size, inv_bc2_sqrt);
   for (int i = tid; i < 2 * L; i += THREADS) {
     const int tex = i >= L ? 1 : 0, l = i - tex * L;
     const int k0 = tex ? 3 : 0, k1 = tex ? 4 : 3;
@@ -466,20 +341,12 @@ __global__ __launch_bounds__(THREADS) void code_fit_kernel(FitArgs a) {
     const size_t e = (size_t)c * 2 * L + i;
     if (a.grad) a.grad[e] = gsum;
     if (a.update) {
-      float pi = cv * (1.0f - a.lr * a.wd);
-      const float m0 = a.exp_avg[e], v0 = a.exp_avg_sq[e];
-      const float mi = m0 + (gsum - m0) * (1.0f - a.b1);
-      const float vi = v0 * a.b2 + (1.0f - a.b2) * gsum * gsum;
-      const float denom = sqrtf(vi) * inv_bc2_sqrt + a.adam_eps;
-      pi -= step_size * (mi / denom);
-      code[i] = pi; a.exp_avg[e] = mi; a.exp_avg_sq[e] = vi;
+      const AdamElement n = adam_element(cv, a.exp_avg[e], a.exp_avg_sq[e], gsum, 1.0f - a.lr * a.wd, step_size, inv_bc2_sqrt, a.b1, a.b2,
+                                         a.adam_eps);
+      code[i] = n.p; a.exp_avg[e] = n.m; a.exp_avg_sq[e] = n.v;
     }
   }
-  // ---- the test outputs
-  if (a.sigma) for (int i = tid; i < RS; i += THREADS) a.sigma[(size_t)c * RS + i] = w_sig[i];
-  if (a.z) for (int i = tid; i < RS; i += THREADS) a.z[(size_t)c * RS + i] = w_z[i];
-  if (a.rgb) for (int i = tid; i < 3 * RS; i += THREADS) a.rgb[(size_t)c * RS * 3 + i] = w_rgb[i];
-  if (a.rows_out) for (int i = tid; i < R; i += THREADS) a.rows_out[(size_t)c * R + i] = w_rows[i];
+  copy_test_outputs(a, ws, c, tid);
 }
 
 cnr::DeviceOnce g_lds_once;
@@ -514,9 +381,5 @@ extern "C" int cnr_code_fit(const float* theta, int64_t class_stride, int64_t of
   a.b2 = beta2; a.adam_eps = adam_eps; a.wd = weight_decay; a.color_scaling = color_scaling; a.opacity_scaling = opacity_scaling;
   a.reg_scaling = reg_scaling; a.losses = losses; a.flags = flags; a.grad = grad; a.sigma = sigma; a.rgb = rgb; a.z = z;
   a.rows_out = rows_out; a.ws = static_cast<uint32_t*>(workspace); a.ws_stride = cnr_obj::ws_words(R, n1 + n2);
-  const int rc = cnr::set_max_dynamic_lds(g_lds_once, reinterpret_cast<const void*>(code_fit_kernel), LDS_BYTES);
-  if (rc) return rc;
-  hipLaunchKernelGGL(code_fit_kernel, dim3((unsigned)K), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, a);
-  CNR_LAUNCH_CHECK();
-  return CNR_OK;
+  return launch(g_lds_once, code_fit_kernel, LDS_BYTES, K, stream, a);
 }

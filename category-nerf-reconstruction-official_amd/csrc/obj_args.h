@@ -8,8 +8,30 @@ namespace cnr_obj {
 constexpr int MAX_S = 64;             // one ray per wave in the composite, whole rays per 64-sample tile
 constexpr int E_ARG = -1;             // CNR_E_ARG
 
-// 4-byte words of one object's workspace: z | pts | sigma | rgb (8 R S) | gt_rgb | gt_depth | rows (5 R) | depth_mask, labels
-// (2 R bytes); a multiple of 4 words, so that every object's block starts 16-byte aligned
+#ifdef __HIPCC__
+#define CNR_OBJ_HD __host__ __device__
+#else
+#define CNR_OBJ_HD
+#endif
+// One owner's workspace (an object of cnr_obj_train, a candidate of cnr_code_fit), the layout both kernels and the host's word
+// count share: z | pts | sigma | rgb | gt_rgb | gt_depth | rows | depth_mask, labels (bytes)
+struct Workspace { float *z, *pts, *sig, *rgb, *gtc, *gtd; int* rows; uint8_t *dm, *lab; };
+CNR_OBJ_HD inline Workspace carve(uint32_t* ws, int R, int S) {
+  const int64_t RS = (int64_t)R * S;
+  Workspace w;
+  w.z = reinterpret_cast<float*>(ws);
+  w.pts = w.z + RS;
+  w.sig = w.pts + 3 * RS;
+  w.rgb = w.sig + RS;
+  w.gtc = w.rgb + 3 * RS;
+  w.gtd = w.gtc + 3 * R;
+  w.rows = reinterpret_cast<int*>(w.gtd + R);
+  w.dm = reinterpret_cast<uint8_t*>(w.rows + R);
+  w.lab = w.dm + R;
+  return w;
+}
+// 4-byte words of carve()'s blocks: z | pts | sigma | rgb (8 R S) | gt_rgb | gt_depth | rows (5 R) | depth_mask, labels
+// (2 R bytes); a multiple of 4 words, so that every owner's block starts 16-byte aligned
 inline int64_t ws_words(int R, int S) {
   const int64_t RS = (int64_t)R * S;
   return (8 * RS + 5 * (int64_t)R + (2 * (int64_t)R + 3) / 4 + 3) & ~(int64_t)3;

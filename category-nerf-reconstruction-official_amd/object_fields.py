@@ -12,10 +12,10 @@ Coordinates: the fields take WORLD coordinates divided by ``cfg.obj_scale``, whi
 import copy
 import os
 
-import numpy as np
 import torch
 
-from . import _C, stepgraph
+from . import _C, pool_step
+from .pool_step import next_state          # (the state rule: one definition for both kernels' trainers)  # noqa: F401
 
 HIDDEN = 32
 PARAM_NAMES = ["in_layer.0.weight", "in_layer.0.bias", "mid1.0.0.weight", "mid1.0.0.bias", "cat_layer.0.weight",
@@ -23,17 +23,6 @@ PARAM_NAMES = ["in_layer.0.weight", "in_layer.0.bias", "mid1.0.0.weight", "mid1.
                "color_linear.0.weight", "color_linear.0.bias", "out_color.weight", "out_color.bias"]
 PARAM_COUNT = 11363          # cnr_obj_param_count(): the 14 tensors above at width 32, then B_layer.weight (21,3)
 CKPT_KEYS = ("FC_state_dict", "PE_state_dict", "obj_scale", "bbox")
-
-
-def next_state(state, rows, R):
-    """The host mirror of the kernel's state rule: state = [cursor, rng step, optimiser step, epoch] of one object after one
-    more step of R rays on a pool of ``rows`` rows (src/scene_cateogries.py:439-449: the epoch ends when fewer than R rows are
-    left behind the next slice)."""
-    cursor, rng, opt, epoch = state
-    cursor += R
-    if cursor >= rows - R:
-        cursor, epoch = 0, epoch + 1
-    return [cursor, rng + 1, opt + 1, epoch]
 
 
 def checkpoint_path(weight_root, obj_id, steps):
@@ -61,7 +50,7 @@ def _check(cfg, pools, obj_ids, R):
             raise ValueError(f"ObjectFieldTrainer: object {obj_id} has a pool of {rows} rows, fewer than the {R} rays of a step")
 
 
-class ObjectFieldTrainer:
+class ObjectFieldTrainer(pool_step.StepBranch):
     def __init__(self, cfg, pools, obj_ids, rays_per_step=None, seed=0, device=None):
         """``pools``: {obj_id: {rgbs (n,4) u8 [r,g,b,state], depth (n,), dirs (n,3), T_wc (n,4,4)}}, any lengths >= the rays of
         a step (default ``cfg.n_per_optim``).  Initialisation is ``Trainer``'s (xavier-normal weights, nn.Linear's biases, the
@@ -78,11 +67,7 @@ class ObjectFieldTrainer:
         self.seed = int(seed)
         self.index = {obj_id: i for i, obj_id in enumerate(self.obj_ids)}
         # ---- the pools, concatenated; object o owns rows [pool_off[o], pool_off[o + 1])
-        cat = lambda key, dt: torch.cat([pools[i][key].to(dev, dt) for i in self.obj_ids]).contiguous()
-        self.pool = dict(rgbs=cat("rgbs", torch.uint8), depth=cat("depth", torch.float32), dirs=cat("dirs", torch.float32),
-                         T=cat("T_wc", torch.float32))
-        self.rows = [int(pools[i]["depth"].shape[0]) for i in self.obj_ids]
-        self.pool_off = torch.tensor(np.concatenate([[0], np.cumsum(self.rows)]), dtype=torch.int64, device=dev)
+        self.pool, self.rows, self.pool_off = pool_step.concat_pools([pools[i] for i in self.obj_ids], "T_wc", dev)
         self.ids = torch.tensor([int(i) & 0x7FFFFFFF for i in self.obj_ids], dtype=torch.int32, device=dev)
         # ---- parameters, moments, state: flat (N, ...) device buffers; the modules' tensors are views of theta
         lib = _C.load()
@@ -98,7 +83,7 @@ class ObjectFieldTrainer:
         self._modules = {}
         for o, obj_id in enumerate(self.obj_ids):
             with torch.random.fork_rng(devices=[]):
-                torch.manual_seed((self.seed * 7919 + 104729 * (int(obj_id) + 1)) & 0x7FFFFFFFFFFF)
+                torch.manual_seed(pool_step.instance_seed(self.seed, obj_id))
                 t = trainer_mod.Trainer(tcfg, 0, [0])
             fc, pe = t.fc_occ_map, t.pe
             assert [k for k, _ in fc.named_parameters()] == PARAM_NAMES and [tuple(p.shape) for p in pe.parameters()] == [(21, 3)]
@@ -111,8 +96,7 @@ class ObjectFieldTrainer:
                 off += k
             assert off == PARAM_COUNT
             self._modules[obj_id] = (pe, fc)
-        self.steps_done = 0
-        self._sched = stepgraph.StepGraphs([self], 3, 8)
+        self._init_steps()
 
     # ---- one launch = one step of every object ---------------------------------------------------------------------------------
     def launch(self, rows=None, u=None, g=None, grad=None, sigma=None, rgb=None, z=None, rows_out=None):
@@ -125,26 +109,6 @@ class ObjectFieldTrainer:
                 0.999, 1e-8, float(cfg.weight_decay), 5.0, 10.0, self._losses, self.flags, grad, sigma, rgb, z, rows_out, self.ws,
                 self.ws.numel())
 
-    # ---- the branch interface of stepgraph.StepGraphs ----------------------------------------------------------------------------
-    parity = 0                # one state copy; a captured step depends on nothing the host changes
-
-    def record(self, slot=None, par=0):
-        self.launch()
-
-    def before_step(self):
-        return 1 << 30        # every object ends its epochs on the device: no step ever waits for the host
-
-    def advance(self, U=1):
-        self.steps_done += U
-
-    def step(self, use_graph=True):
-        """One step of every object; after three eager steps it is captured and replayed."""
-        self._sched.step(use_graph)
-
-    def run(self, n, unroll=8, use_graph=True):
-        """``n`` steps, the same arithmetic as ``n`` calls of ``step()``, in graphs of up to ``unroll`` steps."""
-        self._sched.run(n, unroll, use_graph)
-
     @property
     def losses(self):
         """(3, N): the depth / colour / opacity terms of every object's last step (src/loss.py:18-74), on the device"""
@@ -153,10 +117,6 @@ class ObjectFieldTrainer:
     def modules(self, obj_id):
         """(UniDirsEmbed, OccupancyMap) of one object; their parameters are views of the live flat buffer (no copy-back)"""
         return self._modules[obj_id]
-
-    def state(self):
-        """(N,4) host list of [cursor, rng step, optimiser step, epoch]; synchronises"""
-        return self.d_state.cpu().tolist()
 
     # ---- checkpoints -----------------------------------------------------------------------------------------------------------
     def save_checkpoints(self, weight_root, bboxes=None):
@@ -173,16 +133,7 @@ class ObjectFieldTrainer:
         return files
 
     # ---- from a loaded dataset ---------------------------------------------------------------------------------------------------
-    @staticmethod
-    def crops_of(inst_dict):
-        """[(obj_id, [(frame, w0, w1, h0, h1), ...])] of every instance of every object class of a dataset's ``inst_dict``"""
-        out = []
-        for cls_id, entries in inst_dict.items():
-            if cls_id == 0:
-                continue
-            for obj_id, info in entries.items():
-                out.append((obj_id, [(fi["frame"],) + tuple(int(v) for v in fi["bbox"]) for fi in info["frame_info"]]))
-        return out
+    crops_of = staticmethod(pool_step.crops_of)
 
     @staticmethod
     def pool_rows(inst_dict):
@@ -195,39 +146,9 @@ class ObjectFieldTrainer:
         """{obj_id: pool} by the gather ``sceneCategory`` uses for a single-instance class (src/scene_cateogries.py:164-260): world
         frame (every row carries its frame's T_wc), the crops of ``frame_info``, this / other / unknown pixel states -- ONE
         cnr_gather_pool launch for all objects.  No global shuffle: the kernel's per-epoch bijection orders the rows."""
-        from .scene_cateogries import cameraInfo
-        dev = torch.device(device or dataset._parse_device())
-        sample_dict = dataset.sample_dict
-        per_obj = cls.crops_of(dataset.inst_dict)
-        frames = sorted({c[0] for _, crops in per_obj for c in crops})
-        slot = {f: i for i, f in enumerate(frames)}
-        stack = lambda key, dt: torch.from_numpy(np.stack([np.asarray(sample_dict[f][key]) for f in frames])).to(dt)
-        images = stack("image", torch.uint8).to(dev).contiguous()
-        depths = stack("depth", torch.float32).to(dev).contiguous()
-        masks = stack("obj_mask", torch.int32).to(dev).contiguous()
-        T_wc = stack("T", torch.float32).to(dev)
-        W, H = images.shape[1:3]
-        rays = cameraInfo(cfg, device=dev).rays_dir_cache.contiguous()
-        crops, areas, pose_slot, n_rows = [], [], [], []
-        for obj_id, cr in per_obj:
-            for idx, (frame, w0, w1, h0, h1) in enumerate(cr):
-                crops.append([slot[frame], int(obj_id), 0, w0, w1, h0, h1, idx])
-                areas.append((w1 - w0) * (h1 - h0))
-                pose_slot.append(slot[frame])
-            n_rows.append(sum(areas[-len(cr):]) if cr else 0)
-        N = int(sum(areas))
-        crops_t = torch.tensor(crops, dtype=torch.int32, device=dev)
-        off_t = torch.tensor(np.concatenate([[0], np.cumsum(areas)]), dtype=torch.int64, device=dev)
-        T_crop = T_wc[torch.tensor(pose_slot, device=dev)].contiguous()
-        rgbs = torch.empty(N, 4, dtype=torch.uint8, device=dev)
-        depth, dirs, T_rows = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 4, 4, device=dev)
-        _C.call("cnr_gather_pool", images, depths, masks, rays, T_crop, crops_t, off_t, None, int(W), int(H), len(crops), N,
-                rgbs, depth, dirs, T_rows, None, None)
-        pools, at = {}, 0
-        for (obj_id, _), n in zip(per_obj, n_rows):
-            pools[obj_id] = dict(rgbs=rgbs[at:at + n], depth=depth[at:at + n], dirs=dirs[at:at + n], T_wc=T_rows[at:at + n])
-            at += n
-        return pools
+        per_obj = [(obj_id, [c + (idx,) for idx, c in enumerate(cr)]) for obj_id, cr in cls.crops_of(dataset.inst_dict)]
+        return pool_step.gather_pools(dataset, cfg, per_obj, lambda obj_id, T_wc: T_wc, "T_wc",
+                                      torch.device(device or dataset._parse_device()))
 
     @classmethod
     def from_dataset(cls, dataset, cfg, rays_per_step=None, seed=0, device=None):
