@@ -485,7 +485,161 @@ __global__ __launch_bounds__(64) void composite_kernel(const float* __restrict__
   }
 }
 
+// ---- surface normals -------------------------------------------------------------------------------
+// The winning segment of a pixel by composite_kernel's rule: the largest mass of its pix_segs row, the earlier one among equals;
+// none when the row is empty or the pixel is not opaque enough.  -> the entity, or -1
+__device__ __forceinline__ int surface_entity(const float* __restrict__ mass, const int* __restrict__ pix_segs,
+                                              const int* __restrict__ seg_entity, const float* __restrict__ opacity, float thr,
+                                              int64_t p) {
+  float best = -1.0f;
+  int best_seg = pix_segs[p * KMAX];                      // (the first one when no mass compares above -1, as there)
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) {
+    const int sg = pix_segs[p * KMAX + j];
+    if (sg < 0) break;
+    const float m = mass[p * KMAX + j];
+    if (m > best) { best = m; best_seg = sg; }
+  }
+  if (best_seg < 0 || !(opacity[p] >= thr)) return -1;
+  return seg_entity[best_seg];
+}
+
+// per wave of 64 pixels and field run: the number of pixels whose surface lies in an entity of that run
+__global__ __launch_bounds__(256) void surface_count_kernel(const float* __restrict__ mass, const int* __restrict__ pix_segs,
+                                                            const int* __restrict__ seg_entity, const float* __restrict__ opacity,
+                                                            float thr, const int* __restrict__ entity_run, int64_t P, int n_runs,
+                                                            int* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = n_waves(P);
+  const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= nw) return;
+  const int64_t p = wv * 64 + lane;
+  const int e = p < P ? surface_entity(mass, pix_segs, seg_entity, opacity, thr, p) : -1;
+  const int run = e >= 0 ? entity_run[e] : -1;
+  for (int r = 0; r < n_runs; ++r) {
+    const unsigned long long m = __ballot(run == r);
+    if (lane == 0) counts[(int64_t)r * nw + wv] = __popcll(m);
+  }
+}
+
+// one block: exclusive scan of the (n_runs * nw) counts in (run, wave) order; run_offset (n_runs + 1)
+__global__ __launch_bounds__(1024) void surface_scan_kernel(const int* __restrict__ counts, int64_t nw, int n_runs,
+                                                            int64_t* __restrict__ offsets, int64_t* __restrict__ run_offset) {
+  __shared__ int64_t part[cnr::SCAN_THREADS];
+  const int t = threadIdx.x;
+  cnr::scan_block_counts<1>(counts, nw * n_runs, offsets, run_offset + n_runs, part);
+  __syncthreads();
+  for (int r = t; r < n_runs; r += 1024) run_offset[r] = offsets[(int64_t)r * nw];
+}
+
+__global__ __launch_bounds__(256) void surface_emit_kernel(const float* __restrict__ T_wc, const float* __restrict__ dirs,
+                                                           const float* __restrict__ to_field, const float* __restrict__ depth,
+                                                           const float* __restrict__ opacity, float thr,
+                                                           const float* __restrict__ mass, const int* __restrict__ pix_segs,
+                                                           const int* __restrict__ seg_entity, const int* __restrict__ entity_run,
+                                                           const int* __restrict__ entity_row, int64_t P, int n_runs,
+                                                           const int64_t* __restrict__ offsets, int* __restrict__ surf_entity,
+                                                           int* __restrict__ surf_slot, float* __restrict__ surf_pts,
+                                                           float* __restrict__ list_pts, int* __restrict__ list_row) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = n_waves(P);
+  const int64_t wv = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= nw) return;
+  const int64_t p = wv * 64 + lane;
+  const bool live = p < P;
+  const int e = live ? surface_entity(mass, pix_segs, seg_entity, opacity, thr, p) : -1;
+  const int run = e >= 0 ? entity_run[e] : -1;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int64_t slot = -1;
+  for (int r = 0; r < n_runs; ++r) {
+    const unsigned long long m = __ballot(run == r);
+    if (run == r) slot = offsets[(int64_t)r * nw + wv] + __popcll(m & below);
+  }
+  if (!live) return;
+  float f[3] = {0.f, 0.f, 0.f};
+  if (e >= 0 && slot >= 0 && slot < P) {
+    // cnr_view_points' expressions at z = the rendered depth
+    const Cam cam = load_cam(T_wc);
+    const float z = depth[p];
+    const float cx = z * dirs[p * 3 + 0], cy = z * dirs[p * 3 + 1], cz = z * dirs[p * 3 + 2];
+    float w[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = cam.r[k * 3 + 0] * cx + cam.r[k * 3 + 1] * cy + cam.r[k * 3 + 2] * cz + cam.t[k];
+    affine_point(to_field + (int64_t)e * 12, w[0], w[1], w[2], f);
+    list_pts[slot * 3 + 0] = f[0]; list_pts[slot * 3 + 1] = f[1]; list_pts[slot * 3 + 2] = f[2];
+    list_row[slot] = entity_row[e];
+  }
+  surf_entity[p] = e;
+  surf_slot[p] = (e >= 0 && slot >= 0 && slot < P) ? (int)slot : -1;
+  surf_pts[p * 3 + 0] = f[0]; surf_pts[p * 3 + 1] = f[1]; surf_pts[p * 3 + 2] = f[2];
+}
+
+// n = -A^T g / |A^T g|, A = to_field[entity][:, :3], g = the field-frame gradient at the pixel's slot of the compact list
+__global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ grad_c, const int* __restrict__ surf_slot,
+                                                      const int* __restrict__ surf_entity, const float* __restrict__ to_field,
+                                                      int64_t P, int64_t M, float* __restrict__ normal) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int slot = surf_slot[p], e = surf_entity[p];
+  float v[3] = {0.f, 0.f, 0.f};
+  if (slot >= 0 && slot < M && e >= 0) {
+    const float* A = to_field + (int64_t)e * 12;
+    const float g0 = grad_c[(int64_t)slot * 3 + 0], g1 = grad_c[(int64_t)slot * 3 + 1], g2 = grad_c[(int64_t)slot * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] = -(A[0 * 4 + k] * g0 + A[1 * 4 + k] * g1 + A[2 * 4 + k] * g2);
+    // scaled by the largest component first: the squares of a gradient of 1e-20 or 1e20 neither vanish nor overflow
+    const float big = fmaxf(fabsf(v[0]), fmaxf(fabsf(v[1]), fabsf(v[2])));
+    if (big > 0.0f && fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]) < INFINITY) {      // (false for a NaN or an infinite component)
+      const float a = v[0] / big, b = v[1] / big, c = v[2] / big;
+      const float len = sqrtf(a * a + b * b + c * c);
+      v[0] = a / len; v[1] = b / len; v[2] = c / len;
+    } else {
+      v[0] = 0.f; v[1] = 0.f; v[2] = 0.f;
+    }
+  }
+  normal[p * 3 + 0] = v[0]; normal[p * 3 + 1] = v[1]; normal[p * 3 + 2] = v[2];
+}
+
 }  // namespace
+
+extern "C" int64_t cnr_view_surface_workspace_bytes(int64_t P, int n_runs) {
+  if (P <= 0 || n_runs <= 0) return 0;
+  return ws_counts_bytes(P, n_runs) + n_waves(P) * n_runs * 8;
+}
+
+extern "C" int cnr_view_surface_points(const float* T_wc, const float* dirs, const float* to_field, const float* depth,
+                                       const float* opacity, float opacity_threshold, const float* mass, const int* pix_segs,
+                                       const int* seg_entity, const int* entity_run, const int* entity_row, int64_t P, int n_runs,
+                                       void* workspace, int64_t* run_offset, int* surf_entity, int* surf_slot, float* surf_pts,
+                                       float* list_pts, int* list_row, void* stream) {
+  if (!T_wc || !dirs || !to_field || !depth || !opacity || !mass || !pix_segs || !seg_entity || !entity_run || !entity_row ||
+      !workspace || !run_offset || !surf_entity || !surf_slot || !surf_pts || !list_pts || !list_row || P <= 0 || n_runs <= 0)
+    return CNR_E_ARG;
+  if (P >= (1ll << 31) || n_runs > 32767) return CNR_E_SHAPE;
+  const int64_t nw = n_waves(P);
+  int* counts = static_cast<int*>(workspace);
+  int64_t* offsets = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + ws_counts_bytes(P, n_runs));
+  hipLaunchKernelGGL(surface_count_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mass, pix_segs,
+                     seg_entity, opacity, opacity_threshold, entity_run, P, n_runs, counts);
+  CNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(surface_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, nw, n_runs, offsets, run_offset);
+  CNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(surface_emit_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, (hipStream_t)stream, T_wc, dirs, to_field,
+                     depth, opacity, opacity_threshold, mass, pix_segs, seg_entity, entity_run, entity_row, P, n_runs, offsets,
+                     surf_entity, surf_slot, surf_pts, list_pts, list_row);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_view_normals(const float* grad_c, const int* surf_slot, const int* surf_entity, const float* to_field,
+                                int64_t P, int64_t M, float* normal, void* stream) {
+  if (!surf_slot || !surf_entity || !to_field || !normal || P <= 0 || M < 0 || (M > 0 && !grad_c)) return CNR_E_ARG;
+  if ((P + 255) / 256 >= (1ll << 31)) return CNR_E_SHAPE;
+  hipLaunchKernelGGL(normals_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grad_c, surf_slot,
+                     surf_entity, to_field, P, M, normal);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
 
 extern "C" int64_t cnr_view_segments_workspace_bytes(int64_t P, int E) {
   if (P <= 0 || E <= 0) return 0;

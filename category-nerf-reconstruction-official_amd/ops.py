@@ -458,3 +458,65 @@ class FusedFieldFn(Function):
                   ctx.scale, d_sig.contiguous(), d_rgb.contiguous(), ctx.gs, dtrunk, dB, dbr, C, R, S, ctx.rpc, ctx.mb,
                   wsp, packed_lo=lo if lo.numel() else None)
         return None, dB, dtrunk, dbr, None, None, None, None, None, None
+
+
+# ================================================================================================
+# field gradients: sigma (the x10 occupancy logit) and d sigma / d x  (csrc/field_grad.hip)
+# ================================================================================================
+OCCMAP_GRAD_HIDDEN = (32, 128)      # the hidden sizes cnr_occmap_grad is built for
+
+
+def _grad_points(pts):
+    if not torch.is_tensor(pts) or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("pts must be a (N,3) tensor, not {}".format(tuple(pts.shape) if torch.is_tensor(pts) else type(pts).__name__))
+    return pts.detach().float().contiguous()
+
+
+def field_grad(pts, B, trunk, brows, row, scale):
+    """One CodeNeRF category's geometry branch at pts (N,3) in the field frame -> (sigma (N,), grad (N,3) = d sigma / d pts).
+    B (21,3) (or (1,21,3)), trunk (13892,) (or (1,13892)) the fp32 blob in TRUNK_LAYERS order, brows (rows,4,32) effective bias
+    rows (bias_rows), row (N,) int32 = every point's row of brows, or None for row 0.  No autograd: both outputs are plain
+    values (cnr_field_grad, forward mode)."""
+    pts = _grad_points(pts)
+    N = pts.shape[0]
+    if B.numel() != 63 or trunk.numel() != TRUNK_PARAMS:
+        raise ValueError("B must hold 21 x 3 and trunk {} values".format(TRUNK_PARAMS))
+    if brows.dim() != 3 or tuple(brows.shape[1:]) != (NLAT, W) or brows.shape[0] < 1:
+        raise ValueError("brows must be (rows,4,32), not {}".format(tuple(brows.shape)))
+    if not float(scale) != 0.0:
+        raise ValueError("scale must not be zero")
+    if row is not None:
+        if row.dtype != torch.int32 or row.dim() != 1 or row.shape[0] != N:
+            raise ValueError("row must be int32 of shape ({},)".format(N))
+        if N and not (0 <= int(row.min()) and int(row.max()) < brows.shape[0]):       # the kernel indexes brows with it
+            raise ValueError("row must lie in 0 .. {}".format(brows.shape[0] - 1))
+        row = row.contiguous()
+    sigma, grad = torch.empty(N, device=pts.device), torch.empty(N, 3, device=pts.device)
+    if N:
+        _C.call("cnr_field_grad", pts, row, B.detach().float().contiguous(), trunk.detach().float().contiguous(),
+                brows.detach().float().contiguous(), float(scale), N, sigma, grad)
+    return sigma, grad
+
+
+def occmap_theta(fc):
+    """the flat concatenation of an OccupancyMap's parameters in registration order (cnr_occmap_grad's theta)"""
+    return torch.cat([p.detach().reshape(-1) for p in fc.parameters()]).float().contiguous()
+
+
+def occmap_grad(fc, pe, pts):
+    """An OccupancyMap ``fc`` behind the embedding ``pe`` at pts (N,3) -> (sigma (N,), grad (N,3) = d sigma / d pts).  Hidden
+    sizes 32 and 128 (one hidden block) run cnr_occmap_grad; any other goes through autograd over the modules (same values, many launches)."""
+    pts = _grad_points(pts)
+    N = pts.shape[0]
+    H = fc.out_alpha.weight.shape[1]
+    if H in OCCMAP_GRAD_HIDDEN and len(fc.mid1) == 1 and len(fc.mid2) == 1:
+        sigma, grad = torch.empty(N, device=pts.device), torch.empty(N, 3, device=pts.device)
+        if N:
+            _C.call("cnr_occmap_grad", pts, occmap_theta(fc), pe.B_layer.weight.detach().float().contiguous(), int(H),
+                    float(pe._scale), N, sigma, grad)
+        return sigma, grad
+    with torch.enable_grad():
+        x = pts.clone().requires_grad_(True)
+        sigma = fc(pe(x[:, None, :]), do_color=False)[0].reshape(-1)
+        grad, = torch.autograd.grad(sigma.sum(), x)
+    return sigma.detach(), grad.detach()

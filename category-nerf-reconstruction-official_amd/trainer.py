@@ -57,9 +57,14 @@ class Trainer:
         self.shape_codes = self.shape_codes.to(self.device)
         self.texture_codes = self.texture_codes.to(self.device)
 
-    def meshing(self, inst_id=None, grid_dim=256):
+    def meshing(self, inst_id=None, grid_dim=256, normals="grid"):
         """src/trainer.py:62-123: occupancy on a grid_dim^3 grid over the object's box, marching cubes at 0.5 ('ascent'),
-        back to scene coordinates, vertex colours from eval_points.  None where the reference returns None."""
+        back to scene coordinates, vertex colours from eval_points.  None where the reference returns None.
+        normals: "grid" = the lattice differences marching cubes interpolates (skimage's, faceted on a coarse grid); "field" =
+        the field's own gradient at every vertex (eval_gradient), normalised, pointing towards increasing occupancy as the grid
+        normals do (vis.py); a vertex whose gradient is exactly zero keeps its grid normal."""
+        if normals not in ("grid", "field"):
+            raise ValueError("normals must be 'grid' or 'field', not {!r}".format(normals))
         occ_range = [-1., 1.]
         range_dist = occ_range[1] - occ_range[0]
         boxed = self.cls_id == 0 or self.n_obj == 1
@@ -101,7 +106,34 @@ class Trainer:
             return None
         _, color = ret
         mesh.visual.vertex_colors = (color * 255).detach().squeeze(0).cpu().numpy().astype(np.uint8)
+        if normals == "field":
+            # the mesh has been moved to the coordinates the field takes (eval_points reads its vertices as they are), so the
+            # map from vertex to field point is the identity and M^T grad sigma is grad sigma itself
+            _, g = self.eval_gradient(vertices_pts, inst_id=inst_id)
+            g = g.double().cpu().numpy()
+            ln = np.linalg.norm(g, axis=1, keepdims=True)
+            ok = (ln > 0) & np.isfinite(ln)
+            mesh.vertex_normals = np.where(ok, g / np.where(ok, ln, 1.0), mesh.vertex_normals)
         return mesh
+
+    def eval_gradient(self, points, inst_id=None, chunk_size=500000):
+        """The companion of eval_points: (sigma (N,), grad (N,3)) at (N,3) points in the frame eval_points takes them in --
+        sigma the x10 occupancy logit (occupancy = sigmoid(sigma)), grad = d sigma / d points.  One cnr_field_grad /
+        cnr_occmap_grad launch per chunk (exact fp32, forward mode: DESIGN.md section 3.15); no autograd graph is built."""
+        from . import ops
+        sigma, grad = [], []
+        with torch.no_grad():
+            if self.cls_id != 0:
+                trunk, B, brows = self._codenerf_rows(inst_id)
+            for k in range(0, max(points.shape[0], 1), chunk_size):
+                pts = points[k:k + chunk_size].float().contiguous()
+                if self.cls_id != 0:
+                    s, g = ops.field_grad(pts, B, trunk, brows, None, self.pe._scale)
+                else:
+                    s, g = ops.occmap_grad(self.fc_occ_map, self.pe, pts)
+                sigma.append(s)
+                grad.append(g)
+        return torch.cat(sigma), torch.cat(grad)
 
     def _codenerf_rows(self, inst_id):
         """(trunk (1,13892), B (1,21,3), bias rows (1,4,32)) of one object of this CodeNeRF category"""

@@ -165,15 +165,51 @@ class SceneRenderer:
         return self._dirs
 
     def _category_operands(self, cats):
-        """{category index: (B, packed, packed_lo, bias rows (n_obj,4,32), scale)} of the categories in use"""
+        """{category index: (B, packed, packed_lo, bias rows (n_obj,4,32), scale, trunk)} of the categories in use"""
         out = {}
         for k in cats:
             t = self.categories[k].trainer
             rows = [t._codenerf_rows(i) for i in self.categories[k].obj_ids]
             trunk, B = rows[0][0], rows[0][1]
             brows = torch.cat([r[2] for r in rows], 0).contiguous()
-            out[k] = (B, ops.pack_weights(trunk), ops.pack_weights_lo(trunk), brows, float(t.pe._scale))
+            out[k] = (B, ops.pack_weights(trunk), ops.pack_weights_lo(trunk), brows, float(t.pe._scale), trunk)
         return out
+
+    def _surface_normals(self, T, dirs, to_field, runs, row_of, operands, thr, depth, opacity, mass, pix_segs, seg_entity, normal):
+        """The normal image of one chunk, after its composite: surface points bucketed by field run (cnr_view_surface_points),
+        one gradient launch per run (cnr_field_grad / cnr_occmap_grad), then n = -A^T g / |A^T g| per pixel (cnr_view_normals).
+        -> (surf_entity (P,), surf_pts (P,3))"""
+        dev, P, R = self.device, dirs.shape[0], len(runs)
+        ent_run = torch.empty(to_field.shape[0], dtype=torch.int32)
+        for r, (_, a, b) in enumerate(runs):
+            ent_run[a:b] = r
+        ent_run = ent_run.to(dev)
+        ws = _C.workspace(_C.load().cnr_view_surface_workspace_bytes(P, R), dev, "cnr_view_surface")
+        run_off = torch.empty(R + 1, device=dev, dtype=torch.int64)
+        surf_entity, surf_slot = torch.empty(P, device=dev, dtype=torch.int32), torch.empty(P, device=dev, dtype=torch.int32)
+        surf_pts, list_pts = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
+        list_row = torch.empty(P, device=dev, dtype=torch.int32)
+        _C.call("cnr_view_surface_points", T, dirs, to_field, depth, opacity, float(thr), mass, pix_segs, seg_entity, ent_run, row_of,
+                P, R, ws, run_off, surf_entity, surf_slot, surf_pts, list_pts, list_row)
+        self._mark("surface points")
+        off = run_off.tolist()
+        M = off[R]
+        grad_c = torch.empty(max(M, 1), 3, device=dev)
+        for r, (cat, _, _) in enumerate(runs):
+            m0, m1 = off[r], off[r + 1]
+            if m1 == m0:
+                continue
+            if cat < 0:
+                t = self.scene_bg.trainer
+                _, g = ops.occmap_grad(t.fc_occ_map, t.pe, list_pts[m0:m1])
+            else:
+                B, _, _, brows, scale, trunk = operands[cat]
+                _, g = ops.field_grad(list_pts[m0:m1], B, trunk, brows, list_row[m0:m1], scale)
+            grad_c[m0:m1] = g
+            self._mark("gradient background" if cat < 0 else "gradient category {}".format(cat))
+        _C.call("cnr_view_normals", grad_c, surf_slot, surf_entity, to_field, P, M, normal)
+        self._mark("normals")
+        return surf_entity, surf_pts
 
     # ---- occupancy grids -------------------------------------------------------------------------------------------------
     def lattice_occupancy(self, index, dim):
@@ -266,13 +302,17 @@ class SceneRenderer:
         return bits
 
     def render(self, T_wc, n_samples=64, transforms=None, hidden=(), chunk=65536, opacity_threshold=0.5, return_samples=False,
-               skip_empty=False):
+               skip_empty=False, normals=False):
         """-> {rgb (W,H,3), depth, opacity, var (W,H) float32, instance (W,H) int32 (-1: nothing opaque enough)}; (W,H,...) as
         every image here.  Pixels go through in chunks of ``chunk``; the result does not depend on it.  A pixel met by more
         than 8 boxes raises ValueError.  ``return_samples``: also the intermediate arrays (single chunk only).
         ``skip_empty``: evaluate the fields only where the occupancy grids are set (ValueError without grids): the same
         render with the occupancy of every other sample set to zero.  ``self.active_samples`` then holds (samples evaluated,
-        samples of all segments), and the returned samples' ``pts`` is the compact list (M,3) that ``active_idx`` indexes."""
+        samples of all segments), and the returned samples' ``pts`` is the compact list (M,3) that ``active_idx`` indexes.
+        ``normals``: the result gains ``normal`` (W,H,3): the world-frame unit vector out of the surface (towards decreasing
+        occupancy) at the rendered depth, from the gradient of the field whose segment gave the pixel its label, taken through
+        the *edited* entity's transform; exactly zero where ``instance`` is -1 or the gradient vanishes.  The samples then
+        gain ``surface_pts`` (P,3), field frame, and ``surface_entity`` (P,), -1 for none."""
         S, dev = int(n_samples), self.device
         if not 1 <= S <= SMAX:
             raise ValueError("n_samples must be in 1 .. {}".format(SMAX))
@@ -283,6 +323,8 @@ class SceneRenderer:
         out = dict(rgb=torch.zeros(P_all, 3, device=dev), depth=torch.zeros(P_all, device=dev),
                    opacity=torch.zeros(P_all, device=dev), var=torch.zeros(P_all, device=dev),
                    instance=torch.full((P_all,), -1, device=dev, dtype=torch.int32))
+        if normals:
+            out["normal"] = torch.zeros(P_all, 3, device=dev)
         shape = lambda r: {k: v.reshape(self.W, self.H, *v.shape[1:]) for k, v in r.items()}
         if not ents:
             return shape(out)
@@ -352,7 +394,7 @@ class SceneRenderer:
                         if cat < 0:
                             sg, cl = _bg_logits(self.scene_bg.trainer, pts[m0:m1])
                         else:
-                            B, packed, lo, brows, scale = operands[cat]
+                            B, packed, lo, brows, scale, _ = operands[cat]
                             sg, cl = ops.field_fwd(pts[m0:m1].reshape(1, (m1 - m0) // 64, 64, 3), B, packed, brows,
                                                    block_row[m0 // 64:m1 // 64].reshape(1, -1), scale, packed_lo=lo)
                         sigma_c[m0:m1], color_c[m0:m1] = sg.reshape(-1), cl.reshape(-1, 3)
@@ -372,7 +414,7 @@ class SceneRenderer:
                         if cat < 0:
                             sg, cl = _bg_logits(self.scene_bg.trainer, pts[s0:s1].reshape(-1, 3))
                         else:
-                            B, packed, lo, brows, scale = operands[cat]
+                            B, packed, lo, brows, scale, _ = operands[cat]
                             ray_row = row_of[seg_entity[s0:s1].long()].reshape(1, -1).contiguous()
                             sg, cl = ops.field_fwd(pts[s0:s1].reshape(1, s1 - s0, S, 3), B, packed, brows, ray_row, scale, packed_lo=lo)
                         sigma[s0:s1], color[s0:s1] = sg.reshape(-1, S), cl.reshape(-1, S, 3)
@@ -382,12 +424,18 @@ class SceneRenderer:
                 _C.call("cnr_view_composite", sigma, color, z, pix_segs, seg_entity, inst, P, S, float(opacity_threshold),
                         out["rgb"][sl], out["depth"][sl], out["opacity"][sl], out["var"][sl], mass, out["instance"][sl])
                 self._mark("composite")
+                if normals:
+                    surf_entity, surf_pts = self._surface_normals(T, dirs, to_field, runs, row_of, operands, opacity_threshold,
+                                                                  out["depth"][sl], out["opacity"][sl], mass, pix_segs, seg_entity,
+                                                                  out["normal"][sl])
                 if return_samples:
                     out["samples"] = dict(seg_pixel=seg_pixel[:N], seg_entity=seg_entity[:N], seg_z=seg_z[:N], entity_offset=ent_off,
                                           pix_segs=pix_segs, z=z, pts=pts, sigma=sigma, color=color, mass=mass,
                                           to_box=to_box, to_field=to_field, inst_ids=inst)
                     if skip_empty:
                         out["samples"].update(active_idx=active_idx[:M], active_offset=act_off, block_row=block_row[:M // 64])
+                    if normals:
+                        out["samples"].update(surface_pts=surf_pts, surface_entity=surf_entity)
         samples = out.pop("samples", None)
         res = shape(out)
         if samples is not None:
@@ -396,7 +444,8 @@ class SceneRenderer:
 
 
 def render_to_files(result, out_dir):
-    """rgb.png (8 bit), depth.png (16 bit, millimetres) and instance.png (16 bit, -1 as 65535), transposed back to H x W."""
+    """rgb.png (8 bit), depth.png (16 bit, millimetres) and instance.png (16 bit, -1 as 65535), transposed back to H x W; with a
+    ``normal`` image in the result also normal.png (8 bit, n * 0.5 + 0.5)."""
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
     rgb = (result["rgb"].detach().clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy().transpose(1, 0, 2)
@@ -407,3 +456,24 @@ def render_to_files(result, out_dir):
     if inst.max(initial=-1) >= 65535:
         raise ValueError("instance ids above 65534 do not fit a 16-bit image")
     Image.fromarray(np.ascontiguousarray(np.where(inst < 0, 65535, inst).astype(np.uint16))).save(os.path.join(out_dir, "instance.png"))
+    if "normal" in result:
+        Image.fromarray(encode_normals(result["normal"]), "RGB").save(os.path.join(out_dir, "normal.png"))
+
+
+def encode_normals(normal):
+    """normal (W,H,3) in [-1,1] -> (H,W,3) uint8 = round((n * 0.5 + 0.5) * 255); the zero vector (no surface) is grey 128"""
+    n = (normal.detach().float().cpu().clamp(-1, 1) * 0.5 + 0.5) * 255
+    return np.ascontiguousarray(n.round().to(torch.uint8).numpy().transpose(1, 0, 2))
+
+
+def shade(result, T_wc):
+    """A grey headlight Lambert image (W,H,3) float32 in [0,1] from a render made with ``normals=True``: max(0, -n . v), v the
+    view direction = the camera's optical axis in the world frame (the third column of ``T_wc``'s rotation, normalised: a
+    light at the camera, parallel rays).  Zero where the normal is zero or faces away."""
+    if "normal" not in result:
+        raise ValueError("shade wants a render made with normals=True")
+    n = result["normal"].detach().float()
+    T = np.asarray(T_wc.detach().cpu() if torch.is_tensor(T_wc) else T_wc, np.float64).reshape(4, 4)
+    v = T[:3, 2] / np.linalg.norm(T[:3, 2])
+    lam = (-(n * torch.as_tensor(v, dtype=torch.float32, device=n.device)).sum(-1)).clamp(min=0.0)
+    return lam[..., None].expand(*lam.shape, 3).contiguous()

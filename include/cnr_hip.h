@@ -1179,6 +1179,49 @@ int cnr_code_fit(const float* theta, int64_t class_stride, int64_t off_trunk, in
                  float* grad, float* sigma, float* rgb, float* z, int* rows_out, void* workspace, int64_t workspace_bytes,
                  void* stream);
 
+/* ---- field gradients: the x10 occupancy logit sigma and its spatial derivative d sigma / d x (csrc/field_grad.hip; DESIGN.md
+ * section 3.15).  Forward mode: the value and its three tangents pass through every layer together, T' = mask . (W T), so sigma
+ * comes out on the way and nothing is stashed.  Exact fp32 on the vector unit: fp32 products and sums, accurate sinf / cosf (the
+ * arguments reach 8 pi |x / scale|), ReLU'(0) = 0.  No atomics, and a point's arithmetic does not depend on N, on its place in
+ * the array or on its neighbours: outputs are bit-identical run to run and for any split of the points into calls.  Any N >= 1;
+ * N = 0 returns CNR_OK and launches nothing; pointers of N = 0 are not looked at.  sigma (N,) may be NULL; grad (N,3).
+ *
+ * cnr_field_grad: one CodeNeRF category, geometry branch only (src/model.py:56-75: encoding_xyz, shape_layer_1, cat_layer,
+ * shape_layer_2, encoding_shape, sigma) on e[:87] of the embedding, whose Jacobian is I / scale stacked on
+ * pi 2^k cos(pi 2^k B_j . x / scale) B_j / scale, k = 0..3.  pts (N,3) in the field frame, B (21,3), trunk (CNR_TRUNK_PARAMS) the
+ * fp32 blob (only its first 9 857 floats are read), biasrows (rows,4,32) as cnr_latent_fwd / ops.bias_rows produce them (slots 0..2
+ * are read), row (N,) i32 = every point's row of biasrows, which may change from point to point (NULL: row 0); rows are not
+ * range-checked here.
+ * cnr_occmap_grad: an OccupancyMap (src/model.py:129-147: in_layer, mid1, cat_layer, mid2, out_alpha).  theta: the flat
+ * concatenation of the module's parameters in registration order (in_layer.0 W (H,87) b | mid1.0.0 W (H,H) b | cat_layer.0 W
+ * (H,H+87) b | mid2.0.0 W (H,H) b | out_alpha W (1,H) b | ...; the colour layers behind them are not read), B (21,3).
+ * H = 32 or 128; any other H returns CNR_E_SHAPE before anything else is looked at. */
+int cnr_field_grad(const float* pts, const int* row, const float* B, const float* trunk, const float* biasrows,
+                   float scale, int64_t N, float* sigma, float* grad, void* stream);
+int cnr_occmap_grad(const float* pts, const float* theta, const float* B, int H, float scale, int64_t N,
+                    float* sigma, float* grad, void* stream);
+
+/* ---- surface normals of a rendered view (csrc/view.hip).  After cnr_view_composite on the same P pixels.
+ * cnr_view_surface_points: per pixel the winning segment = the one cnr_view_composite took the label from (the largest entry of
+ * its mass row, the earlier one among equals), its entity e = seg_entity[.], or none when the pixel has no segment or opacity <
+ * opacity_threshold; the surface point = to_field[e] . (T_wc . (depth d, 1)) in cnr_view_points' expressions at z = the rendered
+ * depth.  The pixels with a surface are bucketed by field run, run = entity_run[e] in [0, n_runs): a compact list in (run, pixel)
+ * order, run r owning [run_offset[r], run_offset[r+1]), run_offset (n_runs + 1,) i64 on the device, M = run_offset[n_runs] <= P.
+ * Outputs: surf_entity (P,) i32 (-1: none), surf_slot (P,) i32 = the pixel's place in the list (-1: none), surf_pts (P,3) (zero
+ * for none), list_pts (P,3) and list_row (P,) i32 = entity_row[e], of which the first M entries are written.
+ * workspace >= cnr_view_surface_workspace_bytes(P, n_runs).  P < 2^31, n_runs <= 32767 (else CNR_E_SHAPE).  No atomics.
+ * cnr_view_normals: grad_c (M,3) = d sigma / d x at list_pts in the field frame -> normal (P,3) = -A^T g / |A^T g| with A =
+ * to_field[surf_entity[p]][:, :3] and g = grad_c[surf_slot[p]]: the world-frame unit vector out of the surface, towards
+ * decreasing occupancy; exactly zero where the pixel has no surface or A^T g is zero (or not finite).  Every pixel is written. */
+int64_t cnr_view_surface_workspace_bytes(int64_t P, int n_runs);
+int cnr_view_surface_points(const float* T_wc, const float* dirs, const float* to_field, const float* depth,
+                            const float* opacity, float opacity_threshold, const float* mass, const int* pix_segs,
+                            const int* seg_entity, const int* entity_run, const int* entity_row, int64_t P, int n_runs,
+                            void* workspace, int64_t* run_offset, int* surf_entity, int* surf_slot, float* surf_pts,
+                            float* list_pts, int* list_row, void* stream);
+int cnr_view_normals(const float* grad_c, const int* surf_slot, const int* surf_entity, const float* to_field, int64_t P,
+                     int64_t M, float* normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,12 @@ get_dataset, one sceneCategory per class), loads the newest checkpoint of each f
 (16 bit, millimetres) and instance.png (16 bit, 65535 = nothing) into --out.  Two edits, neither of which touches the trained
 state: --move INST tx ty tz translates an instance in world coordinates, --hide INST leaves it out.  --skip-empty builds
 one occupancy grid per entity from the loaded weights (G^3 cells, a cell kept where the occupancy reaches --tau on meshing's
-lattice or in a neighbouring cell) and evaluates the fields only inside the kept cells.
+lattice or in a neighbouring cell) and evaluates the fields only inside the kept cells.  --normals adds normal.png (the
+world-frame surface normal from the fields' own gradients, n * 0.5 + 0.5 in 8 bits), --shade also shade.png, a grey headlight
+Lambert image made from it.
 
     python tools/render_view.py --config configs/Replica/config_replica_room0.json --logdir logs/room0 --frame 0 --out view0
-        [--samples 64] [--move 12 0.3 0 0] [--hide 7] [--skip-empty [--grid 64] [--tau 1e-3]]"""
+        [--samples 64] [--move 12 0.3 0 0] [--hide 7] [--skip-empty [--grid 64] [--tau 1e-3]] [--normals] [--shade]"""
 import argparse
 import glob
 import os
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--skip-empty", action="store_true", help="skip the samples in empty cells of per-entity occupancy grids")
     ap.add_argument("--grid", type=int, default=64, metavar="G", help="cells per axis of the occupancy grids (a multiple of 4, 4 .. 128)")
     ap.add_argument("--tau", type=float, default=1e-3, metavar="T", help="a cell is kept where the occupancy reaches T")
+    ap.add_argument("--normals", action="store_true", help="also write normal.png: surface normals from the field gradients")
+    ap.add_argument("--shade", action="store_true", help="also write shade.png, a headlight Lambert image (implies --normals)")
     ap.add_argument("--allow-pickle", action="store_true", help="unpickle the checkpoints instead of the weights-only read: needed for a background's box object and for numpy "
                     "scalar ids (trusted files only)")
     a = ap.parse_args()
@@ -66,13 +70,20 @@ def main():
     if a.skip_empty:
         renderer.build_grids(resolution=a.grid, threshold=a.tau)
     with torch.no_grad():
-        result = renderer.render(T_wc, n_samples=a.samples, transforms=transforms, hidden=set(a.hide), skip_empty=a.skip_empty)
+        result = renderer.render(T_wc, n_samples=a.samples, transforms=transforms, hidden=set(a.hide), skip_empty=a.skip_empty,
+                                 normals=a.normals or a.shade)
     if a.skip_empty:
         evaluated, total = renderer.active_samples
         print("evaluated {} of {} samples ({:.1%})".format(evaluated, total, evaluated / max(total, 1)))
     cnr.view.render_to_files(result, a.out)
+    names = ["rgb.png", "depth.png", "instance.png"] + (["normal.png"] if "normal" in result else [])
+    if a.shade:
+        from PIL import Image
+        grey = (cnr.view.shade(result, T_wc).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy().transpose(1, 0, 2)
+        Image.fromarray(np.ascontiguousarray(grey), "RGB").save(os.path.join(a.out, "shade.png"))
+        names.append("shade.png")
     shown = sorted(int(i) for i in torch.unique(result["instance"]).tolist())
-    print("wrote rgb.png, depth.png, instance.png to {}; instances in view: {}".format(a.out, shown))
+    print("wrote {} to {}; instances in view: {}".format(", ".join(names), a.out, shown))
 
 
 if __name__ == "__main__":
