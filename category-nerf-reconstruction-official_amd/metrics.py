@@ -19,7 +19,7 @@ import torch
 from . import _C
 
 __all__ = ["accuracy", "completion", "accuracy_ratio", "completion_ratio", "chamfer", "nn_dist", "dist_stats",
-           "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric"]
+           "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images"]
 
 
 def _device():
@@ -284,3 +284,36 @@ def calc_3d_metric(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0):
     s_comp, c_comp = _stats_device(nn_dist(gt_pc, rec_pc), 0.05)
     acc, comp, cnt = (v.item() for v in (s_acc, s_comp, c_comp))
     return [[acc / N * 100], [comp / N * 100], [cnt / N * 100]]
+
+
+# ---- depth L1 ----------------------------------------------------------------------------------------------------------
+def depth_l1_images(depth_rec, depth_gt):
+    """Two stacks of depth images of one shape (tensors on any device, 0 = nothing hit) -> (sum of |rec - gt| over the pixels
+    hit in both, float64 tensor; both, only_rec, only_gt, neither: Python ints)"""
+    a, b = torch.as_tensor(depth_rec), torch.as_tensor(depth_gt)
+    if a.shape != b.shape:
+        raise ValueError("depth images of different shapes: {} and {}".format(tuple(a.shape), tuple(b.shape)))
+    ha, hb = a > 0, b > 0
+    both = ha & hb
+    total = ((a.double() - b.double()).abs() * both).sum()
+    n = [int(x) for x in torch.stack([both.sum(), (ha & ~hb).sum(), (~ha & hb).sum(), (~ha & ~hb).sum()]).tolist()]
+    return total, n[0], n[1], n[2], n[3]
+
+
+def depth_l1(mesh_rec, mesh_gt, T_wcs, rasterizer, views_per_launch=None):
+    """The depth L1 of the usual reconstruction table: both meshes (``vis.Mesh``, a tuple, or a ``raster.MeshScene``) rendered
+    by ``rasterizer`` (``raster.MeshRasterizer``) from the poses ``T_wcs`` (V,4,4) -> {l1: the mean |depth_rec - depth_gt| in
+    metres over the pixels of all views where both were hit (summed in fp64 on the device; nan when there is no such pixel),
+    both, only_rec, only_gt, neither: the pixel counts}."""
+    from . import raster
+    scenes = [m if isinstance(m, raster.MeshScene) else raster.MeshScene(m, device=rasterizer.device) for m in (mesh_rec, mesh_gt)]
+    T, _ = raster._poses(T_wcs)
+    step = min(rasterizer.views_per_launch(s, views_per_launch) for s in scenes)
+    total, counts = torch.zeros((), dtype=torch.float64, device=rasterizer.device), [0, 0, 0, 0]
+    for a in range(0, T.shape[0], step):
+        d = [rasterizer.render(s, T[a:a + step], attributes=False, views_per_launch=step)["depth"] for s in scenes]
+        part = depth_l1_images(d[0], d[1])
+        total = total + part[0]
+        counts = [c + p for c, p in zip(counts, part[1:])]
+    l1 = float(total) / counts[0] if counts[0] else float("nan")
+    return dict(l1=l1, both=counts[0], only_rec=counts[1], only_gt=counts[2], neither=counts[3])

@@ -1222,6 +1222,50 @@ int cnr_view_surface_points(const float* T_wc, const float* dirs, const float* t
 int cnr_view_normals(const float* grad_c, const int* surf_slot, const int* surf_entity, const float* to_field, int64_t P,
                      int64_t M, float* normal, void* stream);
 
+/* ---- mesh rasterisation: which pixel sees which triangle at what z-depth (csrc/raster.hip).
+ * verts (Nv,3) f32, faces (F,3) i32 (indices are NOT range-checked here: cnr_amd.raster.MeshScene does), T_cw (V,4,4) f64
+ * row-major world -> camera, dirs (W*H,3) f32 = the cameraInfo cache rows, pixel (w,h) at row w H + h, of the intrinsics fx fy
+ * cx cy.  All images are (V,W,H,...).  0 <= zmin <= zmax; 1 <= W, H <= 32768; V >= 1; 1 <= F < 2^31; F V <= 2^40; V x tiles < 2^31
+ * with tiles = ceil(W / 8) ceil(H / 8) (else CNR_E_SHAPE).  workspace >= cnr_raster_workspace_bytes(F, V, W, H) and the SAME
+ * workspace goes through bin_count -> bin_emit -> tiles -> attributes.
+ *
+ * Coverage (fp64, no contraction, as parenthesised): v_k = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 per row r of T_cw; n0 = v1 x v2,
+ * n1 = v2 x v0, n2 = v0 x v1 with (a x b).x = a.y b.z - a.z b.y and so on; det = (v0.x n0.x + v0.y n0.y) + v0.z n0.z,
+ * s = sign(det), det == 0 covers nothing.  Per pixel, d = (dx, dy, 1) widened from dirs: e_i = (n_i.x dx + n_i.y dy) + n_i.z,
+ * S = (e0 + e1) + e2, t = det / S; covered iff s e_i >= 0 (all i), s S > 0, zmin <= t <= zmax.  Winner: smallest (t, face).
+ *
+ * cnr_raster_bin_count: the records, a conservative box of 8 x 8 pixel tiles per (view, face) (the triangle cut at z >=
+ * max(zmin, 2^-13), projected, grown by one pixel, clamped; every tile for a face that comes nearer than 2^-13 where a pixel
+ * could still see it, which only zmin < 2^-13 allows; none for det == 0, for a face wholly nearer than zmin, and with cull_backfaces for
+ * det < 0), the per-(view, tile) list lengths and starts; n_pairs (1,) i64 on the device = the number of (view, tile, face)
+ * pairs.  cnr_raster_bin_emit: pair_face (n_pairs,) i32, the lists (integer cursors: the order inside a list is not fixed, the
+ * images are).  cnr_raster_tiles: depth f32 (0: no hit; else t rounded once), face i32 (-1: no hit), bary (.,2) f32 = e1 / S,
+ * e2 / S of the winner (0: no hit); every pixel is written.
+ * cnr_raster_attributes: from face_img (the face image of cnr_raster_tiles on the same workspace) and fp64 barycentrics b_i =
+ * e_i / S recomputed from the records: rgb = (b0 c0 + b1 c1) + b2 c2 of colors (Nv,3), instance = face_label[face] (-1: no
+ * hit), normal (world frame, unit): vertex_normals = 0 the geometric normal (p1 - p0) x (p2 - p0) turned so that n . d_world < 0,
+ * vertex_normals = 1 the normalised (b0 N0 + b1 N1) + b2 N2 of normals (Nv,3) with its sign as given; exactly zero where nothing
+ * was hit or the vector vanishes.
+ * cnr_raster_visible: seen (F,) u8 |= 1 and count (F,) i32 += the number of the V views in which the face won a pixel; with
+ * depth_obs (V,W,H) (may be NULL, then depth may be too) a pixel counts only if depth_obs > 0 and (double)depth <=
+ * (double)depth_obs + tol.  Plain stores of one value, no atomics; the caller zeroes seen and count before the first call.
+ * workspace >= cnr_raster_visible_workspace_bytes(F, V).  No floating-point atomics anywhere; bit-identical run to run. */
+int64_t cnr_raster_workspace_bytes(int64_t F, int V, int W, int H);
+int cnr_raster_bin_count(const float* verts, const int* faces, int64_t F, const double* T_cw, int V, int W, int H,
+                         double fx, double fy, double cx, double cy, double zmin, int cull_backfaces, void* workspace,
+                         int64_t* n_pairs, void* stream);
+int cnr_raster_bin_emit(int64_t F, int V, int W, int H, void* workspace, int* pair_face, void* stream);
+int cnr_raster_tiles(const float* dirs, int64_t F, int V, int W, int H, double zmin, double zmax,
+                     const void* workspace, const int* pair_face, float* depth, int* face, float* bary,
+                     void* stream);
+int cnr_raster_attributes(const float* dirs, const float* verts, const int* faces, const float* colors,
+                          const float* normals, const int* face_label, const double* T_cw, int64_t F, int V, int W,
+                          int H, int vertex_normals, const void* workspace, const int* face_img, float* rgb,
+                          int* instance, float* normal, void* stream);
+int64_t cnr_raster_visible_workspace_bytes(int64_t F, int V);
+int cnr_raster_visible(const int* face_img, const float* depth, const float* depth_obs, double tol, int64_t F, int V,
+                       int W, int H, void* workspace, uint8_t* seen, int* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
