@@ -16,11 +16,16 @@ constexpr int ROWS_MAX = 15;
 constexpr int ROWS_TILE_MAX = 128;
 constexpr int REC_ENTRIES = ((TRUNK + 126 + ROWS_MAX * 128 + 255) / 256) * 256;  // one workgroup's record
 // A record entry is a bf16 (round 4; fp32 before): 256 records x 64.5 KB written by the field kernel and read once by the step's
-// last launch were 15 of the 21 MB the step body moves at configs[1].  Each workgroup's partial sum is rounded once (2^-9
-// relative, unbiased); the fixed-order sum over the records stays fp32, so the summed gradient carries ~2^-9 / sqrt(records) =
-// 1e-4 of rounding noise -- under the f16 forward's own (tests/test_fullsize_gpu.py bars unchanged).  bf16, not f16: a workgroup's
-// share of a small gradient entry sits far below f16's 6e-8.  The per-object bias-row sums of the step go through the int64
-// fixed-point table as before (exact).
+// last launch were 15 of the 21 MB the step body moves at configs[1].  Each workgroup's partial sum is rounded once (half an ulp
+// at most: 2^-9 relative to the PARTIAL, unbiased); the fixed-order sum over the records stays fp32.  The summed gradient therefore
+// carries rounding noise of 2^-9 / sqrt(records) relative to the partials, records per class = 256 / C: ~1e-4 .. 2e-4 at the 256
+// records of configs[1] (measured 2.0e-4 on the trunk) -- under the f16 forward's own, tests/test_fullsize_gpu.py bars unchanged --
+// but 5e-4 .. 1.4e-3 at the 10 .. 63 records of many classes per GPU and of the small test shapes.  An entry whose partials CANCEL
+// keeps an absolute error of 2^-9 |partial| per record, whatever the sum: with random upstream gradients 256 records leave 2e-3
+// (tests/test_fused_gpu.py, linearity).  The noise is predictable entry by entry from the records themselves (sum of ulp^2 / 12);
+// tests/record_noise.py turns that into the checks of the gradient-equivalence tests.  bf16, not f16: a workgroup's share of a small
+// gradient entry sits far below f16's 6e-8.  The per-object bias-row sums of the step go through the int64 fixed-point table as
+// before (exact).
 typedef unsigned short rec_t;
 __device__ __forceinline__ rec_t rec_pack(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }   // v_cvt_pk_bf16_f32: RNE
 __device__ __forceinline__ float rec_unpack(rec_t b) { return __builtin_bit_cast(float, (unsigned int)b << 16); }

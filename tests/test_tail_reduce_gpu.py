@@ -15,12 +15,9 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from record_noise import LATENT_BIASES, ROWS_MAX, TR, written_mask  # noqa: F401  (the record's constants live there)
 
 pytestmark = pytest.mark.gpu
-
-TR = 13892                                   # trunk parameters = first dB record entry
-LATENT_BIASES = (3840, 8736, 4896, 13281)    # biases of the latent-conditioned layers: no record entry is written for them
-ROWS_MAX = 15                                # up to this many rows per class the record carries their sums behind the dB halves
 
 
 @pytest.fixture(scope="module")
@@ -50,11 +47,7 @@ def _ordered_sum(x):
 
 
 def _unwritten(E, n_obj):
-    m = torch.zeros(E, dtype=torch.bool)
-    for off in LATENT_BIASES:
-        m[off:off + 32] = True
-    m[TR + 126 + (n_obj * 128 if n_obj <= ROWS_MAX else 0):] = True
-    return m
+    return ~written_mask(E, n_obj)
 
 
 def _step_grad(_C, theta, lay, L, n_obj, C, zl, ws, nwg, fix, reg, fill):
