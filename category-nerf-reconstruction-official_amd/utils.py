@@ -368,6 +368,31 @@ def tsdf_unit_tables(keys, frames):
     return units.contiguous(), frame_ofs, frames.to(torch.int32).contiguous(), nb.contiguous()
 
 
+def _unit_neighbours(units):
+    """tsdf_unit_tables' neighbours alone, for ascending unit keys"""
+    return tsdf_unit_tables(units, torch.zeros(len(units), dtype=torch.int64, device=units.device))[3]
+
+
+def tsdf_unit_neighbourhood(units):
+    """units (U,) ascending int64 keys (device or CPU) -> hood (U,27) int32: for the offset (dx, dy, dz) in {-1,0,1}^3 at column
+    (dx + 1) 9 + (dy + 1) 3 + (dz + 1) the index of that unit, or -1 where there is none or its index leaves the 21-bit range.
+    Column 13 is the unit itself; columns 22, 16 and 14 are tsdf_unit_tables' +x, +y, +z neighbours.  What cnr_tsdf_mesh_count
+    and _emit take: the three +1 columns do not chain to a diagonal (unit +x+y can exist while +x does not)."""
+    units = units.to(torch.int64)
+    U, mask = len(units), (1 << TSDF_AXIS_BITS) - 1
+    if U == 0:
+        return torch.full((0, 27), -1, dtype=torch.int32, device=units.device)
+    # all 27 columns at once: (U,27,3) biased indices of the wanted units, one searchsorted
+    shifts = torch.tensor([2 * TSDF_AXIS_BITS, TSDF_AXIS_BITS, 0], dtype=torch.int64, device=units.device)
+    col = torch.arange(27, dtype=torch.int64, device=units.device)
+    offsets = torch.stack([col // 9 - 1, col // 3 % 3 - 1, col % 3 - 1], 1)
+    n = ((units[:, None] >> shifts) & mask)[:, None, :] + offsets[None]
+    inside = ((n >= 0) & (n <= mask)).all(-1)
+    want = torch.where(inside, (n << shifts).sum(-1), torch.full_like(inside, -1, dtype=torch.int64))
+    at = torch.searchsorted(units, want.reshape(-1)).clamp_(max=U - 1).reshape(U, 27)
+    return torch.where(units[at] == want, at, torch.full_like(at, -1)).to(torch.int32).contiguous()
+
+
 class TSDFVolume:
     """ScalableTSDFVolume(voxel_length, sdf_trunc, RGB8) for one batch of frames: integrate_frames once, then
     extract_point_cloud.  After integrate_frames: units, frame_ofs, frame_idx (and, on request, the kernel's slots),
@@ -452,6 +477,65 @@ class TSDFVolume:
         points, colors = self.extract_points()
         return PointCloud(points.float(), colors.float())
 
+    @classmethod
+    def from_blocks(cls, units, tsdf, weight, color, voxel_length, sdf_trunc, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
+        """A volume of given blocks (a saved volume, or a synthetic one): units (U,) ascending distinct keys, tsdf (U,4096),
+        weight (U,4096), color (U,4096,3); `neighbours` as tsdf_unit_tables fills it."""
+        vol = cls(voxel_length, sdf_trunc, device=device, max_block_bytes=max_block_bytes)
+        dev = vol.device
+        units = torch.as_tensor(units).to(device=dev, dtype=torch.int64).contiguous()
+        U = len(units)
+        if units.dim() != 1 or (U and int(units.min()) < 0) or (U > 1 and not bool((units[1:] > units[:-1]).all())):
+            raise ValueError("TSDFVolume.from_blocks: units (U,) are distinct keys of three biased 21-bit indices, ascending")
+        if U * TSDF_BLOCK_BYTES > vol.max_block_bytes:
+            from . import _C
+            raise _C.CnrError(f"TSDFVolume: the blocks of {U} units take {U * TSDF_BLOCK_BYTES} bytes, more than max_block_bytes = "
+                              f"{vol.max_block_bytes}")
+        blocks = [torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous() for a in (tsdf, weight, color)]
+        want = [(U, TSDF_UNIT ** 3), (U, TSDF_UNIT ** 3), (U, TSDF_UNIT ** 3, 3)]
+        if [tuple(b.shape) for b in blocks] != want:
+            raise ValueError(f"TSDFVolume.from_blocks: tsdf, weight, color of {U} units have the shapes {want}")
+        vol.units, vol.neighbours = units, _unit_neighbours(units)
+        vol.tsdf, vol.weight, vol.color = blocks
+        return vol
+
+    def extract_triangle_mesh_raw(self):
+        """Marching cubes over the observed voxels (weight != 0), across units (csrc/tsdf_mesh.hip) ->
+        (verts (V,3) f64, colors (V,3) f64 in [0, 1], normals (V,3) f64, faces (F,3) i32) device tensors, vertices in the order
+        unit, voxel, axis and faces in the order unit, voxel, table; None when there is no vertex or no face.  Normals and
+        right-hand face normals point to increasing tsdf (free space)."""
+        from . import _C
+        if self.units is None:
+            raise ValueError("TSDFVolume: extract before integrate_frames")
+        U, dev = len(self.units), self.device
+        if U == 0:
+            return None
+        hood = tsdf_unit_neighbourhood(self.units)
+        ws = _C.workspace(_C.load().cnr_tsdf_mesh_workspace_bytes(U), dev, "cnr_tsdf_mesh")
+        cnt = torch.zeros(2, device=dev, dtype=torch.int64)
+        _C.call("cnr_tsdf_mesh_count", self.tsdf, self.weight, hood, U, ws, cnt)
+        V, F = (int(v) for v in cnt.tolist())
+        if V == 0 or F == 0:
+            return None
+        if V >= 1 << 31:
+            raise _C.CnrError(f"cnr_tsdf_mesh: {V} vertices, more than int32 faces can name")
+        verts, colors, normals = (torch.empty(V, 3, device=dev, dtype=torch.float64) for _ in range(3))
+        faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+        _C.call("cnr_tsdf_mesh_emit", self.units, self.tsdf, self.weight, self.color, hood, U, self.voxel_length, ws, verts, colors,
+                normals, faces)
+        return verts, colors, normals, faces
+
+    def extract_triangle_mesh(self):
+        """-> vis.Mesh (f64 vertices and normals, vertex colours clip(rint(255 c), 0, 255)), or None when the volume has no face"""
+        from . import vis
+        raw = self.extract_triangle_mesh_raw()
+        if raw is None:
+            return None
+        verts, colors, normals, faces = (a.cpu().numpy() for a in raw)
+        mesh = vis.Mesh(verts, faces, normals)
+        mesh.visual.vertex_colors = np.clip(np.rint(255.0 * colors), 0, 255)
+        return mesh
+
 
 def _radius_cell_tables(points, radius):
     """The cell tables cnr_radius_count and cnr_hybrid_search take, for (n,3) f32 device points (n >= 1) and cells of edge
@@ -533,11 +617,10 @@ def estimate_normals_device(points, radius, max_nn, centroid=None):
 MIN_POINTS_AFTER_OUTLIER_REMOVAL = 100
 
 
-def accumulate_pointcloud_tsdf(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size=0.01, depth_scale=0.001,
-                               max_depth=6.0, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
-    """src/utils.py:212-247: the instance's depth of every frame of inst_info_list fused into a TSDF volume (voxel_size,
-    sdf_trunc = 4 voxel_size, RGB8), its surface points, voxel_down_sample(voxel_size), remove_radius_outlier(100, 0.05) -- and
-    the unfiltered cloud where fewer than 100 points survive that."""
+def _fuse_instance_volume(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size, depth_scale, max_depth, device,
+                          max_block_bytes):
+    """the instance's masked depth of every frame of inst_info_list integrated into one TSDFVolume(voxel_size, 4 voxel_size)
+    -> (volume, number of frames)"""
     dev = _cuda_device(device)
     depths, images, poses = [], [], []
     for entry in inst_info_list:
@@ -552,15 +635,38 @@ def accumulate_pointcloud_tsdf(inst_id, inst_info_list, frame_samples, intrinsic
         raise ValueError(f"instance {inst_id}: no frames")
     volume = TSDFVolume(voxel_size, 4 * voxel_size, device=dev, max_block_bytes=max_block_bytes)
     volume.integrate_frames(torch.stack(depths), torch.stack(images), intrinsic_open3d, np.stack(poses))
+    return volume, len(depths)
+
+
+def accumulate_pointcloud_tsdf(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size=0.01, depth_scale=0.001,
+                               max_depth=6.0, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
+    """src/utils.py:212-247: the instance's depth of every frame of inst_info_list fused into a TSDF volume (voxel_size,
+    sdf_trunc = 4 voxel_size, RGB8), its surface points, voxel_down_sample(voxel_size), remove_radius_outlier(100, 0.05) -- and
+    the unfiltered cloud where fewer than 100 points survive that."""
+    volume, n_frames = _fuse_instance_volume(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size, depth_scale,
+                                             max_depth, device, max_block_bytes)
     cloud = volume.extract_point_cloud()
     if len(cloud) == 0:
-        raise ValueError(f"instance {inst_id}: the TSDF volume of its {len(depths)} frames has no surface point")
+        raise ValueError(f"instance {inst_id}: the TSDF volume of its {n_frames} frames has no surface point")
     cloud = cloud.voxel_down_sample(voxel_size)
     kept, _ = cloud.remove_radius_outlier(nb_points=100, radius=0.05)
     if len(kept) < MIN_POINTS_AFTER_OUTLIER_REMOVAL:
         print("too few points left after outlier rejection")
         return cloud
     return kept
+
+
+def accumulate_mesh_tsdf(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size=0.01, depth_scale=0.001,
+                         max_depth=6.0, device=None, max_block_bytes=DEFAULT_TSDF_BLOCK_BYTES):
+    """The classical baseline: the volume of accumulate_pointcloud_tsdf (the same frames, the same fusion), and its triangle
+    mesh (TSDFVolume.extract_triangle_mesh) -> vis.Mesh in world coordinates, coloured.  mesh.units = the volume's unit count."""
+    volume, n_frames = _fuse_instance_volume(inst_id, inst_info_list, frame_samples, intrinsic_open3d, voxel_size, depth_scale,
+                                             max_depth, device, max_block_bytes)
+    mesh = volume.extract_triangle_mesh()
+    if mesh is None:
+        raise ValueError(f"instance {inst_id}: the TSDF volume of its {n_frames} frames has no surface triangle")
+    mesh.units = len(volume.units)
+    return mesh
 
 
 def transform_pointcloud(cloud, T_rel):

@@ -918,6 +918,30 @@ int cnr_tsdf_extract_count(const float* tsdf, const float* weight, const int* ne
                            int64_t* count_out, void* stream);
 int cnr_tsdf_extract_emit(const int64_t* units, const float* tsdf, const float* weight, const float* colors, const int* neighbours,
                           int64_t U, double voxel, void* workspace, double* points, double* colors_out, void* stream);
+/* The triangle mesh of an integrated volume (csrc/tsdf_mesh.hip): marching cubes across units.
+ * Inputs: units (U,) ascending keys, tsdf (U,4096), weight (U,4096), colors (U,4096,3) f32 as cnr_tsdf_integrate writes them, and
+ * hood (U,27) i32: for the offset (dx, dy, dz) in {-1,0,1}^3 at column (dx + 1) 9 + (dy + 1) 3 + (dz + 1) the index of that unit
+ * or -1 (column 13: the unit itself; an index outside [0, U) counts as -1).
+ * A voxel is observed when its unit exists and weight != 0 (no +-0.98 band).  A cell is named by its min-corner voxel; corner c
+ * is the voxel at +((c >> 2) & 1, (c >> 1) & 1, c & 1) (mc_table.h's numbering); the cell is valid when all 8 corners are
+ * observed; bit c of its case is set when tsdf[c] < 0 (+0, -0 and NaN: not set); its triangles are MC_NTRI / MC_TRI's, each
+ * edge named by MC_EDGE_LO's owning voxel and axis.
+ * Vertices: one per (owner voxel, axis) that a valid cell uses, none else.  fp64, every product and sum rounded on its own:
+ * the owner's centre unit 16 voxel + (ijk + 0.5) voxel with coordinate `axis` replaced by (p0 r1 + p1 r0) / (r0 + r1),
+ * p1 = p0 + voxel, r = |tsdf| of the two ends (cnr_tsdf_extract_emit's formulas); colours (c0 r1 + c1 r0) / (r0 + r1) / 255.
+ * Normals: per end and axis (f+ - f-) 0.5 where both axis neighbours are observed, the one-sided difference where one is, else
+ * 0; the two ends blended (g0 r1 + g1 r0) / (r0 + r1); divided by sqrt((nx nx + ny ny) + nz nz) where that is > 0, else 0.
+ * They point to increasing tsdf, and so does every face's right-hand normal (cnr_mc's faces on -tsdf, level 0, ascent 0).
+ * Order: vertices by (unit, voxel, axis), faces by (unit, cell's voxel, table order); bit-identical from run to run.
+ * cnr_tsdf_mesh_count writes counts_out (2,) i64 = {V, F} (device) and keeps per-voxel and per-unit tables in workspace
+ * (>= cnr_tsdf_mesh_workspace_bytes(U)); cnr_tsdf_mesh_emit, with the same inputs and workspace after it on the same stream,
+ * writes verts, colors_out, normals (V,3) f64 and faces (F,3) i32.  V >= 2^31: CNR_E_SHAPE (emit reads the count back, and
+ * waits for the stream, only for U >= 174763, below which no volume holds that many). */
+int64_t cnr_tsdf_mesh_workspace_bytes(int64_t U);
+int cnr_tsdf_mesh_count(const float* tsdf, const float* weight, const int* hood, int64_t U, void* workspace, int64_t* counts_out,
+                        void* stream);
+int cnr_tsdf_mesh_emit(const int64_t* units, const float* tsdf, const float* weight, const float* colors, const int* hood, int64_t U,
+                       double voxel, void* workspace, double* verts, double* colors_out, double* normals, int* faces, void* stream);
 /* open3d's remove_radius_outlier counts.  cnr_radius_cell_keys: keys[i] = the packed cell floor(double(p) / radius) per axis
  * (biased like a unit key), or -1 and bit 0 of *err for an index outside [-2^20, 2^20) or not a number.  The caller sorts the
  * keys (stable) and passes the permutation, the sorted keys, the C distinct keys ascending and starts (C + 1,) i64 (cell c holds

@@ -1,8 +1,9 @@
 """Times the stages of the TSDF path (csrc/tsdf.hip, cnr_amd.utils.TSDFVolume) on the GPU by device events: the
 touch list of every frame, the unit tables (torch), the integration, the extraction, the 1 cm down-sample and the radius count,
-on a synthetic sequence: a camera turning inside a box room of 5 x 4 x 2.6 m, 640 x 480 frames.
+and the triangle mesh (csrc/tsdf_mesh.hip: the 27-table, count, emit), on a synthetic sequence: a camera turning inside a box
+room of 5 x 4 x 2.6 m, 640 x 480 frames.
 
-    python tools/time_tsdf.py [--frames 300] [--reps 3] [--out FILE.json]"""
+    python tools/time_tsdf.py [--frames 300] [--reps 3] [--out FILE.json] [--mesh-out profiles/tsdf_mesh_time.json] [--mesh-reps 200]"""
 import argparse
 import json
 import os
@@ -60,6 +61,8 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mesh-reps", type=int, default=200, help="repeats of the sub-millisecond mesh stages")
+    ap.add_argument("--mesh-out", default=None, help="write the mesh stages' times and achieved bytes/s (profiles/tsdf_mesh_time.json)")
     a = ap.parse_args()
     import cnr_amd as cnr
     _C, U = cnr._C, cnr.utils
@@ -106,6 +109,29 @@ def main():
     rows["radius_count_ms"] = round(_ms(lambda: U.radius_neighbour_counts(ds.points_device, 0.05), a.reps), 3)
     counts = U.radius_neighbour_counts(ds.points_device, 0.05)
     rows["radius_count_mean"], rows["radius_kept"] = round(float(counts.float().mean()), 2), int((counts > 100).sum())
+    # the triangle mesh (csrc/tsdf_mesh.hip): the 27-table (torch), count and emit, against the bytes each stage must read.
+    # These stages take a fraction of a millisecond, so they (and the points extraction beside them) are timed over more repeats.
+    mreps = max(a.reps, a.mesh_reps)
+    hood_ms = _ms(lambda: U.tsdf_unit_neighbourhood(units), mreps)
+    hood = U.tsdf_unit_neighbourhood(units)
+    ws = _C.workspace(_C.load().cnr_tsdf_mesh_workspace_bytes(n_units), dev, "cnr_tsdf_mesh")
+    cnt = torch.zeros(2, device=dev, dtype=torch.int64)
+    count_ms = _ms(lambda: _C.call("cnr_tsdf_mesh_count", tsdf, weight, hood, n_units, ws, cnt), mreps)
+    V, Fc = (int(v) for v in cnt.tolist())
+    verts, vcol, vnor = (torch.empty(max(V, 1), 3, device=dev, dtype=torch.float64) for _ in range(3))
+    faces = torch.empty(max(Fc, 1), 3, device=dev, dtype=torch.int32)
+    emit_ms = _ms(lambda: _C.call("cnr_tsdf_mesh_emit", units, tsdf, weight, color, hood, n_units, voxel, ws, verts, vcol, vnor, faces),
+                  mreps)
+    points_ms = _ms(vol.extract_points, mreps)
+    count_bytes = n_units * 2 * 4096 * 4                      # tsdf + weight of every unit once
+    emit_bytes = count_bytes + V * 2 * 3 * 4                  # ... and the two ends' colours of every emitted vertex
+    points_bytes = count_bytes + rows["extracted_points"] * 2 * 3 * 4
+    rows.update(neighbourhood_ms=round(hood_ms, 3), mesh_count_ms=round(count_ms, 4), mesh_emit_ms=round(emit_ms, 4), mesh_vertices=V,
+                mesh_faces=Fc)
+    stage = lambda ms, nbytes: dict(ms=round(ms, 4), must_read_bytes=nbytes, bytes_per_s=float("%.4g" % (nbytes / (ms * 1e-3))))
+    mesh_rows = dict(units=n_units, vertices=V, faces=Fc, extracted_points=rows["extracted_points"], block_bytes=rows["block_bytes"],
+                     repeats=mreps, neighbourhood=dict(ms=round(hood_ms, 4)), mesh_count=stage(count_ms, count_bytes),
+                     mesh_emit=stage(emit_ms, emit_bytes), extract=stage(points_ms, points_bytes))
     t = time.perf_counter()
     v2 = U.TSDFVolume(voxel, trunc, device=dev).integrate_frames(depths, colors, np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1]]),
                                                                  T_WC)
@@ -117,6 +143,16 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(dict(device=torch.cuda.get_device_name(0), reps=a.reps, rows=rows), f, indent=1)
+    if a.mesh_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.mesh_out)), exist_ok=True)
+        cached = ("the blocks (block_bytes) fit in the 256 MiB Infinity Cache, so bytes_per_s is a cache-resident rate, not an HBM rate; "
+                  if rows["block_bytes"] < (256 << 20) else "")
+        note = ("device-event times over `repeats` back-to-back calls after one warm-up call; " + cached +
+                "must_read_bytes: tsdf + weight of every unit once (8 KB per unit), plus for mesh_emit and extract "
+                "the two ends' colours of every emitted vertex or point; extract = extract_points (count, one read-back, emit), the "
+                "yardstick of the same run")
+        with open(a.mesh_out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), reps=a.reps, frames=F, note=note, stages=mesh_rows), f, indent=1)
 
 
 if __name__ == "__main__":
