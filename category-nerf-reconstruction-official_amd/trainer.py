@@ -57,12 +57,15 @@ class Trainer:
         self.shape_codes = self.shape_codes.to(self.device)
         self.texture_codes = self.texture_codes.to(self.device)
 
-    def meshing(self, inst_id=None, grid_dim=256, normals="grid"):
+    def meshing(self, inst_id=None, grid_dim=256, normals="grid", clean=None):
         """src/trainer.py:62-123: occupancy on a grid_dim^3 grid over the object's box, marching cubes at 0.5 ('ascent'),
         back to scene coordinates, vertex colours from eval_points.  None where the reference returns None.
         normals: "grid" = the lattice differences marching cubes interpolates (skimage's, faceted on a coarse grid); "field" =
         the field's own gradient at every vertex (eval_gradient), normalised, pointing towards increasing occupancy as the grid
-        normals do (vis.py); a vertex whose gradient is exactly zero keeps its grid normal."""
+        normals do (vis.py); a vertex whose gradient is exactly zero keeps its grid normal.
+        clean: None, or a dict of meshops.clean_mesh options (keep_largest=1, min_faces=..., weld=...): the floaters are dropped on
+        the device, in scene coordinates, BEFORE the colour pass, so the field is never evaluated at a dropped vertex; the report is
+        left in self.last_clean_report."""
         if normals not in ("grid", "field"):
             raise ValueError("normals must be 'grid' or 'field', not {!r}".format(normals))
         occ_range = [-1., 1.]
@@ -100,6 +103,13 @@ class Trainer:
         mesh.apply_scale(scale_np)                       # to scene coordinates
         if boxed:
             mesh.apply_transform(transform_np)
+        if clean is not None:
+            from . import meshops
+            pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
+            tri = torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int32)).to(self.device)
+            kept_faces, kept, self.last_clean_report = meshops.clean_device(pts, tri, **dict(clean))
+            idx = kept.cpu().numpy().astype(np.int64)
+            mesh = vis.Mesh(mesh.vertices[idx], kept_faces.cpu().numpy().astype(np.int64).reshape(-1, 3), mesh.vertex_normals[idx])
         vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
         ret = self.eval_points(vertices_pts) if self.cls_id == 0 else self.eval_points(vertices_pts, inst_id=inst_id)
         if ret is None:

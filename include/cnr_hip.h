@@ -1290,6 +1290,65 @@ int64_t cnr_raster_visible_workspace_bytes(int64_t F, int V);
 int cnr_raster_visible(const int* face_img, const float* depth, const float* depth_obs, double tol, int64_t F, int V,
                        int W, int H, void* workspace, uint8_t* seen, int* count, void* stream);
 
+/* ---- the mesh as a graph: components, edge statistics, compaction, welding (csrc/mesh_topo.hip) ----
+ * faces (F,3) i32 into V vertices, F <= (2^31 - 1) / 3, V < 2^31.  err (1,) i32 on the device, zeroed by the caller, is OR-ed
+ * with 1 when a bounded union/find or flatten loop ran out and with 2 when an index outside its range was met (and skipped).
+ * Integer atomics only (minima, counts); bit-identical run to run.
+ *
+ * check_faces: err |= 2 when a face index is outside [0, V); the other entry points trust faces only after that.
+ * labels_init: L[i] = i.  union_pairs: joins pairs (m,2) i32 of elements of [0, n).  union_faces (vertex connectivity): joins
+ * (v0,v1), (v0,v2) of every face and sets used[v] = 1 (used (V,) u8, zeroed by the caller).  edge_keys: keys (3F,) i64,
+ * keys[3 f + k] = min << 32 | max of corners k, (k + 1) % 3, or -1 when they are equal.  union_edges (edge connectivity): keys
+ * sorted stably, perm (3F,) i64 = the slots 3 f + k in sorted order; joins the faces of neighbouring equal keys >= 0.
+ * flatten: afterwards L[i] = the smallest element of i's set (workspace >= cnr_mesh_flatten_workspace_bytes(n)).
+ * roots_count/_emit: the i with L[i] == i and (used == NULL or used[i]), ascending, roots (C,) i32; the rank is the component id.
+ * assign: comp[i] = the rank of L[i] in roots, -1 where used[i] == 0.  cross_component: mode 0 vertex_component (V,) = the
+ * smallest face_component over the faces that use the vertex, -1 for none; mode 1 face_component[f] = vertex_component[v0].
+ * edge_stats: counts (C,3) i32 zeroed by the caller; per run of equal keys of multiplicity m, for the component c of its first
+ * face: counts[c][0] += m == 1 (boundary), [1] += m > 2 (non-manifold), [2] += m == 2 and both faces run the edge the same way.
+ * component_stats: order (F,) i64 = the faces stably sorted by component, sorted_component (F,) i32 their components;
+ * n_faces, n_vertices (C,) i32 (a vertex counts for vertex_component[v]), and with verts (V,3) f32 != NULL area (C,) f64,
+ * bbox_min/max (C,3) f32 -- per-face areas and boxes into workspace (>= cnr_mesh_component_stats_workspace_bytes(F); may be
+ * NULL without verts), then one wave per component; the exact order of operations is in csrc/mesh_topo.hip.
+ * compact_count/_emit: the faces with keep_face != 0 in their old order; reindex != 0 re-indexes them to the vertices they use
+ * in their old order (vertex_map (V,) i32, -1 = dropped; kept_vertices ascending), reindex == 0 keeps their indices
+ * (vertex_map, kept_vertices may be NULL).  counts_out (2,) i64 = kept faces, kept vertices (0 without reindex).
+ * weld_runs: perm (V,) i64 = the vertices in sorted order; rows (V,3) i32 the positions' bit patterns in INPUT order (exact
+ * mode) or sorted_keys (V,) i64 in SORTED order (cell mode), exactly one of them; a sorted position starts a run when it is
+ * the first, differs from its predecessor, holds a NaN (rows) or is -1 (keys); rep[perm[j]] = perm[head of j's run].
+ * remap_faces: out = remap[faces], keep[f] = 0 when drop_degenerate and two corners of out coincide, else 1. */
+int cnr_mesh_check_faces(const int* faces, int64_t F, int64_t V, int* err, void* stream);
+int cnr_mesh_labels_init(int* labels, int64_t n, void* stream);
+int cnr_mesh_union_pairs(const int* pairs, int64_t m, int64_t n, int* labels, int* err, void* stream);
+int cnr_mesh_union_faces(const int* faces, int64_t F, int64_t V, int* labels, uint8_t* used, int* err, void* stream);
+int cnr_mesh_edge_keys(const int* faces, int64_t F, int64_t* keys, void* stream);
+int cnr_mesh_union_edges(const int64_t* sorted_keys, const int64_t* perm, int64_t F, int* labels, int* err, void* stream);
+int64_t cnr_mesh_flatten_workspace_bytes(int64_t n);
+int cnr_mesh_flatten(int* labels, int64_t n, void* workspace, int* err, void* stream);
+int64_t cnr_mesh_roots_workspace_bytes(int64_t n);
+int cnr_mesh_roots_count(const int* labels, const uint8_t* used, int64_t n, void* workspace, int64_t* count_out,
+                         void* stream);
+int cnr_mesh_roots_emit(const int* labels, const uint8_t* used, int64_t n, const void* workspace, int* roots, void* stream);
+int cnr_mesh_assign(const int* labels, const uint8_t* used, int64_t n, const int* roots, int64_t C, int* comp, int* err,
+                    void* stream);
+int cnr_mesh_cross_component(const int* faces, int64_t F, int64_t V, int mode, int* face_component, int* vertex_component,
+                             void* stream);
+int cnr_mesh_edge_stats(const int64_t* sorted_keys, const int64_t* perm, const int* faces, int64_t F,
+                        const int* face_component, int64_t C, int* counts, void* stream);
+int64_t cnr_mesh_component_stats_workspace_bytes(int64_t F);
+int cnr_mesh_component_stats(const float* verts, const int* faces, const int64_t* order, const int* sorted_component,
+                             int64_t F, int64_t V, int64_t C, const int* vertex_component, void* workspace, int* n_faces,
+                             int* n_vertices, double* area, float* bbox_min, float* bbox_max, void* stream);
+int64_t cnr_mesh_compact_workspace_bytes(int64_t F, int64_t V);
+int cnr_mesh_compact_count(const int* faces, int64_t F, int64_t V, const uint8_t* keep_face, int reindex, void* workspace,
+                           int64_t* counts_out, void* stream);
+int cnr_mesh_compact_emit(const int* faces, int64_t F, int64_t V, const uint8_t* keep_face, int reindex,
+                          const void* workspace, int* out_faces, int* vertex_map, int* kept_vertices, void* stream);
+int cnr_weld_runs(const int* rows, const int64_t* sorted_keys, const int64_t* perm, int64_t V, int* rep, int* err,
+                  void* stream);
+int cnr_mesh_remap_faces(const int* faces, int64_t F, const int* remap, int drop_degenerate, int* out_faces, uint8_t* keep,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

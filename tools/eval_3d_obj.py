@@ -1,6 +1,7 @@
 """3-D metrics of the reconstructed meshes (metric/eval_3D_obj.py's command line and output files), on cnr_amd.metrics:
 
     python tools/eval_3d_obj.py --data_dir Datasets/Replica --log_dir logs/Replica [--log_dir_ref DIR] [--iteration 10000]
+                                [--clean keep_largest=1,...]
 
 For every scene of the dataset (the last component of --data_dir: Replica or ScanNet) whose <log_dir>/<scene>/scene_mesh exists,
 every object mesh iteration_<it>_obj<id>.obj written by train.py is scored against its ground-truth mesh in
@@ -10,7 +11,9 @@ metrics_3D_obj.npy ((3, objects, 1)).  N = 10 000 samples per object, 200 000 fo
 the union of the background classes' meshes) -- as in the reference, id 0 is left out where the ids are parsed from the file
 names.  A --log_dir_ref mesh it_<it>_obj<id>.obj, where present, sets the crop box instead of the ground truth.
 Differences from the reference: only the meshes of --iteration are listed (the reference lists every .obj and then opens
-the --iteration one), scenes without a scene_mesh directory are skipped, and the samples are seeded (cnr_amd.metrics)."""
+the --iteration one), scenes without a scene_mesh directory are skipped, and the samples are seeded (cnr_amd.metrics).
+--clean (default off; the reference scores the mesh as it is) drops the reconstruction's floaters first: the options of
+cnr_amd.meshops.clean_mesh as name=value pairs, e.g. keep_largest=1 or min_area_fraction=0.01,weld=0."""
 import argparse
 import csv
 import json
@@ -86,8 +89,11 @@ def main(argv=None):
     ap.add_argument("--log_dir", default="logs/Replica", type=str)
     ap.add_argument("--log_dir_ref", default="", type=str)
     ap.add_argument("--iteration", default=10000, type=int)
+    ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
     args = ap.parse_args(argv)
+    from cnr_amd.meshops import clean_mesh, parse_clean_options
     from cnr_amd.metrics import calc_3d_metric
+    clean = parse_clean_options(args.clean) if args.clean else None
     from cnr_amd.vis import load_mesh
 
     dataset = os.path.basename(os.path.normpath(args.data_dir))
@@ -120,6 +126,10 @@ def main(argv=None):
                 mesh_gt = load_mesh(os.path.join(gt_dir, "mesh_semantic.ply_%d.ply" % obj_id) if dataset == "Replica"
                                     else os.path.join(gt_dir, "%s_vh_clean_2.ply_%d.ply" % (exp, obj_id)))
             mesh_rec = load_mesh(os.path.join(mesh_dir, "iteration_%d_obj%d.obj" % (args.iteration, obj_id)))
+            if clean is not None:
+                mesh_rec, report = clean_mesh(mesh_rec, **clean)
+                print("obj %d: kept %d of %d components, %d of %d faces" % (obj_id, report["n_kept"], report["n_components"],
+                                                                           report["faces_out"], report["faces_in"]))
             ref_file = os.path.join(mesh_dir_ref, "it_%d_obj%d.obj" % (args.iteration, obj_id))
             mesh_ref = load_mesh(ref_file) if os.path.exists(ref_file) else mesh_gt
             metrics = calc_3d_metric(mesh_rec, mesh_ref, N=N, mesh_gt=mesh_gt)

@@ -3,11 +3,12 @@ training run's log directory, the instance's pose from the dataset's registratio
 frames -- the partially observed case -- and every start is optimised in the same launches.
 
     python tools/fit_codes.py --config CFG.json --logdir LOGS --inst I [--frames a:b] [--starts mean,objects] [--iters 500]
-                              [--rays 120] [--seed 0] [--mesh OUT.obj] [--grid 128]
+                              [--rays 120] [--seed 0] [--mesh OUT.obj] [--grid 128] [--clean keep_largest=1,...]
 
 --starts: a comma list of mean | objects | randomM (M random starts).  Prints the score of every start before and after, writes
 LOGS/codes_<I>.pt = {inst_id, cls_id, start, score, shape_code, texture_code, scores, codes (M,2,L)} and, with --mesh, the mesh
-of the best start (the category's checkpoint stays as it is)."""
+of the best start (the category's checkpoint stays as it is); --clean (default off) hands Trainer.meshing the options of
+cnr_amd.meshops.clean_mesh as name=value pairs, so floaters are dropped before the colour pass."""
 import argparse
 import glob
 import os
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mesh", default=None)
     ap.add_argument("--grid", type=int, default=128)
+    ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
     a = ap.parse_args()
     import cnr_amd as cnr
     from cnr_amd.code_fit import CodeFitter, load_category
@@ -88,7 +90,7 @@ def main():
         if box is None:
             raise SystemExit(f"--mesh: instance {a.inst} has no bbox3D in the registration result, and meshing needs its extent")
         fit.attach(trainer, a.inst, extent=np.asarray(box.extent))
-        mesh = trainer.meshing(a.inst, grid_dim=a.grid)
+        mesh = trainer.meshing(a.inst, grid_dim=a.grid, clean=cnr.meshops.parse_clean_options(a.clean) if a.clean else None)
         if mesh is None:
             print("no surface at 0.5 occupancy: no mesh written")
         else:

@@ -3,11 +3,13 @@
 is scored by the same command as the trained meshes.
 
     python tools/tsdf_mesh.py --config CFG --out DIR [--inst ID ...] [--voxel 0.01] [--iteration 10000]
+                                 [--clean keep_largest=1,...]
 
 The sequence is loaded with get_dataset (a cached registration result gives inst_dict; its frame_info names every instance's
 frames).  Without --inst every instance is fused, the background (id 0) included.  Written: DIR/iteration_<IT>_obj<ID>.obj;
 printed: one JSON line per object with V, F, units and seconds.  An instance whose volume has no triangle is reported and
-skipped."""
+skipped.  --clean (default off) drops floaters before the file is written: the options of cnr_amd.meshops.clean_mesh as
+name=value pairs (weld=0 also welds the seams between separately fused volumes)."""
 import argparse
 import json
 import os
@@ -38,6 +40,7 @@ def main(argv=None):
     ap.add_argument("--inst", type=int, nargs="*", default=None)
     ap.add_argument("--voxel", type=float, default=0.01)
     ap.add_argument("--iteration", type=int, default=10000)
+    ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
     a = ap.parse_args(argv)
     import torch
 
@@ -50,6 +53,7 @@ def main(argv=None):
     if missing:
         raise SystemExit(f"no instance {missing} in the sequence (it has {sorted(frames_of)})")
     os.makedirs(a.out, exist_ok=True)
+    clean = cnr.meshops.parse_clean_options(a.clean) if a.clean else None
     for inst_id in wanted:
         t = time.perf_counter()
         row = dict(obj=inst_id, frames=len(frames_of[inst_id]))
@@ -59,9 +63,13 @@ def main(argv=None):
         except ValueError as e:
             print(json.dumps(dict(row, skipped=str(e))), flush=True)
             continue
+        units = mesh.units
+        if clean is not None:
+            mesh, report = cnr.meshops.clean_mesh(mesh, **clean)
+            row.update(components=report["n_components"], kept=report["n_kept"])
         path = mesh.export(os.path.join(a.out, "iteration_%d_obj%d.obj" % (a.iteration, inst_id)))
         torch.cuda.synchronize()
-        print(json.dumps(dict(row, V=len(mesh.vertices), F=len(mesh.faces), units=mesh.units, seconds=round(time.perf_counter() - t, 3),
+        print(json.dumps(dict(row, V=len(mesh.vertices), F=len(mesh.faces), units=units, seconds=round(time.perf_counter() - t, 3),
                               file=path)), flush=True)
 
 
