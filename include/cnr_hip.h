@@ -1349,6 +1349,35 @@ int cnr_weld_runs(const int* rows, const int64_t* sorted_keys, const int64_t* pe
 int cnr_mesh_remap_faces(const int* faces, int64_t F, const int* remap, int drop_degenerate, int* out_faces, uint8_t* keep,
                          void* stream);
 
+/* ---- image-space view scores: PSNR, SSIM, depth L1 and mask IoU sums per (image, row) (csrc/image_metric.hip; DESIGN.md
+ * section 3.18).  N pairs of W x H images, (N,W,H,...) contiguous, pixel (w,h) at w H + h.  rgb_rec (N,W,H,3) f32; rgb_gt f32
+ * (gt_u8 = 0) or u8 (gt_u8 = 1: a byte v enters as the double v / 255.0, an f32 as its exact double).  depth_rec, depth_gt
+ * (N,W,H) f32, 0 = nothing there, both NULL with has_depth = 0.  label_rec, label_gt (N,W,H) i32, both NULL with has_labels = 0
+ * (then K must be 0).  ids (K,) i32 on the device, strictly ascending (NOT checked here: the caller does, on the host),
+ * 0 <= K <= 255; may be NULL with K = 0.  Row k < K: the pixels with label_gt == ids[k]; row K: every pixel.
+ *
+ * counts (7,N,K+1) i64, field-major: n_pix, n_ssim, n_both, n_only_rec, n_only_gt, n_rec, inter.  sums (3,N,K+1) f64: se,
+ * ssim, depth_abs.  se = sum over the row's pixels and 3 channels of (a - b)^2 in double.  n_ssim / ssim: the row's pixels
+ * whose 11 x 11 window lies inside the image, and the sum over them of S averaged over the channels; S is Wang et al.'s SSIM
+ * with the normalised Gaussian weights exp(-i^2 / 4.5), i = -5..5, moments accumulated in double, C1 = 1e-4, C2 = 9e-4.  "hit"
+ * is depth > 0: n_both, n_only_rec, n_only_gt count, depth_abs sums |double(rec) - double(gt)| over the pixels hit in both
+ * (all 0 without depth).  Row k < K: n_rec = |label_rec == ids[k]|, inter = those with label_gt == ids[k] too; row K: n_rec =
+ * W H and inter = |label_rec == label_gt| (both 0 without labels).  A NaN is not masked: it reaches the float sums of every
+ * row that holds the pixel and no count.  ssim_map (N,W,H) f32 (may be NULL): the channel mean of S, 0 where the window is
+ * not inside the image.  W < 11 or H < 11 is valid (n_ssim = 0).
+ *
+ * Tiles of CNR_IMG_TILE_W x CNR_IMG_TILE_H pixels with a 5-pixel halo; no floating-point atomics and no integer ones: every
+ * sum is formed in an order fixed by W, H and the tile shape, so an image's rows are bit-identical from run to run and for
+ * any N it is batched with.  workspace >= cnr_image_scores_workspace_bytes(N, W, H, K), 8-byte aligned.
+ * CNR_E_ARG: W, H or N < 1, K outside 0..255, a required pointer NULL, a flag that contradicts its pointers, K > 0 without
+ * labels.  CNR_E_SHAPE: N > 65535, W or H > 32768. */
+#define CNR_IMG_TILE_W 16
+#define CNR_IMG_TILE_H 32
+int64_t cnr_image_scores_workspace_bytes(int N, int W, int H, int K);
+int cnr_image_scores(const float* rgb_rec, const void* rgb_gt, int gt_u8, const float* depth_rec, const float* depth_gt,
+                     int has_depth, const int* label_rec, const int* label_gt, int has_labels, const int* ids, int K, int N,
+                     int W, int H, void* workspace, float* ssim_map, int64_t* counts, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,28 @@ def newest_checkpoint(logdir, cls_id):
     return files[-1] if files else None
 
 
+def build_scene(config, logdir, allow_pickle=False):
+    """The scene as train.py builds it (cameraInfo, get_dataset, one sceneCategory per class) with the newest checkpoint of
+    every class under `logdir` loaded -> (cfg, data, SceneRenderer).  tools/eval_views.py builds its scene here too."""
+    import cnr_amd as cnr
+    from cnr_amd.scene_cateogries import cameraInfo, sceneCategory
+    cfg = cnr.cfg.Config(config)
+    cam_info = cameraInfo(cfg)
+    data = cnr.dataset.get_dataset(cfg)
+    cls_dict, scene_bg = {}, None
+    for cls_id in data.inst_dict.keys():                              # train.py:46-64
+        sc = sceneCategory(cfg, cls_id, data.inst_dict[cls_id], data.sample_dict, cam_info.rays_dir_cache)
+        ckpt = newest_checkpoint(logdir, cls_id)
+        if ckpt is None:
+            raise SystemExit("no checkpoint of class {} under {}".format(cls_id, logdir))
+        sc.load_checkpoints(ckpt, allow_pickle=allow_pickle)
+        if cls_id == 0:
+            scene_bg = sc
+        else:
+            cls_dict[cls_id] = sc
+    return cfg, data, cnr.view.SceneRenderer(cls_dict, scene_bg, cfg)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True)
@@ -45,22 +67,7 @@ def main():
                     "scalar ids (trusted files only)")
     a = ap.parse_args()
     import cnr_amd as cnr
-    from cnr_amd.scene_cateogries import cameraInfo, sceneCategory
-    cfg = cnr.cfg.Config(a.config)
-    cam_info = cameraInfo(cfg)
-    data = cnr.dataset.get_dataset(cfg)
-    cls_dict, scene_bg = {}, None
-    for cls_id in data.inst_dict.keys():                              # train.py:46-64
-        sc = sceneCategory(cfg, cls_id, data.inst_dict[cls_id], data.sample_dict, cam_info.rays_dir_cache)
-        ckpt = newest_checkpoint(a.logdir, cls_id)
-        if ckpt is None:
-            raise SystemExit("no checkpoint of class {} under {}".format(cls_id, a.logdir))
-        sc.load_checkpoints(ckpt, allow_pickle=a.allow_pickle)
-        if cls_id == 0:
-            scene_bg = sc
-        else:
-            cls_dict[cls_id] = sc
-    renderer = cnr.view.SceneRenderer(cls_dict, scene_bg, cfg)
+    cfg, data, renderer = build_scene(a.config, a.logdir, a.allow_pickle)
     transforms = {}
     for inst, tx, ty, tz in a.move:
         E = np.eye(4)
