@@ -251,7 +251,7 @@ def test_one_launch_object_row_forms_against_precise_emulation(cnr, dev, n_obj, 
     assert (num / den) ** 0.5 < 5e-3
 
 
-@pytest.mark.parametrize("C,n_obj,L", [(1, 4, 256), (2, 3, 32), (1, 7, 64), (1, 1, 32), (2, 12, 32)])
+@pytest.mark.parametrize("C,n_obj,L", [(1, 4, 256), (2, 3, 32), (1, 7, 64), (1, 1, 32), (2, 12, 32), (1, 33, 32), (1, 64, 64)])
 def test_latent_bwd_against_autograd(cnr, dev, C, n_obj, L):
     """cnr_latent_fwd / cnr_latent_bwd (a7 + the four latent layers + the code regulariser, src/model.py:38-51,
     src/loss.py:5-15) against torch autograd on given bias-row gradients: <= 1e-5; trunk entries are ADDED."""

@@ -79,8 +79,10 @@ def _step_tail(_C, theta, lay, L, n_obj, C, zl, ws, nwg, fix, reg, fill):
 
 # (1, 4, 32, 1) one record; (.., 3) an empty quarter; (2, 3, 32, 37) and (2, 15, 32, 50) two classes, ragged quarters;
 # (.., 129) per = 33: one full chunk and a rest of one; (1, 4, 256, 256) the benchmarked count; (1, 7, 64, 260) per = 65: the
-# loop beyond one round of loads
-SHAPES = [(1, 4, 32, 1), (1, 4, 32, 3), (2, 3, 32, 37), (1, 4, 32, 129), (1, 4, 256, 256), (1, 7, 64, 260), (2, 15, 32, 50)]
+# loop beyond one round of loads; (1, 20, 32, 37) and (2, 100, 32, 130) more than 15 objects: the record carries no row sums (the
+# one-object-per-tile form), so that whole region is unwritten
+SHAPES = [(1, 4, 32, 1), (1, 4, 32, 3), (2, 3, 32, 37), (1, 4, 32, 129), (1, 4, 256, 256), (1, 7, 64, 260), (2, 15, 32, 50),
+          (1, 20, 32, 37), (2, 100, 32, 130)]
 
 
 @pytest.mark.parametrize("C,n_obj,L,nwg", SHAPES)
