@@ -1,6 +1,8 @@
 """The mesh as a graph, on the device (csrc/mesh_topo.hip): welding of coincident vertices, connected
 components by edge or by vertex with their table (faces, vertices, area, bounding box, boundary / non-manifold edges,
-watertightness), compaction of a face selection, and ``clean_mesh``: dropping the floaters of a marching-cubes mesh.
+watertightness), compaction of a face selection, and ``clean_mesh``: dropping the floaters of a marching-cubes mesh.  And making
+it smaller (csrc/mesh_simplify.hip): ``simplify``, uniform vertex clustering with quadric placement, and
+``vertex_normals``.
 
 Device tensors in and out (``clean_mesh`` and ``mesh_to_device`` take a host ``vis.Mesh``).  The sorts are
 ``torch.sort(stable=True)``, every other step is a HIP kernel; there is no CPU path.  A union/find loop that runs out of its bound
@@ -17,6 +19,8 @@ LARGEST_BY = ("area", "faces", "diag")
 
 def _raise_if_set(err, what):
     e = int(err.item())
+    if e & 4:
+        raise ValueError(f"{what}: a vertex is not finite, or the grid has more than 2^21 cells on an axis")
     if e & 2:
         raise ValueError(f"{what}: an index lies outside its range")
     if e & 1:
@@ -393,5 +397,269 @@ def parse_clean_options(text):
         k = k.strip()
         if k not in kinds or not v.strip():
             raise ValueError(f"--clean: cannot read {item!r}; options are {sorted(kinds)} as name=value")
+        out[k] = kinds[k](v.strip())
+    return out
+
+
+# ---- simplification: uniform vertex clustering with quadric placement (csrc/mesh_simplify.hip) -------
+PLACEMENT = ("quadric", "mean", "representative")
+SEARCH_TRIALS = 24
+TOTAL_BLOCK = 256
+
+
+def _segment_sum(items, gather, gather_div, sorted_seg, C, err):
+    """(C,K) f64: cnr_segment_sum_f64 of items (n,K) f64 over the positions of sorted_seg (N,) i32, ascending"""
+    K, N = items.shape[1], len(sorted_seg)
+    out = torch.empty(C, K, device=items.device, dtype=torch.float64)
+    _C.call("cnr_segment_sum_f64", items, gather, int(gather_div), sorted_seg, N, len(items), K, C, out, err)
+    return out
+
+
+def _fixed_order_total(values, err):
+    """the sum of values (n,) f64 in an order fixed by n alone: cnr_segment_sum_f64 over blocks of TOTAL_BLOCK consecutive values,
+    again over the blocks' sums while more than TOTAL_BLOCK are left, then over what is left as one segment -> (1,) f64"""
+    dev = values.device
+    while len(values) > TOTAL_BLOCK:
+        n = len(values)
+        seg = (torch.arange(n, device=dev) // TOTAL_BLOCK).to(torch.int32)
+        values = _segment_sum(values.view(n, 1), None, 1, seg, -(-n // TOTAL_BLOCK), err).view(-1)
+    return _segment_sum(values.view(len(values), 1), None, 1, torch.zeros(len(values), device=dev, dtype=torch.int32), 1, err).view(-1)
+
+
+def _clusters(verts, cell, err, mark=lambda name: None):
+    """the cells of cnr_voxel_keys as weld(cell > 0) numbers them -> (min (3,) f32, keys (V,) i64, roots (C,) i32, cluster (V,) i32)"""
+    V, dev = len(verts), verts.device
+    lib = _C.load()
+    mn = torch.empty(3, device=dev, dtype=torch.float32)
+    _C.call("cnr_points_min", verts, V, _C.workspace(lib.cnr_points_min_workspace_bytes(V), dev, "cnr_points_min"), mn)
+    keys = torch.empty(V, device=dev, dtype=torch.int64)
+    _C.call("cnr_voxel_keys", verts, V, mn, float(cell), keys)
+    _C.call("cnr_simplify_check_keys", keys, V, err)
+    mark("keys")
+    skeys, perm = torch.sort(keys, stable=True)
+    mark("sort_keys")
+    rep = torch.empty(V, device=dev, dtype=torch.int32)
+    _C.call("cnr_weld_runs", None, skeys, perm, V, rep, err)
+    _raise_if_set(err, "simplify")
+    roots = _roots(rep, None, V)
+    cluster = torch.empty(V, device=dev, dtype=torch.int32)
+    _C.call("cnr_mesh_assign", rep, None, V, roots, len(roots), cluster, err)
+    return mn, keys, roots, cluster
+
+
+def _cluster_faces(f, cluster, C, err, mark=lambda name: None):
+    """-> (corner clusters (F,3) i32 of EVERY input face, the faces with three distinct clusters (F1,3) i32 in their old order,
+    keep (F1,) u8 = 1 for the lowest face of every run of equal rows).  Rows: the face rotated so that its smallest index leads;
+    (a, c, b) is another row than (a, b, c)."""
+    F, dev = len(f), f.device
+    corners = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    keep = torch.empty(F, device=dev, dtype=torch.uint8)
+    _C.call("cnr_mesh_remap_faces", f, F, cluster, 1, corners, keep)
+    f1 = compact(corners, C, keep, reindex=False)
+    mark("remap")
+    F1 = len(f1)
+    if F1 == 0:
+        return corners, f1, torch.zeros(0, device=dev, dtype=torch.uint8)
+    rows = torch.empty(F1, 3, device=dev, dtype=torch.int32)
+    _C.call("cnr_simplify_face_rows", f1, F1, rows)
+    mark("face_rows")
+    perm = torch.arange(F1, device=dev)
+    for axis in (2, 1, 0):                                               # three stable sorts, as weld's exact mode
+        perm = perm[torch.sort(rows[perm, axis], stable=True)[1]]
+    mark("sort_rows")
+    rep = torch.empty(F1, device=dev, dtype=torch.int32)
+    _C.call("cnr_weld_runs", rows, None, perm.contiguous(), F1, rep, err)
+    keep1 = (rep == torch.arange(F1, device=dev, dtype=torch.int32)).to(torch.uint8)
+    mark("duplicates")
+    return corners, f1, keep1
+
+
+def _faces_out(verts, f, cell):
+    """the integer stages only: the number of faces simplify(cell) returns"""
+    err = torch.zeros(1, device=verts.device, dtype=torch.int32)
+    _, _, roots, cluster = _clusters(verts, cell, err)
+    _, _, keep1 = _cluster_faces(f, cluster, len(roots), err)
+    _raise_if_set(err, "simplify")
+    return int(keep1.sum().item()) if len(keep1) else 0
+
+
+def search_cell(target_faces, diag, faces_out):
+    """Bisection of the cell size on the host, in its logarithm, between diag and diag / 2^20, at most SEARCH_TRIALS calls of
+    faces_out(cell) -> (cell, [(cell, faces_out), ...]): the finest cell tried whose faces_out <= target_faces."""
+    target = int(target_faces)
+    if target < 0:
+        raise ValueError("target_faces must be >= 0")
+    if not (diag > 0 and np.isfinite(diag)):
+        raise ValueError("target_faces needs a bounding box with a finite, positive diagonal")
+    trials = []
+
+    def run(cell):
+        trials.append((cell, int(faces_out(cell))))
+        return trials[-1][1]
+    hi, lo = float(diag), float(diag) / 2.0 ** 20
+    if run(hi) > target:
+        raise ValueError(f"target_faces={target}: even a cell of the bounding-box diagonal leaves {trials[-1][1]} faces")
+    if run(lo) > target:
+        while len(trials) < SEARCH_TRIALS:
+            mid = float(np.sqrt(lo * hi))
+            if not lo < mid < hi:
+                break
+            if run(mid) <= target:
+                hi = mid
+            else:
+                lo = mid
+    return min(c for c, n in trials if n <= target), trials
+
+
+def _bbox_diag(verts):
+    lo, hi = verts.amin(0).double().cpu().numpy(), verts.amax(0).double().cpu().numpy()
+    d = hi - lo
+    return float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+
+
+def simplify(verts, faces, cell=None, target_faces=None, placement="quadric", tau=1e-3, details=False, timer=None):
+    """Uniform vertex clustering with quadric placement (Lindstrom 2000; the quadrics per corner, as open3d's
+    simplify_vertex_clustering).  verts (V,3) f32, faces (F,3) on the device -> (verts' (V',3) f32, faces' (F',3) i32,
+    vertex_map (V,) i32: the output vertex of every input vertex or -1, report).
+
+    The clusters are the cells of the grid of pitch `cell` through min - cell / 2 (weld's), numbered by their lowest input
+    vertex.  Every input face adds its plane quadric, weighted by its squared area, to the cluster of each of its corners.
+    placement: "quadric" = the minimiser of the cluster's quadric about the cluster mean, eigenvalues <= tau x the largest
+    dropped, clamped per axis to the cluster's cell; "mean" = the mean of the cluster's vertices; "representative" = the
+    lowest input vertex, bit-exact (weld's choice).  Faces with fewer than three distinct clusters are dropped, then every face
+    that repeats an earlier one (the same three clusters in the same cyclic order; the opposite orientation is another face);
+    clusters no face uses are dropped last.  A surviving face keeps its corner order.
+    Exactly one of cell and target_faces: target_faces bisects the cell on the host (search_cell) over the integer stages.
+    report: cell, clusters, faces_in, faces_collapsed, faces_duplicate, faces_out, vertices_out, clamped (clusters the clamp
+    moved), quadric_error (the clusters' errors x^T A x - 2 b^T x + c summed in a fixed order: _fixed_order_total), search
+    [(cell, faces_out), ...], representatives (V',) i32 = the lowest input vertex of every output vertex's cluster; with
+    details=True also cluster (V,) i32, roots (C,), quadrics (C,10), possum (C,3), cluster_error (C,), cluster_clamped (C,),
+    cluster_verts (C,3), kept_clusters (V',).  A non-finite vertex or more than 2^21 cells on an axis raises ValueError."""
+    if placement not in PLACEMENT:
+        raise ValueError(f"placement must be one of {PLACEMENT}, not {placement!r}")
+    if (cell is None) == (target_faces is None):
+        raise ValueError("give exactly one of cell and target_faces")
+    if cell is not None and not (float(cell) > 0 and np.isfinite(float(cell))):
+        raise ValueError("cell must be > 0")
+    if not 0 <= float(tau) < 1:
+        raise ValueError("tau must lie in [0, 1)")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must have the shape (V,3), not {tuple(verts.shape)}")
+    verts = verts.float().contiguous()
+    V, dev = len(verts), verts.device
+    f = _faces_i32(faces, V, "simplify")
+    F = len(f)
+    if V > 0x7f800000:
+        raise ValueError("simplify: V must stay below 2^31 - 2^23 (the face rows are compared as cnr_weld_runs compares rows)")
+    mark = timer or (lambda name: None)
+    z32 = torch.zeros(0, device=dev, dtype=torch.int32)
+    report = dict(cell=None if cell is None else float(cell), clusters=0, faces_in=F, faces_collapsed=0, faces_duplicate=0,
+                  faces_out=0, vertices_out=0, clamped=0, quadric_error=0.0, search=[], representatives=z32)
+
+    def empty():
+        return (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, device=dev, dtype=torch.int32),
+                torch.full((V,), -1, device=dev, dtype=torch.int32), report)
+    if F == 0 or V == 0:
+        return empty()
+    if cell is None:
+        cell, report["search"] = search_cell(target_faces, _bbox_diag(verts), lambda c: _faces_out(verts, f, c))
+        report["cell"] = cell
+    cell = float(cell)
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    mn, keys, roots, cluster = _clusters(verts, cell, err, mark)
+    C = len(roots)
+    mark("cluster_ids")
+    corners, f1, keep1 = _cluster_faces(f, cluster, C, err, mark)
+    _raise_if_set(err, "simplify")
+    F1 = len(f1)
+    report.update(clusters=C, faces_collapsed=F - F1)
+    if details:
+        report.update(cluster=cluster, roots=roots, keys=keys, min=mn)
+    if F1 == 0:
+        return empty()
+    out_f, cmap, kept_c = compact(f1, C, keep1)
+    mark("compact")
+    # the fp64 part: every input face's record to the cluster of each corner, the clusters' position sums, the placement
+    records = torch.empty(F, 10, device=dev, dtype=torch.float64)
+    _C.call("cnr_simplify_face_records", verts, f, mn, F, V, records, err)
+    mark("records")
+    sseg, cperm = torch.sort(corners.view(-1), stable=True)
+    mark("sort_corners")
+    quadrics = _segment_sum(records, cperm, 3, sseg, C, err)
+    mark("sum_quadrics")
+    possum = sclu = None
+    if placement != "representative":
+        q = torch.empty(V, 3, device=dev, dtype=torch.float64)
+        _C.call("cnr_simplify_vertex_q", verts, mn, V, q)
+        sclu, vperm = torch.sort(cluster, stable=True)
+        mark("sort_vertices")
+        possum = _segment_sum(q, vperm, 1, sclu, C, err)
+        mark("sum_positions")
+    placed = torch.empty(C, 3, device=dev, dtype=torch.float32)
+    cerr = torch.empty(C, device=dev, dtype=torch.float64)
+    clamped = torch.empty(C, device=dev, dtype=torch.uint8)
+    _C.call("cnr_simplify_place", quadrics, possum, sclu, verts, roots, keys, mn, V, C, cell, float(tau), PLACEMENT.index(placement),
+            placed, cerr, clamped, err)
+    mark("place")
+    total = _fixed_order_total(cerr, err)
+    mark("total_error")
+    _raise_if_set(err, "simplify")
+    out_v = placed.index_select(0, kept_c.long())
+    vertex_map = cmap.index_select(0, cluster.long())
+    mark("gather")
+    report.update(faces_duplicate=F1 - len(out_f), faces_out=len(out_f), vertices_out=len(kept_c), clamped=int(clamped.sum().item()),
+                  quadric_error=float(total.item()), representatives=roots.index_select(0, kept_c.long()))
+    if details:
+        report.update(quadrics=quadrics, possum=possum, cluster_error=cerr, cluster_clamped=clamped, cluster_verts=placed,
+                      kept_clusters=kept_c)
+    return out_v, out_f, vertex_map, report
+
+
+def vertex_normals(verts, faces):
+    """(V,3) f32: the normalised sum of (p1 - p0) x (p2 - p0) over the faces at each vertex (area-weighted), summed in fp64 in
+    cnr_segment_sum_f64's order over the corners sorted stably by vertex.  By vis.py's orientation convention it points to the
+    side the marching-cubes normals point to.  A vertex no face uses, or whose sum is zero, gets zeros."""
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must have the shape (V,3), not {tuple(verts.shape)}")
+    verts = verts.float().contiguous()
+    V, dev = len(verts), verts.device
+    f = _faces_i32(faces, V, "vertex_normals")
+    F = len(f)
+    out = torch.zeros(V, 3, device=dev, dtype=torch.float32)
+    if F == 0 or V == 0:
+        return out
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    fn = torch.empty(F, 3, device=dev, dtype=torch.float64)
+    _C.call("cnr_mesh_face_normals_f64", verts, f, F, V, fn, err)
+    sseg, perm = torch.sort(f.view(-1), stable=True)
+    sums = _segment_sum(fn, perm, 3, sseg, V, err)
+    _raise_if_set(err, "vertex_normals")
+    _C.call("cnr_mesh_normals_finish", sums, V, out)
+    return out
+
+
+def simplify_mesh(mesh, cell=None, target_faces=None, placement="quadric", tau=1e-3, device=None):
+    """``simplify`` of a ``vis.Mesh`` -> (mesh, report).  Positions are the device result as float64; the colour of an output
+    vertex is its cluster representative's (the lowest input index, as weld: no averaging); normals are ``vertex_normals`` of
+    the output."""
+    d = mesh_to_device(mesh, device)
+    v, f, _, report = simplify(d["verts"], d["faces"], cell=cell, target_faces=target_faces, placement=placement, tau=tau)
+    out = Mesh(v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(np.int64).reshape(-1, 3),
+               vertex_normals(v, f).cpu().numpy().astype(np.float64))
+    out.visual.vertex_colors = mesh.visual.vertex_colors[report["representatives"].cpu().numpy().astype(np.int64)]
+    return out, report
+
+
+def parse_simplify_options(text):
+    """the tools' ``--simplify`` string, e.g. "cell=0.02,placement=mean" or "target_faces=20000" -> the dict of simplify options"""
+    kinds = dict(cell=float, target_faces=int, placement=str, tau=float)
+    out = {}
+    for item in (text or "").split(","):
+        if not item.strip():
+            continue
+        k, _, v = item.partition("=")
+        k = k.strip()
+        if k not in kinds or not v.strip():
+            raise ValueError(f"--simplify: cannot read {item!r}; options are {sorted(kinds)} as name=value")
         out[k] = kinds[k](v.strip())
     return out

@@ -57,7 +57,7 @@ class Trainer:
         self.shape_codes = self.shape_codes.to(self.device)
         self.texture_codes = self.texture_codes.to(self.device)
 
-    def meshing(self, inst_id=None, grid_dim=256, normals="grid", clean=None):
+    def meshing(self, inst_id=None, grid_dim=256, normals="grid", clean=None, simplify=None):
         """src/trainer.py:62-123: occupancy on a grid_dim^3 grid over the object's box, marching cubes at 0.5 ('ascent'),
         back to scene coordinates, vertex colours from eval_points.  None where the reference returns None.
         normals: "grid" = the lattice differences marching cubes interpolates (skimage's, faceted on a coarse grid); "field" =
@@ -65,7 +65,11 @@ class Trainer:
         normals do (vis.py); a vertex whose gradient is exactly zero keeps its grid normal.
         clean: None, or a dict of meshops.clean_mesh options (keep_largest=1, min_faces=..., weld=...): the floaters are dropped on
         the device, in scene coordinates, BEFORE the colour pass, so the field is never evaluated at a dropped vertex; the report is
-        left in self.last_clean_report."""
+        left in self.last_clean_report.
+        simplify: None, or a dict of meshops.simplify options (cell=... or target_faces=..., placement=..., tau=...): vertex
+        clustering with quadric placement on the device, in scene coordinates, AFTER clean and BEFORE the colour pass, so the
+        colours are the field's at the new vertices; normals="grid" then means meshops.vertex_normals of the output faces.  The
+        report is left in self.last_simplify_report; None when no face survives."""
         if normals not in ("grid", "field"):
             raise ValueError("normals must be 'grid' or 'field', not {!r}".format(normals))
         occ_range = [-1., 1.]
@@ -110,6 +114,17 @@ class Trainer:
             kept_faces, kept, self.last_clean_report = meshops.clean_device(pts, tri, **dict(clean))
             idx = kept.cpu().numpy().astype(np.int64)
             mesh = vis.Mesh(mesh.vertices[idx], kept_faces.cpu().numpy().astype(np.int64).reshape(-1, 3), mesh.vertex_normals[idx])
+        if simplify is not None:
+            from . import meshops
+            pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
+            tri = torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int32)).to(self.device)
+            pts, tri, _, self.last_simplify_report = meshops.simplify(pts, tri, **dict(simplify))
+            if len(tri) == 0:
+                print("simplification left no face")
+                return None
+            # the lattice normals do not exist at moved vertices: "grid" takes the output faces' own, "field" replaces them below
+            mesh = vis.Mesh(pts.cpu().numpy().astype(np.float64), tri.cpu().numpy().astype(np.int64).reshape(-1, 3),
+                            meshops.vertex_normals(pts, tri).cpu().numpy().astype(np.float64))
         vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
         ret = self.eval_points(vertices_pts) if self.cls_id == 0 else self.eval_points(vertices_pts, inst_id=inst_id)
         if ret is None:

@@ -1349,6 +1349,43 @@ int cnr_weld_runs(const int* rows, const int64_t* sorted_keys, const int64_t* pe
 int cnr_mesh_remap_faces(const int* faces, int64_t F, const int* remap, int drop_degenerate, int* out_faces, uint8_t* keep,
                          void* stream);
 
+/* ---- mesh simplification: uniform vertex clustering with quadric placement (csrc/mesh_simplify.hip) ----
+ * The clusters are the cells of cnr_voxel_keys, numbered by cnr_weld_runs / cnr_mesh_roots_* / cnr_mesh_assign; the faces go
+ * through cnr_mesh_remap_faces and cnr_mesh_compact_*.  These entry points add the fp64 part and the face rows.  No
+ * floating-point atomics, every sum in an order fixed by the data, bit-identical run to run; none needs a workspace.  err (1,)
+ * i32 on the device, zeroed by the caller, as above: |= 2 for an index outside its range (the entry is skipped), |= 4 for a
+ * vertex without a cell (key -1).  The arithmetic, operation by operation, is csrc/mesh_simplify_common.h.
+ *
+ * check_keys: err |= 4 when a key (V,) i64 is negative.  vertex_q: q (V,3) f64 = (double)verts - (double)min_xyz.
+ * face_records: records (F,10) f64 per face, with q as above, n = (q1 - q0) x (q2 - q0) (products rounded, then the difference),
+ * d = (nx q0x + ny q0y) + nz q0z: nx nx, nx ny, nx nz, ny ny, ny nz, nz nz, nx d, ny d, nz d, d d.
+ * face_normals_f64: normals (F,3) f64 = (p1 - p0) x (p2 - p0) of the fp32 corners as doubles.
+ * segment_sum_f64: items (n_items,K) f64, 1 <= K <= 16; position j < N belongs to segment sorted_seg[j] (i32, ascending) and
+ * takes item gather[j] / gather_div (gather (N,) i64; NULL: item j); out (C,K) f64.  A group of 16 lanes per segment: lane l
+ * adds the segment's positions l, l + 16, ... in ascending order from 0.0, then a[l] += a[l ^ 8], ^ 4, ^ 2, ^ 1, lane 0 writes;
+ * an empty segment gives zeros.
+ * place: per cluster c < C with representative roots[c] and cell keys[roots[c]] (keys (V,) i64 in INPUT order); quadrics (C,10)
+ * and possum (C,3) the segment sums of the records and of q; sorted_cluster (V,) i32 the vertices' clusters sorted (for the
+ * count).  placement 0: x = mean + pinv_tau(A) (b - A mean) by a cyclic Jacobi decomposition, eigenvalues <= tau * the largest
+ * dropped; 1: the mean; both clamped per axis to [(i - 0.5) cell, (i + 0.5) cell], moved back by + min and rounded to fp32
+ * (stepped one unit in the last place back when that rounding left the cell); 2: verts[roots[c]] as it is (possum and
+ * sorted_cluster may be NULL).  error (C,) f64 = x^T A x - 2 b^T x + c at the fp64 position, clamped (C,) u8.
+ * face_rows: rows (F,3) i32 = the face rotated so that its smallest index leads.  normals_finish: out (V,3) f32 = sums (V,3) f64
+ * divided by their length sqrt((x x + y y) + z z), zeros where that is 0 or not finite. */
+int cnr_simplify_check_keys(const int64_t* keys, int64_t V, int* err, void* stream);
+int cnr_simplify_vertex_q(const float* verts, const float* min_xyz, int64_t V, double* q, void* stream);
+int cnr_simplify_face_records(const float* verts, const int* faces, const float* min_xyz, int64_t F, int64_t V,
+                              double* records, int* err, void* stream);
+int cnr_mesh_face_normals_f64(const float* verts, const int* faces, int64_t F, int64_t V, double* normals, int* err,
+                              void* stream);
+int cnr_segment_sum_f64(const double* items, const int64_t* gather, int gather_div, const int* sorted_seg, int64_t N,
+                        int64_t n_items, int K, int64_t C, double* out, int* err, void* stream);
+int cnr_simplify_place(const double* quadrics, const double* possum, const int* sorted_cluster, const float* verts,
+                       const int* roots, const int64_t* keys, const float* min_xyz, int64_t V, int64_t C, double cell,
+                       double tau, int placement, float* out_verts, double* error, uint8_t* clamped, int* err, void* stream);
+int cnr_simplify_face_rows(const int* faces, int64_t F, int* rows, void* stream);
+int cnr_mesh_normals_finish(const double* sums, int64_t V, float* out, void* stream);
+
 /* ---- image-space view scores: PSNR, SSIM, depth L1 and mask IoU sums per (image, row) (csrc/image_metric.hip; DESIGN.md
  * section 3.18).  N pairs of W x H images, (N,W,H,...) contiguous, pixel (w,h) at w H + h.  rgb_rec (N,W,H,3) f32; rgb_gt f32
  * (gt_u8 = 0) or u8 (gt_u8 = 1: a byte v enters as the double v / 255.0, an f32 as its exact double).  depth_rec, depth_gt

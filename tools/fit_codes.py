@@ -4,11 +4,13 @@ frames -- the partially observed case -- and every start is optimised in the sam
 
     python tools/fit_codes.py --config CFG.json --logdir LOGS --inst I [--frames a:b] [--starts mean,objects] [--iters 500]
                               [--rays 120] [--seed 0] [--mesh OUT.obj] [--grid 128] [--clean keep_largest=1,...]
+                              [--simplify cell=0.02,...]
 
 --starts: a comma list of mean | objects | randomM (M random starts).  Prints the score of every start before and after, writes
 LOGS/codes_<I>.pt = {inst_id, cls_id, start, score, shape_code, texture_code, scores, codes (M,2,L)} and, with --mesh, the mesh
 of the best start (the category's checkpoint stays as it is); --clean (default off) hands Trainer.meshing the options of
-cnr_amd.meshops.clean_mesh as name=value pairs, so floaters are dropped before the colour pass."""
+cnr_amd.meshops.clean_mesh as name=value pairs, so floaters are dropped before the colour pass; --simplify (default off) the
+options of cnr_amd.meshops.simplify (cell=... or target_faces=..., placement=...), applied after --clean and before the colours."""
 import argparse
 import glob
 import os
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--mesh", default=None)
     ap.add_argument("--grid", type=int, default=128)
     ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
+    ap.add_argument("--simplify", default=None, help="simplify the mesh: simplify options as name=value,... e.g. cell=0.02 or target_faces=20000 (default: off)")
     a = ap.parse_args()
     import cnr_amd as cnr
     from cnr_amd.code_fit import CodeFitter, load_category
@@ -90,7 +93,8 @@ def main():
         if box is None:
             raise SystemExit(f"--mesh: instance {a.inst} has no bbox3D in the registration result, and meshing needs its extent")
         fit.attach(trainer, a.inst, extent=np.asarray(box.extent))
-        mesh = trainer.meshing(a.inst, grid_dim=a.grid, clean=cnr.meshops.parse_clean_options(a.clean) if a.clean else None)
+        mesh = trainer.meshing(a.inst, grid_dim=a.grid, clean=cnr.meshops.parse_clean_options(a.clean) if a.clean else None,
+                               simplify=cnr.meshops.parse_simplify_options(a.simplify) if a.simplify else None)
         if mesh is None:
             print("no surface at 0.5 occupancy: no mesh written")
         else:
