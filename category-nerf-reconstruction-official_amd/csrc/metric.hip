@@ -12,6 +12,7 @@
 //   cnr_face_area_scan   per-face area (fp64 cross product of the fp32 corners), its inclusive prefix: block sums, one-workgroup
 //                        scan of them, block scans.
 //   cnr_sample_surface   per sample: searchsorted-left on the prefix, the reflected barycentric point (fp64, rounded once).
+//   cnr_sample_faces     the face index of that search alone, through the same device function.
 //   cnr_clip_box_*       Sutherland-Hodgman against 6 planes in registers (fp64), fan triangulation; classify, scan, emit as
 //                        csrc/mcubes.hip does, so the output is in (face, fan) order.
 #include "cnr_common.h"
@@ -217,20 +218,32 @@ __global__ __launch_bounds__(FA_BLOCK) void fa_scan_kernel(const double* __restr
 }
 
 // ---- surface sampling --------------------------------------------------------------------------------------------------
+// searchsorted(cum, u0 * total, side='left'): the first f with cum[f] >= u0 * total (the last face when there is none)
+__device__ __forceinline__ int64_t sample_face(const double* __restrict__ cum, int64_t F, double total, double u0) {
+  const double target = u0 * total;
+  int64_t lo = 0, hi = F;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (cum[mid] < target) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < F ? lo : F - 1;
+}
+
+// the face index alone (cnr_sample_faces): u is the same (n,3) array of draws, of which only u0 is read
+__global__ __launch_bounds__(256) void sample_faces_kernel(int64_t F, const double* __restrict__ cum, const double* __restrict__ u,
+                                                           int64_t n, int* __restrict__ face_out) {
+  const double total = cum[F - 1];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    face_out[i] = (int)sample_face(cum, F, total, u[3 * i]);
+}
+
 __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int64_t F,
                                                      const double* __restrict__ cum, const double* __restrict__ u, int64_t n,
                                                      float* __restrict__ out) {
   const double total = cum[F - 1];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const double target = u[3 * i] * total;
-    // searchsorted(cum, target, side='left'): the first f with cum[f] >= target
-    int64_t lo = 0, hi = F;
-    while (lo < hi) {
-      const int64_t mid = lo + ((hi - lo) >> 1);
-      if (cum[mid] < target) lo = mid + 1;
-      else hi = mid;
-    }
-    const int64_t f = lo < F ? lo : F - 1;
+    const int64_t f = sample_face(cum, F, total, u[3 * i]);
     double a = u[3 * i + 1], b = u[3 * i + 2];
     if (a + b > 1.0) {
       a = fabs(a - 1.0);
@@ -406,6 +419,15 @@ extern "C" int cnr_sample_surface(const float* verts, const int* faces, int64_t 
   if (F < 1 || n < 0) return CNR_E_SHAPE;
   if (n == 0) return CNR_OK;
   hipLaunchKernelGGL(sample_kernel, dim3(grid_of(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, verts, faces, F, cum, u, n, out);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_sample_faces(const double* cum, int64_t F, const double* u, int64_t n, int* face_out, void* stream) {
+  if (!cum || !u || !face_out) return CNR_E_ARG;
+  if (F < 1 || F > 0x7fffffff || n < 0) return CNR_E_SHAPE;
+  if (n == 0) return CNR_OK;
+  hipLaunchKernelGGL(sample_faces_kernel, dim3(grid_of(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, F, cum, u, n, face_out);
   CNR_LAUNCH_CHECK();
   return CNR_OK;
 }

@@ -5,6 +5,9 @@ tensors, (n,3)) and return Python floats; the exact nearest-neighbour search (th
 ``cnr_nn_dist`` (csrc/metric.hip), fp32 distances of fp32 points, their mean in fp64.  ``calc_3d_metric`` is
 the reference's per-object score: the oriented box of ``mesh_ref``, the reconstruction clipped to it, three area-weighted
 samples, accuracy / completion in cm and the completion ratio at 5 cm in %; the samples stay on the device.
+``point_mesh_distance`` is the exact distance from points to a triangle mesh with the closest face (``cnr_point_mesh_dist``,
+csrc/point_mesh.hip), and ``calc_3d_metric_surface`` the same score with every distance taken to the other
+mesh instead of to samples of it, plus precision / recall / F-score and normal consistency.
 
 Differences from the reference, all deliberate:
 * the ground truth is an argument (``mesh_gt``, default ``mesh_ref``); the reference reads a module-level ``mesh_gt`` and uses
@@ -19,7 +22,8 @@ import torch
 from . import _C
 
 __all__ = ["accuracy", "completion", "accuracy_ratio", "completion_ratio", "chamfer", "nn_dist", "dist_stats",
-           "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images"]
+           "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images",
+           "point_mesh_distance", "sample_surface_faces", "calc_3d_metric_surface"]
 
 
 def _device():
@@ -110,7 +114,7 @@ def _area_scan(tri):
     return area, cum
 
 
-def _sample(tri, count, rng):
+def _sample(tri, count, rng, with_face=False):
     verts, faces, F = tri
     if F < 1:
         raise ValueError("cannot sample a mesh without faces")
@@ -118,13 +122,126 @@ def _sample(tri, count, rng):
     u = torch.from_numpy(rng.random((int(count), 3))).to(verts.device)
     out = torch.empty(int(count), 3, device=verts.device, dtype=torch.float32)
     _C.call("cnr_sample_surface", verts, faces, F, cum, u, int(count), out)
-    return out
+    if not with_face:
+        return out
+    face = torch.empty(int(count), device=verts.device, dtype=torch.int32)
+    _C.call("cnr_sample_faces", cum, F, u, int(count), face)
+    return out, face
 
 
 def sample_surface(mesh, count, seed=0):
     """trimesh.sample.sample_surface's algorithm on the GPU: `count` area-weighted points of `mesh` (a vis.Mesh or anything with
     vertices / faces) from numpy.random.default_rng(seed).random((count, 3)) -> (count, 3) f32 device tensor"""
     return _sample(_mesh_device(mesh, _device()), count, np.random.default_rng(seed))
+
+
+def sample_surface_faces(mesh, count, seed=0):
+    """sample_surface with the face every sample was drawn from -> (points (count,3) f32, face (count,) i32) device tensors;
+    the same draws, so points is bit-equal to sample_surface(mesh, count, seed)"""
+    return _sample(_triangles(mesh, _device()), count, np.random.default_rng(seed), with_face=True)
+
+
+# ---- point to mesh -----------------------------------------------------------------------------------------------------
+def _triangles(mesh, dev, check=True):
+    """a vis.Mesh (anything with vertices / faces), a (verts, faces) pair (arrays or tensors; faces None: verts is a (F*3,3)
+    soup) or the (verts, faces, F) triple that _mesh_device / _clip return -> that triple on `dev`"""
+    if hasattr(mesh, "vertices"):
+        return _mesh_device(mesh, dev)
+    if not isinstance(mesh, (tuple, list)) or len(mesh) not in (2, 3):
+        raise ValueError("a mesh is a vis.Mesh, a (verts, faces) pair, or a (F*3,3) soup with faces=None")
+    v, f = mesh[0], mesh[1]
+    v = (v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if f is None:
+        if len(v) % 3:
+            raise ValueError("a triangle soup has 3 vertices per face")
+        return v, None, len(v) // 3
+    f = (f if torch.is_tensor(f) else torch.from_numpy(np.asarray(f))).to(device=dev).reshape(-1, 3)
+    if check and len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
+        raise ValueError("mesh faces index outside its vertices")
+    return v, f.to(torch.int32).contiguous(), len(f)
+
+
+def _point_mesh(q, tri, closest=False):
+    verts, faces, F = tri
+    if F < 1:
+        raise ValueError("point_mesh_distance of a mesh without faces")
+    if F >= 2 ** 31:
+        raise ValueError("point_mesh_distance: the face count must stay below 2^31")
+    nq, dev = len(q), q.device
+    ws = _C.workspace(_C.load().cnr_point_mesh_workspace_bytes(nq, F), dev, "cnr_point_mesh_dist")
+    dist = torch.empty(nq, device=dev, dtype=torch.float32)
+    face = torch.empty(nq, device=dev, dtype=torch.int32)
+    near = torch.empty(nq, 3, device=dev, dtype=torch.float32) if closest else None
+    _C.call("cnr_point_mesh_dist", q, nq, verts, faces, F, dist, face, near, ws)
+    return (dist, face, near) if closest else (dist, face)
+
+
+def point_mesh_distance(points, mesh, closest=False, check=True):
+    """The exact distance of every point to a triangle mesh (cnr_point_mesh_dist, csrc/point_mesh.hip): brute
+    force over all faces in fp32, difference first.  `mesh`: a vis.Mesh, a (verts, faces) pair, or a ((F*3,3) soup, None) pair.
+    -> (dist (n,) f32, face (n,) i32: the lowest index among the closest faces) and, with closest=True, the closest point
+    (n,3) f32; device tensors.  A face with coincident or collinear corners counts as the segment or point it covers.
+    check=True (the default) raises ValueError for non-finite coordinates and faces that index outside the vertices."""
+    q = _points(points)
+    tri = _triangles(mesh, q.device, check)
+    if check and not (bool(torch.isfinite(q).all()) and bool(torch.isfinite(tri[0]).all())):
+        raise ValueError("point_mesh_distance: non-finite coordinates")
+    return _point_mesh(q, tri, closest)
+
+
+def _unit_face_normals(tri):
+    """(F,3) f64 unit normals: the fp64 cross product of the fp32 corners, normalised; zero rows for faces without one"""
+    verts, faces, F = tri
+    c = verts.double().view(F, 3, 3) if faces is None else verts.double()[faces.long()]
+    n = torch.linalg.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
+    ln = n.norm(dim=1, keepdim=True)
+    return torch.where(ln > 0, n / torch.where(ln > 0, ln, torch.ones_like(ln)), torch.zeros_like(n))
+
+
+def _normal_consistency(n_src, n_dst):
+    """mean |n_src . n_dst| over the pairs where both normals exist -> (mean or nan, pairs)"""
+    ok = (n_src.abs().sum(1) > 0) & (n_dst.abs().sum(1) > 0)
+    pairs = int(ok.sum())
+    if pairs == 0:
+        return float("nan"), 0
+    return float(((n_src * n_dst).sum(1).abs() * ok).sum() / pairs), pairs
+
+
+def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, threshold=0.05):
+    """calc_3d_metric with every distance taken from a sample to the other MESH, not to samples of it: the same oriented box
+    and clip, the same three draws in the same order from numpy.random.default_rng(seed).  Accuracy: the clipped
+    reconstruction's samples to the ground-truth mesh; completion: the ground truth's samples to the whole reconstruction.
+    -> dict(accuracy_cm, completion_cm, completion_ratio (% below threshold), precision, recall (fractions below threshold),
+    fscore (their harmonic mean, 0 when both are 0), normal_consistency_acc, normal_consistency_comp, normal_consistency (their
+    mean), normal_pairs (acc, comp)), or None after printing "no mesh found".  Normal consistency is the mean |n_src . n_dst| of
+    the unit normal of the face a sample came from and that of its closest face (unsigned: ground-truth meshes are not
+    consistently oriented); pairs with a face without a normal on either side are left out and counted."""
+    mesh_gt = mesh_ref if mesh_gt is None else mesh_gt
+    transform, extents = oriented_bounds(mesh_ref)
+    dev = _device()
+    rec = _mesh_device(mesh_rec, dev)
+    rec_acc = _clip(rec, box_planes(transform, extents))
+    if rec_acc is None:
+        print("no mesh found")
+        return None
+    gt = _mesh_device(mesh_gt, dev)
+    rng = np.random.default_rng(seed)
+    rng.random((int(N), 3))                                 # calc_3d_metric's first draw (the whole reconstruction): not needed here
+    acc_pc, acc_src = _sample(rec_acc, N, rng, with_face=True)
+    gt_pc, gt_src = _sample(gt, N, rng, with_face=True)
+    d_acc, f_acc = _point_mesh(acc_pc, gt)
+    d_comp, f_comp = _point_mesh(gt_pc, rec)
+    s_acc, c_acc = (v.item() for v in _stats_device(d_acc, threshold))
+    s_comp, c_comp = (v.item() for v in _stats_device(d_comp, threshold))
+    precision, recall = c_acc / N, c_comp / N
+    n_rec_acc, n_gt, n_rec = _unit_face_normals(rec_acc), _unit_face_normals(gt), _unit_face_normals(rec)
+    nc_acc, p_acc = _normal_consistency(n_rec_acc[acc_src.long()], n_gt[f_acc.long()])
+    nc_comp, p_comp = _normal_consistency(n_gt[gt_src.long()], n_rec[f_comp.long()])
+    return dict(accuracy_cm=s_acc / N * 100, completion_cm=s_comp / N * 100, completion_ratio=c_comp / N * 100,
+                precision=precision, recall=recall,
+                fscore=2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0,
+                normal_consistency_acc=nc_acc, normal_consistency_comp=nc_comp, normal_consistency=(nc_acc + nc_comp) / 2,
+                normal_pairs=(p_acc, p_comp))
 
 
 # ---- oriented bounding box (host) --------------------------------------------------------------------------------------

@@ -811,6 +811,25 @@ int cnr_clip_box_count(const float* verts, const int* faces, int64_t F, const do
                        int64_t* count_out, void* stream);
 int cnr_clip_box_emit(const float* verts, const int* faces, int64_t F, const double* planes, void* workspace, float* tris,
                       void* stream);
+/* The face index of cnr_sample_surface's search alone: face_out[i] (i32) = the first f with cum[f] >= u[3 i] cum[F-1], the last
+ * face when there is none; u is the same (n,3) f64 array of draws (only u0 is read).  1 <= F < 2^31, n >= 0. */
+int cnr_sample_faces(const double* cum, int64_t F, const double* u, int64_t n, int* face_out, void* stream);
+/* Point-to-mesh distance, exact and brute force (tests/pointmesh_cpu.py restates it).  q (nq,3) f32; the
+ * triangle forms of cnr_face_area_scan (faces == NULL: a soup).  Per query: dist_out (f32) = sqrt of the minimum over all faces
+ * of the fp32 squared distance to the face's closest point, face_out (i32) = the lowest face index that attains it,
+ * closest_out (nq,3) f32 or NULL = q + r with r = closest - q of that face.  fp32 without contraction, difference first
+ * (ap = q - a, then dot products of ap and the edges): Ericson's seven regions with ab.bp = ab.ap - ab.ab etc., one division
+ * in the vertex and edge regions, r = -(n . ap) n with the face's unit normal in the interior; a face whose fp32 edge vectors
+ * are exactly parallel or zero stands for its longest edge.  Inputs must be finite.
+ * nq >= 1, 1 <= F < 2^31; workspace >= cnr_point_mesh_workspace_bytes(nq, F) = align256(64 F) + chunks * align256(8 nq), where
+ * chunks is the number of face chunks of the grid.  No atomics; bit-identical run to run. */
+int64_t cnr_point_mesh_workspace_bytes(int64_t nq, int64_t F);
+int cnr_point_mesh_dist(const float* q, int64_t nq, const float* verts, const int* faces, int64_t F, float* dist_out,
+                        int* face_out, float* closest_out, void* workspace, void* stream);
+/* One pass of cnr_point_mesh_dist alone, for timing: pass 1 = face records, 2 = partial minima, 3 = finish; same arguments
+ * and workspace, the passes in that order give cnr_point_mesh_dist's result. */
+int cnr_point_mesh_pass(const float* q, int64_t nq, const float* verts, const int* faces, int64_t F, float* dist_out,
+                        int* face_out, float* closest_out, void* workspace, int pass, void* stream);
 
 /* ---- Category registration on point clouds: src/category_registration.py, src/utils.py:189-366.  DESIGN.md §3.9.  The
  * contracts of the metric kernels hold: caller-allocated outputs, workspace queries, no float atomics, fixed reduction

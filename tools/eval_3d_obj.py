@@ -1,7 +1,7 @@
 """3-D metrics of the reconstructed meshes (metric/eval_3D_obj.py's command line and output files), on cnr_amd.metrics:
 
     python tools/eval_3d_obj.py --data_dir Datasets/Replica --log_dir logs/Replica [--log_dir_ref DIR] [--iteration 10000]
-                                [--clean keep_largest=1,...]
+                                [--clean keep_largest=1,...] [--surface]
 
 For every scene of the dataset (the last component of --data_dir: Replica or ScanNet) whose <log_dir>/<scene>/scene_mesh exists,
 every object mesh iteration_<it>_obj<id>.obj written by train.py is scored against its ground-truth mesh in
@@ -13,7 +13,10 @@ names.  A --log_dir_ref mesh it_<it>_obj<id>.obj, where present, sets the crop b
 Differences from the reference: only the meshes of --iteration are listed (the reference lists every .obj and then opens
 the --iteration one), scenes without a scene_mesh directory are skipped, and the samples are seeded (cnr_amd.metrics).
 --clean (default off; the reference scores the mesh as it is) drops the reconstruction's floaters first: the options of
-cnr_amd.meshops.clean_mesh as name=value pairs, e.g. keep_largest=1 or min_area_fraction=0.01,weld=0."""
+cnr_amd.meshops.clean_mesh as name=value pairs, e.g. keep_largest=1 or min_area_fraction=0.01,weld=0.
+--surface (default off) adds cnr_amd.metrics.calc_3d_metric_surface per object and in the mean: the same samples measured
+against the other MESH (accuracy, completion, completion ratio), precision / recall / F-score at 5 cm and normal
+consistency; written to <log_dir>/<scene>/eval_mesh/metrics_3D_obj_surface.json."""
 import argparse
 import csv
 import json
@@ -31,6 +34,8 @@ REPLICA_BG = [5, 12, 30, 31, 40, 60, 92, 93, 95, 97, 98, 79]
 REPLICA_SCENES = ["room_0", "room_1", "room_2", "office_0", "office_1", "office_2", "office_3", "office_4"]
 SCANNET_BG = [-1, 0, 1, 3, 16, 41, 232, 21, 161, 128, 21]
 SCANNET_SCENES = ["scene0013_02", "scene0059_00", "scene0066_00", "scene0281_00"]
+SURFACE_COLUMNS = ["accuracy_cm", "completion_cm", "completion_ratio", "precision", "recall", "fscore",
+                   "normal_consistency_acc", "normal_consistency_comp", "normal_consistency"]
 
 
 def concatenate(meshes):
@@ -90,9 +95,10 @@ def main(argv=None):
     ap.add_argument("--log_dir_ref", default="", type=str)
     ap.add_argument("--iteration", default=10000, type=int)
     ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
+    ap.add_argument("--surface", action="store_true", help="also score against the meshes themselves: point-to-mesh distances, F-score, normal consistency (default: off)")
     args = ap.parse_args(argv)
     from cnr_amd.meshops import clean_mesh, parse_clean_options
-    from cnr_amd.metrics import calc_3d_metric
+    from cnr_amd.metrics import calc_3d_metric, calc_3d_metric_surface
     clean = parse_clean_options(args.clean) if args.clean else None
     from cnr_amd.vis import load_mesh
 
@@ -116,6 +122,7 @@ def main(argv=None):
         output_path = os.path.join(exp_dir, "eval_mesh")
         os.makedirs(output_path, exist_ok=True)
         metrics_3D = [[] for _ in range(3)]
+        surface = {}
         for obj_id in get_obj_ids(mesh_dir, args.iteration):
             if obj_id == 0:
                 N = 200000
@@ -138,9 +145,19 @@ def main(argv=None):
             np.save(os.path.join(output_path, "metric_obj%d.npy" % obj_id), np.array(metrics))
             for k in range(3):
                 metrics_3D[k].append(metrics[k])
+            if args.surface:
+                row = calc_3d_metric_surface(mesh_rec, mesh_ref, N=N, mesh_gt=mesh_gt)
+                if row is not None:
+                    surface[obj_id] = row
+                    print("surface obj %d: " % obj_id + "  ".join("%s %.4f" % (k, row[k]) for k in SURFACE_COLUMNS))
         metrics_3D = np.array(metrics_3D)
         np.save(os.path.join(output_path, "metrics_3D_obj.npy"), metrics_3D)
         print("metrics 3D obj \n Acc | Comp | Comp Ratio 5cm \n", metrics_3D.mean(axis=1) if metrics_3D.size else metrics_3D)
+        if args.surface:
+            mean = {k: float(np.mean([r[k] for r in surface.values()])) for k in SURFACE_COLUMNS} if surface else {}
+            with open(os.path.join(output_path, "metrics_3D_obj_surface.json"), "w") as f:
+                json.dump(dict(objects={str(k): v for k, v in surface.items()}, mean=mean), f, indent=1)
+            print("surface mean: " + "  ".join("%s %.4f" % (k, mean[k]) for k in SURFACE_COLUMNS))
         print("-----------------------------------------")
         print("finish exp ", exp)
 
