@@ -7,7 +7,8 @@ the reference's per-object score: the oriented box of ``mesh_ref``, the reconstr
 samples, accuracy / completion in cm and the completion ratio at 5 cm in %; the samples stay on the device.
 ``point_mesh_distance`` is the exact distance from points to a triangle mesh with the closest face (``cnr_point_mesh_dist``,
 csrc/point_mesh.hip), and ``calc_3d_metric_surface`` the same score with every distance taken to the other
-mesh instead of to samples of it, plus precision / recall / F-score and normal consistency.
+mesh instead of to samples of it, plus precision / recall / F-score and normal consistency.  ``MeshIndex`` (opt-in,
+csrc/point_mesh_index.hip) answers the same queries bit for bit through a tile-box index that skips most of the mesh.
 
 Differences from the reference, all deliberate:
 * the ground truth is an argument (``mesh_gt``, default ``mesh_ref``); the reference reads a module-level ``mesh_gt`` and uses
@@ -23,7 +24,7 @@ from . import _C
 
 __all__ = ["accuracy", "completion", "accuracy_ratio", "completion_ratio", "chamfer", "nn_dist", "dist_stats",
            "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images",
-           "point_mesh_distance", "sample_surface_faces", "calc_3d_metric_surface"]
+           "point_mesh_distance", "sample_surface_faces", "calc_3d_metric_surface", "MeshIndex"]
 
 
 def _device():
@@ -176,13 +177,91 @@ def _point_mesh(q, tri, closest=False):
     return (dist, face, near) if closest else (dist, face)
 
 
-def point_mesh_distance(points, mesh, closest=False, check=True):
+class MeshIndex:
+    """The tile-box index of one mesh (csrc/point_mesh_index.hip, DESIGN.md §3.20 "The tile-box index"): the faces ordered along
+    a Morton curve, a bounding box per tile of `tile_faces` consecutive faces.  Built once (three launches and a sort), it
+    answers any number of ``query`` calls with cnr_point_mesh_dist's result bit for bit while evaluating only the tiles that can
+    hold a query group's minimum.  `mesh` and `check` as for point_mesh_distance.  Holds device tensors only."""
+
+    def __init__(self, mesh, check=True):
+        dev = mesh[0].device if isinstance(mesh, (tuple, list)) and torch.is_tensor(mesh[0]) and mesh[0].is_cuda else _device()
+        verts, faces, F = _triangles(mesh, dev, check)
+        if F < 1:
+            raise ValueError("MeshIndex of a mesh without faces")
+        if F >= 2 ** 31:
+            raise ValueError("MeshIndex: the face count must stay below 2^31")
+        if check and not bool(torch.isfinite(verts).all()):
+            raise ValueError("MeshIndex: non-finite coordinates")
+        self.device, self.faces, self.check = dev, F, check
+        self.tile_faces, self.group_queries = _index_params()
+        self.tiles = -(-F // self.tile_faces)
+        self.bbox = torch.cat([verts.amin(0), verts.amax(0)]).contiguous()
+        keys = torch.empty(F, device=dev, dtype=torch.int32)
+        _C.call("cnr_pm_index_keys", verts, faces, F, self.bbox, keys)
+        order = torch.sort(keys, stable=True).indices
+        self.index = _C.workspace(_C.load().cnr_pm_index_bytes(F), dev, "cnr_pm_index_build")
+        _C.call("cnr_pm_index_build", verts, faces, F, keys, order, self.index)
+
+    def _query(self, q, closest=False):
+        nq, dev = len(q), q.device
+        if dev != self.device:
+            raise ValueError("MeshIndex.query: the points are on another device than the index")
+        keys = torch.empty(nq, device=dev, dtype=torch.int32)
+        _C.call("cnr_pm_query_keys", q, nq, self.bbox, keys)
+        order = torch.sort(keys, stable=True).indices
+        ws = _C.workspace(_C.load().cnr_point_mesh_indexed_workspace_bytes(nq, self.faces), dev, "cnr_point_mesh_dist_indexed")
+        dist = torch.empty(nq, device=dev, dtype=torch.float32)
+        face = torch.empty(nq, device=dev, dtype=torch.int32)
+        near = torch.empty(nq, 3, device=dev, dtype=torch.float32) if closest else None
+        _C.call("cnr_point_mesh_dist_indexed", q, nq, keys, order, self.index, self.faces, dist, face, near, ws)
+        groups = -(-nq // self.group_queries)
+        return dist, face, near, ws[:4 * groups].view(torch.int32)
+
+    def query(self, points, closest=False, stats=False, check=None):
+        """-> (dist, face[, closest][, stats]) as point_mesh_distance; stats = dict(tiles, groups, tiles_visited, tile_faces,
+        group_queries): tiles_visited of groups * tiles tile evaluations were made (the one host read of the call).
+        check: whether non-finite points raise ValueError; None takes the index's own setting"""
+        q = _points(points, self.device)
+        if (self.check if check is None else check) and not bool(torch.isfinite(q).all()):
+            raise ValueError("point_mesh_distance: non-finite coordinates")
+        dist, face, near, visited = self._query(q, closest)
+        out = (dist, face, near) if closest else (dist, face)
+        if stats:
+            out += (dict(tiles=self.tiles, groups=len(visited), tiles_visited=int(visited.sum()), tile_faces=self.tile_faces,
+                         group_queries=self.group_queries),)
+        return out
+
+
+def _index_params():
+    import ctypes
+    tile, group = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _C.load().cnr_pm_index_params(ctypes.byref(tile), ctypes.byref(group))
+    if rc != 0:
+        raise _C.CnrError(f"cnr_pm_index_params failed with {rc}")
+    return tile.value, group.value
+
+
+def _distance(q, tri, index):
+    """(dist, face) of device points to the (verts, faces, F) triple: brute force, or through a throw-away MeshIndex"""
+    if not index:
+        return _point_mesh(q, tri)
+    return MeshIndex(tri, check=False)._query(q)[:2]
+
+
+def point_mesh_distance(points, mesh, closest=False, check=True, index=None):
     """The exact distance of every point to a triangle mesh (cnr_point_mesh_dist, csrc/point_mesh.hip): brute
     force over all faces in fp32, difference first.  `mesh`: a vis.Mesh, a (verts, faces) pair, or a ((F*3,3) soup, None) pair.
     -> (dist (n,) f32, face (n,) i32: the lowest index among the closest faces) and, with closest=True, the closest point
     (n,3) f32; device tensors.  A face with coincident or collinear corners counts as the segment or point it covers.
-    check=True (the default) raises ValueError for non-finite coordinates and faces that index outside the vertices."""
+    check=True (the default) raises ValueError for non-finite coordinates and faces that index outside the vertices.
+    index: None or False is the brute force; True builds a throw-away MeshIndex of `mesh` and queries it; a MeshIndex is used
+    as given (`mesh` is then not read, and `check` applies to the points alone: the mesh was checked, or not, when the index
+    was built).  The result is the same bit for bit."""
+    if isinstance(index, MeshIndex):
+        return index.query(points, closest=closest, check=check)
     q = _points(points)
+    if index:
+        return MeshIndex(_triangles(mesh, q.device, check), check=check).query(q, closest=closest)
     tri = _triangles(mesh, q.device, check)
     if check and not (bool(torch.isfinite(q).all()) and bool(torch.isfinite(tri[0]).all())):
         raise ValueError("point_mesh_distance: non-finite coordinates")
@@ -207,7 +286,7 @@ def _normal_consistency(n_src, n_dst):
     return float(((n_src * n_dst).sum(1).abs() * ok).sum() / pairs), pairs
 
 
-def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, threshold=0.05):
+def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, threshold=0.05, index=False):
     """calc_3d_metric with every distance taken from a sample to the other MESH, not to samples of it: the same oriented box
     and clip, the same three draws in the same order from numpy.random.default_rng(seed).  Accuracy: the clipped
     reconstruction's samples to the ground-truth mesh; completion: the ground truth's samples to the whole reconstruction.
@@ -215,7 +294,8 @@ def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, t
     fscore (their harmonic mean, 0 when both are 0), normal_consistency_acc, normal_consistency_comp, normal_consistency (their
     mean), normal_pairs (acc, comp)), or None after printing "no mesh found".  Normal consistency is the mean |n_src . n_dst| of
     the unit normal of the face a sample came from and that of its closest face (unsigned: ground-truth meshes are not
-    consistently oriented); pairs with a face without a normal on either side are left out and counted."""
+    consistently oriented); pairs with a face without a normal on either side are left out and counted.  index=True takes the two
+    distances through a MeshIndex of each mesh (the same numbers, fewer pairs)."""
     mesh_gt = mesh_ref if mesh_gt is None else mesh_gt
     transform, extents = oriented_bounds(mesh_ref)
     dev = _device()
@@ -229,8 +309,8 @@ def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, t
     rng.random((int(N), 3))                                 # calc_3d_metric's first draw (the whole reconstruction): not needed here
     acc_pc, acc_src = _sample(rec_acc, N, rng, with_face=True)
     gt_pc, gt_src = _sample(gt, N, rng, with_face=True)
-    d_acc, f_acc = _point_mesh(acc_pc, gt)
-    d_comp, f_comp = _point_mesh(gt_pc, rec)
+    d_acc, f_acc = _distance(acc_pc, gt, index)
+    d_comp, f_comp = _distance(gt_pc, rec, index)
     s_acc, c_acc = (v.item() for v in _stats_device(d_acc, threshold))
     s_comp, c_comp = (v.item() for v in _stats_device(d_comp, threshold))
     precision, recall = c_acc / N, c_comp / N

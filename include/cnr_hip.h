@@ -830,6 +830,36 @@ int cnr_point_mesh_dist(const float* q, int64_t nq, const float* verts, const in
  * and workspace, the passes in that order give cnr_point_mesh_dist's result. */
 int cnr_point_mesh_pass(const float* q, int64_t nq, const float* verts, const int* faces, int64_t F, float* dist_out,
                         int* face_out, float* closest_out, void* workspace, int pass, void* stream);
+/* The same result, bit for bit, through a tile-box index that culls (DESIGN.md §3.20 "The tile-box index";
+ * tests/pointmesh_index_cpu.py restates it).  Built once per mesh, used for any number of query sets; opt-in.
+ * cnr_pm_index_params: *tile_faces = TILE, the faces per tile, *group_queries = GROUP, the queries per culling group.
+ * cnr_pm_index_keys: keys_out[f] (i32) = the 30-bit Morton code (10 bits per axis, x the lowest bit of each triple) of the centre
+ * 0.5 (min + max) of face f's box, quantised over bbox (6 f32 on the device: lo xyz, hi xyz): per axis 0 when hi - lo is not
+ * a positive finite fp32 number, else min(1023, (int)(((clamp(x, lo, hi) - lo) / (hi - lo)) * 1024)), fp32 without contraction.  cnr_pm_query_keys: the same
+ * of the queries themselves.  The caller sorts (stably) and passes the permutations as int64 `order` / `qorder`
+ * (torch.sort's indices): position -> original index.
+ * cnr_pm_index_build(verts, faces | NULL, F, keys, order, index_out): index_out (cnr_pm_index_bytes(F) = align256(64 F) +
+ * align256(32 tiles) bytes, tiles = ceil(F / TILE)) receives cnr_point_mesh_dist's face records in key order, the face's original
+ * index bit-cast into the sixteenth float, then one row of 8 floats per tile of TILE consecutive faces: box lo xyz, Lmax, box hi
+ * xyz, the tile's first key (bit-cast); lo / hi are the exact min / max of the faces' corners, Lmax = sqrtf of the largest fp32
+ * squared edge (ab, ac, bc: differences first) of the tile.
+ * cnr_point_mesh_dist_indexed: q, dist_out, face_out (ORIGINAL face indices), closest_out | NULL as for cnr_point_mesh_dist, all
+ * at the queries' original positions; qkeys from cnr_pm_query_keys with the index's bbox, qorder their stable order.  A group of
+ * GROUP consecutive queries in key order evaluates a seed tile, then every tile t for which NOT
+ * lb - 32 2^-24 (lb + Lmax_t) > sqrt(M): lb = sqrtf of the squared per-axis gaps max(lo_t - hi_g, lo_g - hi_t, 0) between the
+ * tile's box and the group's, M the largest current minimum of the group's queries, re-read after every tile.  Among equal
+ * minima the lowest original index wins.  workspace >= cnr_point_mesh_indexed_workspace_bytes(nq, F) = align256(4 groups),
+ * groups = ceil(nq / GROUP); after the call its first `groups` i32 hold the number of tiles each group evaluated.
+ * nq >= 1, 1 <= F < 2^31.  No atomics, one launch, bit-identical run to run. */
+int cnr_pm_index_params(int* tile_faces, int* group_queries);
+int64_t cnr_pm_index_bytes(int64_t F);
+int cnr_pm_index_keys(const float* verts, const int* faces, int64_t F, const float* bbox, int* keys_out, void* stream);
+int cnr_pm_index_build(const float* verts, const int* faces, int64_t F, const int* keys, const int64_t* order, void* index_out,
+                       void* stream);
+int cnr_pm_query_keys(const float* q, int64_t nq, const float* bbox, int* keys_out, void* stream);
+int64_t cnr_point_mesh_indexed_workspace_bytes(int64_t nq, int64_t F);
+int cnr_point_mesh_dist_indexed(const float* q, int64_t nq, const int* qkeys, const int64_t* qorder, const void* index, int64_t F,
+                                float* dist_out, int* face_out, float* closest_out, void* workspace, void* stream);
 
 /* ---- Category registration on point clouds: src/category_registration.py, src/utils.py:189-366.  DESIGN.md §3.9.  The
  * contracts of the metric kernels hold: caller-allocated outputs, workspace queries, no float atomics, fixed reduction

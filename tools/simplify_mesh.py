@@ -2,7 +2,7 @@
 §3.19), and print the report.
 
     python tools/simplify_mesh.py in.{obj,ply} out.obj (--cell C | --faces N) [--placement quadric|mean|representative] [--tau T]
-                                  [--deviation [N]]
+                                  [--deviation [N] [--index]]
 
 --cell C clusters the vertices on a grid of pitch C; --faces N bisects the pitch until at most N faces are left.  An output
 vertex is placed by its cluster's quadric (the default), at the cluster mean, or at the cluster's lowest input vertex; it takes
@@ -50,13 +50,15 @@ def main(argv=None):
     ap.add_argument("--tau", type=float, default=1e-3)
     ap.add_argument("--deviation", type=int, nargs="?", const=100000, default=None, metavar="N",
                     help="measure the output against the input with N samples per side (default: off)")
+    ap.add_argument("--index", action="store_true",
+                    help="with --deviation: distances through a tile-box index of each mesh; the same numbers (default: off)")
     a = ap.parse_args(argv)
     import cnr_amd as cnr
     mesh = load(cnr, a.src)
     out, report = cnr.meshops.simplify_mesh(mesh, cell=a.cell, target_faces=a.faces, placement=a.placement, tau=a.tau)
     print_report(report)
     if a.deviation is not None and len(out.faces) and len(mesh.faces):
-        print_deviation(cnr.meshops.deviation_mesh(mesh, out, samples=a.deviation))
+        print_deviation(cnr.meshops.deviation_mesh(mesh, out, samples=a.deviation, index=a.index))
     out.export(a.dst)
 
 
