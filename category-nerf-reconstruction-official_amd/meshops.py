@@ -4,13 +4,14 @@ watertightness), compaction of a face selection, and ``clean_mesh``: dropping th
 it smaller (csrc/mesh_simplify.hip): ``simplify``, uniform vertex clustering with quadric placement, and
 ``vertex_normals``.
 
-Device tensors in and out (``clean_mesh`` and ``mesh_to_device`` take a host ``vis.Mesh``).  The sorts are
+Device tensors in and out (``clean_mesh``, ``simplify_mesh`` and ``deviation_mesh`` take a host ``vis.Mesh``).  The sorts are
 ``torch.sort(stable=True)``, every other step is a HIP kernel; there is no CPU path.  A union/find loop that runs out of its bound
 raises CnrError, an out-of-range face index raises ValueError."""
 import numpy as np
 import torch
 
 from . import _C
+from .devmesh import DeviceMesh, check_faces, device_mesh, require_finite
 from .vis import Mesh
 
 CONNECTIVITY = ("edge", "vertex")
@@ -25,32 +26,6 @@ def _raise_if_set(err, what):
         raise ValueError(f"{what}: an index lies outside its range")
     if e & 1:
         raise _C.CnrError(f"{what}: a union/find loop ran out of its bound (the label array is corrupt)")
-
-
-def _faces_i32(faces, n_vertices, what):
-    """(F,3) device faces -> contiguous int32, range-checked on the device against [0, n_vertices)"""
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: faces must have the shape (F,3), not {tuple(faces.shape)}")
-    if not faces.is_cuda:
-        raise _C.CnrError(f"{what}: cnr kernels take device tensors only; there is no CPU path")
-    n_vertices = int(n_vertices)
-    F = faces.shape[0]
-    if n_vertices < 0 or n_vertices > 2 ** 31 - 1 or 3 * F > 2 ** 31 - 1:
-        raise ValueError(f"{what}: V and 3 F must stay below 2^31")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{what}: faces must be int32 or int64")
-    if faces.dtype == torch.int64 and F:
-        lo, hi = (int(v) for v in torch.stack([faces.min(), faces.max()]).cpu())
-        if lo < 0 or hi >= n_vertices:
-            raise ValueError(f"{what}: an index lies outside its range")
-    f = faces.to(torch.int32).contiguous()
-    if F:
-        if n_vertices < 1:
-            raise ValueError(f"{what}: an index lies outside its range")
-        err = torch.zeros(1, device=f.device, dtype=torch.int32)
-        _C.call("cnr_mesh_check_faces", f, F, n_vertices, err)
-        _raise_if_set(err, what)
-    return f
 
 
 def _flatten(labels, n, err):
@@ -137,7 +112,7 @@ def components(faces, n_vertices, verts=None, connectivity="edge", timer=None):
     if connectivity not in CONNECTIVITY:
         raise ValueError(f"connectivity must be one of {CONNECTIVITY}, not {connectivity!r}")
     V = int(n_vertices)
-    f = _faces_i32(faces, V, "components")
+    f = check_faces(faces, V, "components")
     F, dev = f.shape[0], f.device
     mark = timer or (lambda name: None)
     if verts is not None:
@@ -157,29 +132,22 @@ def components(faces, n_vertices, verts=None, connectivity="edge", timer=None):
     mark("sort_edges")
     face_comp = torch.empty(F, device=dev, dtype=torch.int32)
     vert_comp = torch.empty(V, device=dev, dtype=torch.int32)
-    if connectivity == "edge":
-        labels = torch.empty(F, device=dev, dtype=torch.int32)
-        _C.call("cnr_mesh_labels_init", labels, F)
-        _C.call("cnr_mesh_union_edges", skeys, perm, F, labels, err)
-        mark("union")
-        _flatten(labels, F, err)
-        mark("flatten")
-        roots = _roots(labels, None, F)
-        _raise_if_set(err, "components")
-        _C.call("cnr_mesh_assign", labels, None, F, roots, len(roots), face_comp, err)
-        _C.call("cnr_mesh_cross_component", f, F, V, 0, face_comp, vert_comp)
-    else:
-        labels = torch.empty(V, device=dev, dtype=torch.int32)
-        used = torch.zeros(V, device=dev, dtype=torch.uint8)
-        _C.call("cnr_mesh_labels_init", labels, V)
+    by_vertex = connectivity == "vertex"                 # the sets are of vertices (those a face uses), else of faces
+    n = V if by_vertex else F
+    labels = torch.empty(n, device=dev, dtype=torch.int32)
+    used = torch.zeros(V, device=dev, dtype=torch.uint8) if by_vertex else None
+    _C.call("cnr_mesh_labels_init", labels, n)
+    if by_vertex:
         _C.call("cnr_mesh_union_faces", f, F, V, labels, used, err)
-        mark("union")
-        _flatten(labels, V, err)
-        mark("flatten")
-        roots = _roots(labels, used, V)
-        _raise_if_set(err, "components")
-        _C.call("cnr_mesh_assign", labels, used, V, roots, len(roots), vert_comp, err)
-        _C.call("cnr_mesh_cross_component", f, F, V, 1, face_comp, vert_comp)
+    else:
+        _C.call("cnr_mesh_union_edges", skeys, perm, F, labels, err)
+    mark("union")
+    _flatten(labels, n, err)
+    mark("flatten")
+    roots = _roots(labels, used, n)
+    _raise_if_set(err, "components")
+    _C.call("cnr_mesh_assign", labels, used, n, roots, len(roots), vert_comp if by_vertex else face_comp, err)
+    _C.call("cnr_mesh_cross_component", f, F, V, 1 if by_vertex else 0, face_comp, vert_comp)
     C = len(roots)
     mark("roots_assign")
     edge_counts = torch.zeros(C, 3, device=dev, dtype=torch.int32)
@@ -215,7 +183,7 @@ def compact(faces, n_vertices, keep_face, reindex=True):
     raster.cull_mesh) -> (faces (F',3) i32, vertex_map (V,) i32 with -1 = dropped, kept_vertices (V',) i32 ascending); gather
     attributes with ``attr.index_select(0, kept_vertices.long())``.  reindex=False keeps the indices -> faces only."""
     V = int(n_vertices)
-    f = _faces_i32(faces, V, "compact")
+    f = check_faces(faces, V, "compact")
     F, dev = f.shape[0], f.device
     if tuple(keep_face.shape) != (F,):
         raise ValueError(f"keep_face must have the shape ({F},), not {tuple(keep_face.shape)}")
@@ -239,6 +207,44 @@ def compact(faces, n_vertices, keep_face, reindex=True):
     return out, vmap, kept
 
 
+def _lex_order(rows):
+    """the permutation (n,) i64 that puts the rows (n,3) i32 in (column 0, 1, 2) order: three stable sorts, the last column first"""
+    perm = torch.arange(len(rows), device=rows.device)
+    for axis in (2, 1, 0):
+        perm = perm[torch.sort(rows[perm, axis], stable=True)[1]]
+    return perm.contiguous()
+
+
+def _number_runs(rep, err):
+    """cnr_weld_runs' representatives (n,) i32 -> (roots (C,) i32 ascending, the number 0 .. C-1 of every element's run (n,) i32)"""
+    n = len(rep)
+    roots = _roots(rep, None, n)
+    number = torch.empty(n, device=rep.device, dtype=torch.int32)
+    _C.call("cnr_mesh_assign", rep, None, n, roots, len(roots), number, err)
+    return roots, number
+
+
+def _clusters(verts, cell, err, strict=False, mark=lambda name: None):
+    """the cells of cnr_voxel_keys numbered by their lowest vertex (weld's cell > 0, simplify's clusters) -> (min (3,) f32, keys
+    (V,) i64, roots (C,) i32, cluster (V,) i32).  strict is simplify's contract: cnr_simplify_check_keys flags a non-finite
+    vertex or more than 2^21 cells on an axis, and a set flag raises before the runs are counted; weld takes such rows as they come."""
+    V, dev = len(verts), verts.device
+    mn = torch.empty(3, device=dev, dtype=torch.float32)
+    _C.call("cnr_points_min", verts, V, _C.workspace(_C.load().cnr_points_min_workspace_bytes(V), dev, "cnr_points_min"), mn)
+    keys = torch.empty(V, device=dev, dtype=torch.int64)
+    _C.call("cnr_voxel_keys", verts, V, mn, float(cell), keys)
+    if strict:
+        _C.call("cnr_simplify_check_keys", keys, V, err)
+    mark("keys")
+    skeys, perm = torch.sort(keys, stable=True)
+    mark("sort_keys")
+    rep = torch.empty(V, device=dev, dtype=torch.int32)
+    _C.call("cnr_weld_runs", None, skeys, perm, V, rep, err)
+    if strict:
+        _raise_if_set(err, "simplify")
+    return (mn, keys) + _number_runs(rep, err)
+
+
 def weld(verts, faces=None, cell=0.0, drop_degenerate=True):
     """Merge coincident vertices.  verts (V,3) f32 with faces (F,3), or faces=None and verts (F,3,3): a triangle soup.
     cell == 0: rows weld when their three fp32 values are bit-equal after -0 -> +0; a row holding a NaN welds with nothing.
@@ -260,29 +266,18 @@ def weld(verts, faces=None, cell=0.0, drop_degenerate=True):
         raise ValueError("cell must be >= 0")
     verts = verts.float().contiguous()
     V, dev = len(verts), verts.device
-    f = _faces_i32(faces, V, "weld")
+    f = check_faces(faces, V, "weld")
     if V == 0:
         z = torch.zeros(0, device=dev, dtype=torch.int32)
         return z, f, z.clone()
     err = torch.zeros(1, device=dev, dtype=torch.int32)
-    rep = torch.empty(V, device=dev, dtype=torch.int32)
     if cell == 0:
         rows = (verts + 0.0).view(torch.int32).contiguous()              # -0 + +0 = +0; every other value as it is
-        perm = torch.arange(V, device=dev)
-        for axis in (2, 1, 0):                                           # three stable sorts: rows in (x, y, z) order
-            perm = perm[torch.sort(rows[perm, axis], stable=True)[1]]
-        _C.call("cnr_weld_runs", rows, None, perm.contiguous(), V, rep, err)
+        rep = torch.empty(V, device=dev, dtype=torch.int32)
+        _C.call("cnr_weld_runs", rows, None, _lex_order(rows), V, rep, err)
+        kept, remap = _number_runs(rep, err)
     else:
-        lib = _C.load()
-        mn = torch.empty(3, device=dev, dtype=torch.float32)
-        _C.call("cnr_points_min", verts, V, _C.workspace(lib.cnr_points_min_workspace_bytes(V), dev, "cnr_points_min"), mn)
-        keys = torch.empty(V, device=dev, dtype=torch.int64)
-        _C.call("cnr_voxel_keys", verts, V, mn, float(cell), keys)
-        skeys, perm = torch.sort(keys, stable=True)
-        _C.call("cnr_weld_runs", None, skeys, perm, V, rep, err)
-    kept = _roots(rep, None, V)
-    remap = torch.empty(V, device=dev, dtype=torch.int32)
-    _C.call("cnr_mesh_assign", rep, None, V, kept, len(kept), remap, err)
+        _, _, kept, remap = _clusters(verts, cell, err)
     _raise_if_set(err, "weld")
     F = len(f)
     if F == 0:
@@ -296,14 +291,6 @@ def weld(verts, faces=None, cell=0.0, drop_degenerate=True):
 
 
 _weld = weld                        # (clean_mesh's option of the same name shadows the function)
-
-
-# ---- vis.Mesh on the device ------------------------------------------------------------------------------------------------
-def mesh_to_device(mesh, device=None):
-    """vis.Mesh -> dict(verts (V,3) f32, faces (F,3) i32) on the device (positions rounded to fp32 once)"""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return dict(verts=torch.from_numpy(np.ascontiguousarray(mesh.vertices, np.float32)).to(dev),
-                faces=torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int32)).to(dev))
 
 
 def select_components(table, keep_largest=None, min_faces=0, min_area=0.0, min_diag=0.0, min_area_fraction=0.0, largest_by="area"):
@@ -348,7 +335,7 @@ def clean_device(verts, faces, weld=None, connectivity="edge", keep_largest=None
     into the INPUT vertices, report).  weld: None (no welding), 0.0 (exact) or a cell size."""
     V = len(verts)
     verts = verts.float().contiguous()
-    f = _faces_i32(faces, V, "clean_mesh")
+    f = check_faces(faces, V, "clean_mesh")
     kept0 = None
     if weld is not None:
         kept0, f, _ = _weld(verts, f, cell=float(weld))
@@ -376,19 +363,14 @@ def clean_mesh(mesh, weld=None, connectivity="edge", keep_largest=None, min_face
     component id, and the result is never empty unless the input is.  Positions, normals and colours of the kept vertices are
     the input's (float64 positions stay float64: the device sees their fp32 roundings, the output gathers the originals).
     report: dict(components=MeshComponents, kept=(n,) bool, n_components, n_kept, faces_in/out, vertices_in/out)."""
-    d = mesh_to_device(mesh, device)
-    out_f, kept, report = clean_device(d["verts"], d["faces"], weld, connectivity, keep_largest, min_faces, min_area, min_diag,
+    d = device_mesh(mesh, device, what="clean_mesh")
+    out_f, kept, report = clean_device(d.verts, d.faces, weld, connectivity, keep_largest, min_faces, min_area, min_diag,
                                        min_area_fraction, largest_by)
-    idx = kept.cpu().numpy().astype(np.int64)
-    out = Mesh(mesh.vertices[idx], out_f.cpu().numpy().astype(np.int64).reshape(-1, 3), mesh.vertex_normals[idx])
-    out.visual.vertex_colors = mesh.visual.vertex_colors[idx]
-    return out, report
+    return mesh.subset(kept.cpu().numpy().astype(np.int64), out_f.cpu().numpy().astype(np.int64).reshape(-1, 3)), report
 
 
-def parse_clean_options(text):
-    """the tools' ``--clean`` string, e.g. "keep_largest=1,min_faces=20,weld=0" -> the dict of clean_mesh options"""
-    kinds = dict(weld=float, connectivity=str, keep_largest=int, min_faces=int, min_area=float, min_diag=float,
-                 min_area_fraction=float, largest_by=str)
+def _parse_options(text, kinds, flag):
+    """a tool's "name=value,name=value" string -> the dict of options, each value read by kinds[name]"""
     out = {}
     for item in (text or "").split(","):
         if not item.strip():
@@ -396,9 +378,15 @@ def parse_clean_options(text):
         k, _, v = item.partition("=")
         k = k.strip()
         if k not in kinds or not v.strip():
-            raise ValueError(f"--clean: cannot read {item!r}; options are {sorted(kinds)} as name=value")
+            raise ValueError(f"{flag}: cannot read {item!r}; options are {sorted(kinds)} as name=value")
         out[k] = kinds[k](v.strip())
     return out
+
+
+def parse_clean_options(text):
+    """the tools' ``--clean`` string, e.g. "keep_largest=1,min_faces=20,weld=0" -> the dict of clean_mesh options"""
+    return _parse_options(text, dict(weld=float, connectivity=str, keep_largest=int, min_faces=int, min_area=float, min_diag=float,
+                                     min_area_fraction=float, largest_by=str), "--clean")
 
 
 # ---- simplification: uniform vertex clustering with quadric placement (csrc/mesh_simplify.hip, DESIGN.md section 3.19) -------
@@ -426,27 +414,6 @@ def _fixed_order_total(values, err):
     return _segment_sum(values.view(len(values), 1), None, 1, torch.zeros(len(values), device=dev, dtype=torch.int32), 1, err).view(-1)
 
 
-def _clusters(verts, cell, err, mark=lambda name: None):
-    """the cells of cnr_voxel_keys as weld(cell > 0) numbers them -> (min (3,) f32, keys (V,) i64, roots (C,) i32, cluster (V,) i32)"""
-    V, dev = len(verts), verts.device
-    lib = _C.load()
-    mn = torch.empty(3, device=dev, dtype=torch.float32)
-    _C.call("cnr_points_min", verts, V, _C.workspace(lib.cnr_points_min_workspace_bytes(V), dev, "cnr_points_min"), mn)
-    keys = torch.empty(V, device=dev, dtype=torch.int64)
-    _C.call("cnr_voxel_keys", verts, V, mn, float(cell), keys)
-    _C.call("cnr_simplify_check_keys", keys, V, err)
-    mark("keys")
-    skeys, perm = torch.sort(keys, stable=True)
-    mark("sort_keys")
-    rep = torch.empty(V, device=dev, dtype=torch.int32)
-    _C.call("cnr_weld_runs", None, skeys, perm, V, rep, err)
-    _raise_if_set(err, "simplify")
-    roots = _roots(rep, None, V)
-    cluster = torch.empty(V, device=dev, dtype=torch.int32)
-    _C.call("cnr_mesh_assign", rep, None, V, roots, len(roots), cluster, err)
-    return mn, keys, roots, cluster
-
-
 def _cluster_faces(f, cluster, C, err, mark=lambda name: None):
     """-> (corner clusters (F,3) i32 of EVERY input face, the faces with three distinct clusters (F1,3) i32 in their old order,
     keep (F1,) u8 = 1 for the lowest face of every run of equal rows).  Rows: the face rotated so that its smallest index leads;
@@ -463,12 +430,10 @@ def _cluster_faces(f, cluster, C, err, mark=lambda name: None):
     rows = torch.empty(F1, 3, device=dev, dtype=torch.int32)
     _C.call("cnr_simplify_face_rows", f1, F1, rows)
     mark("face_rows")
-    perm = torch.arange(F1, device=dev)
-    for axis in (2, 1, 0):                                               # three stable sorts, as weld's exact mode
-        perm = perm[torch.sort(rows[perm, axis], stable=True)[1]]
+    perm = _lex_order(rows)                                              # as weld's exact mode
     mark("sort_rows")
     rep = torch.empty(F1, device=dev, dtype=torch.int32)
-    _C.call("cnr_weld_runs", rows, None, perm.contiguous(), F1, rep, err)
+    _C.call("cnr_weld_runs", rows, None, perm, F1, rep, err)
     keep1 = (rep == torch.arange(F1, device=dev, dtype=torch.int32)).to(torch.uint8)
     mark("duplicates")
     return corners, f1, keep1
@@ -477,7 +442,7 @@ def _cluster_faces(f, cluster, C, err, mark=lambda name: None):
 def _faces_out(verts, f, cell):
     """the integer stages only: the number of faces simplify(cell) returns"""
     err = torch.zeros(1, device=verts.device, dtype=torch.int32)
-    _, _, roots, cluster = _clusters(verts, cell, err)
+    _, _, roots, cluster = _clusters(verts, cell, err, strict=True)
     _, _, keep1 = _cluster_faces(f, cluster, len(roots), err)
     _raise_if_set(err, "simplify")
     return int(keep1.sum().item()) if len(keep1) else 0
@@ -547,7 +512,7 @@ def simplify(verts, faces, cell=None, target_faces=None, placement="quadric", ta
         raise ValueError(f"verts must have the shape (V,3), not {tuple(verts.shape)}")
     verts = verts.float().contiguous()
     V, dev = len(verts), verts.device
-    f = _faces_i32(faces, V, "simplify")
+    f = check_faces(faces, V, "simplify")
     F = len(f)
     if V > 0x7f800000:
         raise ValueError("simplify: V must stay below 2^31 - 2^23 (the face rows are compared as cnr_weld_runs compares rows)")
@@ -566,7 +531,7 @@ def simplify(verts, faces, cell=None, target_faces=None, placement="quadric", ta
         report["cell"] = cell
     cell = float(cell)
     err = torch.zeros(1, device=dev, dtype=torch.int32)
-    mn, keys, roots, cluster = _clusters(verts, cell, err, mark)
+    mn, keys, roots, cluster = _clusters(verts, cell, err, strict=True, mark=mark)
     C = len(roots)
     mark("cluster_ids")
     corners, f1, keep1 = _cluster_faces(f, cluster, C, err, mark)
@@ -623,7 +588,7 @@ def vertex_normals(verts, faces):
         raise ValueError(f"verts must have the shape (V,3), not {tuple(verts.shape)}")
     verts = verts.float().contiguous()
     V, dev = len(verts), verts.device
-    f = _faces_i32(faces, V, "vertex_normals")
+    f = check_faces(faces, V, "vertex_normals")
     F = len(f)
     out = torch.zeros(V, 3, device=dev, dtype=torch.float32)
     if F == 0 or V == 0:
@@ -642,8 +607,8 @@ def simplify_mesh(mesh, cell=None, target_faces=None, placement="quadric", tau=1
     """``simplify`` of a ``vis.Mesh`` -> (mesh, report).  Positions are the device result as float64; the colour of an output
     vertex is its cluster representative's (the lowest input index, as weld: no averaging); normals are ``vertex_normals`` of
     the output."""
-    d = mesh_to_device(mesh, device)
-    v, f, _, report = simplify(d["verts"], d["faces"], cell=cell, target_faces=target_faces, placement=placement, tau=tau)
+    d = device_mesh(mesh, device, what="simplify_mesh")
+    v, f, _, report = simplify(d.verts, d.faces, cell=cell, target_faces=target_faces, placement=placement, tau=tau)
     out = Mesh(v.cpu().numpy().astype(np.float64), f.cpu().numpy().astype(np.int64).reshape(-1, 3),
                vertex_normals(v, f).cpu().numpy().astype(np.float64))
     out.visual.vertex_colors = mesh.visual.vertex_colors[report["representatives"].cpu().numpy().astype(np.int64)]
@@ -651,21 +616,22 @@ def simplify_mesh(mesh, cell=None, target_faces=None, placement="quadric", tau=1
 
 
 # ---- deviation between two meshes (csrc/point_mesh.hip) ---------------------------------------------------
-def _one_sided(verts, f, other, samples, rng, include_vertices, index=False):
+def _one_sided(mesh, other, samples, rng, include_vertices, index=False):
+    """the distances from one DeviceMesh's vertices and samples to the surface of the other -> dict(mean, rms, max, n)"""
     from . import metrics
     parts = []
     if include_vertices:
-        parts.append(verts.index_select(0, torch.unique(f.view(-1).long())))
+        parts.append(mesh.verts.index_select(0, torch.unique(mesh.faces.view(-1).long())))
     if samples > 0:
-        parts.append(metrics._sample((verts, f, len(f)), samples, rng))
+        parts.append(metrics.sample_surface(mesh, samples, rng))
     if not parts:
         raise ValueError("deviation: nothing to measure (samples=0 and include_vertices=False)")
     q = torch.cat(parts).contiguous()
-    d, _ = metrics._distance(q, other, index)
+    d, _ = metrics.point_mesh_distance(q, other, check=False, index=bool(index))
     n = len(d)
-    total, _ = metrics._stats_device(d, float("inf"))
+    total, _ = metrics.dist_stats(d)
     d64 = d.double()
-    return dict(mean=float(total.item()) / n, rms=float(torch.sqrt((d64 * d64).sum() / n)), max=float(d.max()), n=n)
+    return dict(mean=total / n, rms=float(torch.sqrt((d64 * d64).sum() / n)), max=float(d.max()), n=n)
 
 
 def deviation(verts_a, faces_a, verts_b, faces_b, samples=100000, seed=0, include_vertices=True, index=False):
@@ -680,36 +646,24 @@ def deviation(verts_a, faces_a, verts_b, faces_b, samples=100000, seed=0, includ
         if v.dim() != 2 or v.shape[1] != 3:
             raise ValueError(f"verts must have the shape (V,3), not {tuple(v.shape)}")
         v = v.float().contiguous()
-        if not bool(torch.isfinite(v).all()):
-            raise ValueError("deviation: non-finite coordinates")
-        f = _faces_i32(f, len(v), "deviation")
-        if len(f) == 0:
+        require_finite(v, "deviation")
+        m = DeviceMesh(v, check_faces(f, len(v), "deviation"))
+        if m.n_faces == 0:
             raise ValueError(f"deviation: mesh {name} has no faces")
-        sides.append((v, f, len(f)))
+        sides.append(m)
     rng = np.random.default_rng(seed)
     a, b = sides
-    a_to_b = _one_sided(a[0], a[1], b, int(samples), rng, include_vertices, index)
-    b_to_a = _one_sided(b[0], b[1], a, int(samples), rng, include_vertices, index)
-    return dict(a_to_b=a_to_b, b_to_a=b_to_a, hausdorff=max(a_to_b["max"], b_to_a["max"]), diag=_bbox_diag(a[0]))
+    a_to_b = _one_sided(a, b, int(samples), rng, include_vertices, index)
+    b_to_a = _one_sided(b, a, int(samples), rng, include_vertices, index)
+    return dict(a_to_b=a_to_b, b_to_a=b_to_a, hausdorff=max(a_to_b["max"], b_to_a["max"]), diag=_bbox_diag(a.verts))
 
 
 def deviation_mesh(mesh_a, mesh_b, samples=100000, seed=0, include_vertices=True, device=None, index=False):
     """``deviation`` of two ``vis.Mesh``"""
-    a, b = mesh_to_device(mesh_a, device), mesh_to_device(mesh_b, device)
-    return deviation(a["verts"], a["faces"], b["verts"], b["faces"], samples=samples, seed=seed, include_vertices=include_vertices,
-                     index=index)
+    a, b = (device_mesh(m, device, what="deviation_mesh") for m in (mesh_a, mesh_b))
+    return deviation(a.verts, a.faces, b.verts, b.faces, samples=samples, seed=seed, include_vertices=include_vertices, index=index)
 
 
 def parse_simplify_options(text):
     """the tools' ``--simplify`` string, e.g. "cell=0.02,placement=mean" or "target_faces=20000" -> the dict of simplify options"""
-    kinds = dict(cell=float, target_faces=int, placement=str, tau=float)
-    out = {}
-    for item in (text or "").split(","):
-        if not item.strip():
-            continue
-        k, _, v = item.partition("=")
-        k = k.strip()
-        if k not in kinds or not v.strip():
-            raise ValueError(f"--simplify: cannot read {item!r}; options are {sorted(kinds)} as name=value")
-        out[k] = kinds[k](v.strip())
-    return out
+    return _parse_options(text, dict(cell=float, target_faces=int, placement=str, tau=float), "--simplify")

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _C
+from .devmesh import DeviceMesh, device_mesh, require_finite
 
 __all__ = ["accuracy", "completion", "accuracy_ratio", "completion_ratio", "chamfer", "nn_dist", "dist_stats",
            "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images",
@@ -97,17 +98,9 @@ def chamfer(gt_points, rec_points):
     return (completion(gt_points, rec_points) + accuracy(gt_points, rec_points)) / 2.0
 
 
-# ---- triangles on the device: (verts f32 (V,3), faces i32 (F,3) or None for a soup (F,3,3) in verts, F) ------------------
-def _mesh_device(mesh, dev):
-    f = np.asarray(mesh.faces).reshape(-1, 3)
-    v = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.vertices, np.float64).reshape(-1, 3), np.float32)).to(dev)
-    if len(f) and (f.min() < 0 or f.max() >= len(v)):
-        raise ValueError("mesh faces index outside its vertices")
-    return v, torch.from_numpy(np.ascontiguousarray(f, np.int32)).to(dev), len(f)
-
-
+# ---- triangles on the device: a devmesh.DeviceMesh (faces None: a soup, three rows of verts per face) ---------------------
 def _area_scan(tri):
-    verts, faces, F = tri
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     ws = _C.workspace(_C.load().cnr_face_area_workspace_bytes(F), verts.device, "cnr_face_area_scan")
     area = torch.empty(F, device=verts.device, dtype=torch.float64)
     cum = torch.empty(F, device=verts.device, dtype=torch.float64)
@@ -116,7 +109,7 @@ def _area_scan(tri):
 
 
 def _sample(tri, count, rng, with_face=False):
-    verts, faces, F = tri
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     if F < 1:
         raise ValueError("cannot sample a mesh without faces")
     _, cum = _area_scan(tri)
@@ -131,43 +124,23 @@ def _sample(tri, count, rng, with_face=False):
 
 
 def sample_surface(mesh, count, seed=0):
-    """trimesh.sample.sample_surface's algorithm on the GPU: `count` area-weighted points of `mesh` (a vis.Mesh or anything with
-    vertices / faces) from numpy.random.default_rng(seed).random((count, 3)) -> (count, 3) f32 device tensor"""
-    return _sample(_mesh_device(mesh, _device()), count, np.random.default_rng(seed))
+    """trimesh.sample.sample_surface's algorithm on the GPU: `count` area-weighted points of `mesh` (a vis.Mesh or anything
+    devmesh.device_mesh takes) from numpy.random.default_rng(seed).random((count, 3)) -> (count, 3) f32 device tensor.
+    seed may be a numpy Generator, which default_rng hands back as it is: the draw then advances the caller's stream."""
+    return _sample(device_mesh(mesh), count, np.random.default_rng(seed))
 
 
 def sample_surface_faces(mesh, count, seed=0):
     """sample_surface with the face every sample was drawn from -> (points (count,3) f32, face (count,) i32) device tensors;
     the same draws, so points is bit-equal to sample_surface(mesh, count, seed)"""
-    return _sample(_triangles(mesh, _device()), count, np.random.default_rng(seed), with_face=True)
+    return _sample(device_mesh(mesh), count, np.random.default_rng(seed), with_face=True)
 
 
 # ---- point to mesh -----------------------------------------------------------------------------------------------------
-def _triangles(mesh, dev, check=True):
-    """a vis.Mesh (anything with vertices / faces), a (verts, faces) pair (arrays or tensors; faces None: verts is a (F*3,3)
-    soup) or the (verts, faces, F) triple that _mesh_device / _clip return -> that triple on `dev`"""
-    if hasattr(mesh, "vertices"):
-        return _mesh_device(mesh, dev)
-    if not isinstance(mesh, (tuple, list)) or len(mesh) not in (2, 3):
-        raise ValueError("a mesh is a vis.Mesh, a (verts, faces) pair, or a (F*3,3) soup with faces=None")
-    v, f = mesh[0], mesh[1]
-    v = (v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    if f is None:
-        if len(v) % 3:
-            raise ValueError("a triangle soup has 3 vertices per face")
-        return v, None, len(v) // 3
-    f = (f if torch.is_tensor(f) else torch.from_numpy(np.asarray(f))).to(device=dev).reshape(-1, 3)
-    if check and len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
-        raise ValueError("mesh faces index outside its vertices")
-    return v, f.to(torch.int32).contiguous(), len(f)
-
-
 def _point_mesh(q, tri, closest=False):
-    verts, faces, F = tri
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     if F < 1:
         raise ValueError("point_mesh_distance of a mesh without faces")
-    if F >= 2 ** 31:
-        raise ValueError("point_mesh_distance: the face count must stay below 2^31")
     nq, dev = len(q), q.device
     ws = _C.workspace(_C.load().cnr_point_mesh_workspace_bytes(nq, F), dev, "cnr_point_mesh_dist")
     dist = torch.empty(nq, device=dev, dtype=torch.float32)
@@ -184,14 +157,12 @@ class MeshIndex:
     hold a query group's minimum.  `mesh` and `check` as for point_mesh_distance.  Holds device tensors only."""
 
     def __init__(self, mesh, check=True):
-        dev = mesh[0].device if isinstance(mesh, (tuple, list)) and torch.is_tensor(mesh[0]) and mesh[0].is_cuda else _device()
-        verts, faces, F = _triangles(mesh, dev, check)
+        tri = device_mesh(mesh, check=check, what="MeshIndex")
+        verts, faces, F, dev = tri.verts, tri.faces, tri.n_faces, tri.device
         if F < 1:
             raise ValueError("MeshIndex of a mesh without faces")
-        if F >= 2 ** 31:
-            raise ValueError("MeshIndex: the face count must stay below 2^31")
-        if check and not bool(torch.isfinite(verts).all()):
-            raise ValueError("MeshIndex: non-finite coordinates")
+        if check:
+            require_finite(verts, "MeshIndex")
         self.device, self.faces, self.check = dev, F, check
         self.tile_faces, self.group_queries = _index_params()
         self.tiles = -(-F // self.tile_faces)
@@ -222,8 +193,8 @@ class MeshIndex:
         group_queries): tiles_visited of groups * tiles tile evaluations were made (the one host read of the call).
         check: whether non-finite points raise ValueError; None takes the index's own setting"""
         q = _points(points, self.device)
-        if (self.check if check is None else check) and not bool(torch.isfinite(q).all()):
-            raise ValueError("point_mesh_distance: non-finite coordinates")
+        if self.check if check is None else check:
+            require_finite(q, "point_mesh_distance")
         dist, face, near, visited = self._query(q, closest)
         out = (dist, face, near) if closest else (dist, face)
         if stats:
@@ -242,7 +213,7 @@ def _index_params():
 
 
 def _distance(q, tri, index):
-    """(dist, face) of device points to the (verts, faces, F) triple: brute force, or through a throw-away MeshIndex"""
+    """(dist, face) of device points to a DeviceMesh: brute force, or through a throw-away MeshIndex"""
     if not index:
         return _point_mesh(q, tri)
     return MeshIndex(tri, check=False)._query(q)[:2]
@@ -260,17 +231,18 @@ def point_mesh_distance(points, mesh, closest=False, check=True, index=None):
     if isinstance(index, MeshIndex):
         return index.query(points, closest=closest, check=check)
     q = _points(points)
+    tri = device_mesh(mesh, q.device, check=check, what="point_mesh_distance")
     if index:
-        return MeshIndex(_triangles(mesh, q.device, check), check=check).query(q, closest=closest)
-    tri = _triangles(mesh, q.device, check)
-    if check and not (bool(torch.isfinite(q).all()) and bool(torch.isfinite(tri[0]).all())):
-        raise ValueError("point_mesh_distance: non-finite coordinates")
+        return MeshIndex(tri, check=check).query(q, closest=closest)
+    if check:
+        require_finite(q, "point_mesh_distance")
+        require_finite(tri.verts, "point_mesh_distance")
     return _point_mesh(q, tri, closest)
 
 
 def _unit_face_normals(tri):
     """(F,3) f64 unit normals: the fp64 cross product of the fp32 corners, normalised; zero rows for faces without one"""
-    verts, faces, F = tri
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     c = verts.double().view(F, 3, 3) if faces is None else verts.double()[faces.long()]
     n = torch.linalg.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])
     ln = n.norm(dim=1, keepdim=True)
@@ -286,6 +258,20 @@ def _normal_consistency(n_src, n_dst):
     return float(((n_src * n_dst).sum(1).abs() * ok).sum() / pairs), pairs
 
 
+def _metric_inputs(mesh_rec, mesh_ref, mesh_gt, seed):
+    """The opening calc_3d_metric and calc_3d_metric_surface share -> (rec, rec clipped to mesh_ref's oriented box, gt, rng),
+    or None after printing "no mesh found".  The draws from rng, in this order: the whole reconstruction, its clip, the ground
+    truth -- (N,3) uniforms each."""
+    transform, extents = oriented_bounds(mesh_ref)
+    dev = _device()
+    rec = device_mesh(mesh_rec, dev)
+    rec_acc = _clip(rec, box_planes(transform, extents))
+    if rec_acc is None:
+        print("no mesh found")
+        return None
+    return rec, rec_acc, device_mesh(mesh_ref if mesh_gt is None else mesh_gt, dev), np.random.default_rng(seed)
+
+
 def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, threshold=0.05, index=False):
     """calc_3d_metric with every distance taken from a sample to the other MESH, not to samples of it: the same oriented box
     and clip, the same three draws in the same order from numpy.random.default_rng(seed).  Accuracy: the clipped
@@ -296,16 +282,10 @@ def calc_3d_metric_surface(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0, t
     the unit normal of the face a sample came from and that of its closest face (unsigned: ground-truth meshes are not
     consistently oriented); pairs with a face without a normal on either side are left out and counted.  index=True takes the two
     distances through a MeshIndex of each mesh (the same numbers, fewer pairs)."""
-    mesh_gt = mesh_ref if mesh_gt is None else mesh_gt
-    transform, extents = oriented_bounds(mesh_ref)
-    dev = _device()
-    rec = _mesh_device(mesh_rec, dev)
-    rec_acc = _clip(rec, box_planes(transform, extents))
-    if rec_acc is None:
-        print("no mesh found")
+    inputs = _metric_inputs(mesh_rec, mesh_ref, mesh_gt, seed)
+    if inputs is None:
         return None
-    gt = _mesh_device(mesh_gt, dev)
-    rng = np.random.default_rng(seed)
+    rec, rec_acc, gt, rng = inputs
     rng.random((int(N), 3))                                 # calc_3d_metric's first draw (the whole reconstruction): not needed here
     acc_pc, acc_src = _sample(rec_acc, N, rng, with_face=True)
     gt_pc, gt_src = _sample(gt, N, rng, with_face=True)
@@ -433,7 +413,8 @@ def box_planes(transform, extents):
 
 
 def _clip(tri, planes):
-    verts, faces, F = tri
+    """the part of a DeviceMesh inside the box of `planes` -> a soup DeviceMesh, or None when nothing is inside"""
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     if F < 1:
         return None
     dev = verts.device
@@ -446,7 +427,7 @@ def _clip(tri, planes):
         return None
     tris = torch.empty(T, 3, 3, device=dev, dtype=torch.float32)
     _C.call("cnr_clip_box_emit", verts, faces, F, pl, ws, tris)
-    return tris.view(T * 3, 3), None, T
+    return DeviceMesh(tris.view(T * 3, 3), None)
 
 
 def slice_box(mesh, transform, extents):
@@ -454,10 +435,10 @@ def slice_box(mesh, transform, extents):
     the mesh inside the box, crossing triangles split, no cap -> vis.Mesh (an unindexed soup: 3 vertices per triangle; no
     vertices when nothing is inside)"""
     from .vis import Mesh
-    out = _clip(_mesh_device(mesh, _device()), box_planes(transform, extents))
+    out = _clip(device_mesh(mesh), box_planes(transform, extents))
     if out is None:
         return Mesh(np.zeros((0, 3)), np.zeros((0, 3), np.int64))
-    v = out[0].double().cpu().numpy()
+    v = out.verts.double().cpu().numpy()
     return Mesh(v, np.arange(len(v), dtype=np.int64).reshape(-1, 3))
 
 
@@ -465,18 +446,13 @@ def calc_3d_metric(mesh_rec, mesh_ref, N=200000, mesh_gt=None, seed=0):
     """metric/eval_3D_obj.py:10-39: [[accuracy cm], [completion cm], [completion ratio at 5 cm, %]], or None (after printing
     "no mesh found") when nothing of mesh_rec lies in mesh_ref's oriented box.  Accuracy uses the reconstruction clipped to
     that box, completion and its ratio the whole reconstruction."""
-    mesh_gt = mesh_ref if mesh_gt is None else mesh_gt
-    transform, extents = oriented_bounds(mesh_ref)
-    dev = _device()
-    rec = _mesh_device(mesh_rec, dev)
-    rec_acc = _clip(rec, box_planes(transform, extents))
-    if rec_acc is None:
-        print("no mesh found")
+    inputs = _metric_inputs(mesh_rec, mesh_ref, mesh_gt, seed)
+    if inputs is None:
         return None
-    rng = np.random.default_rng(seed)
+    rec, rec_acc, gt, rng = inputs
     rec_pc = _sample(rec, N, rng)
     rec_pc_for_acc = _sample(rec_acc, N, rng)
-    gt_pc = _sample(_mesh_device(mesh_gt, dev), N, rng)
+    gt_pc = _sample(gt, N, rng)
     s_acc, _ = _stats_device(nn_dist(rec_pc_for_acc, gt_pc), float("inf"))
     s_comp, c_comp = _stats_device(nn_dist(gt_pc, rec_pc), 0.05)
     acc, comp, cnt = (v.item() for v in (s_acc, s_comp, c_comp))

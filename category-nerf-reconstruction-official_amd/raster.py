@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _C
+from .devmesh import DeviceMesh, device_mesh
 from .vis import Mesh
 
 # the workspace of one launch (80 bytes of coefficients and 8 of tile box per view and face, 16 per view and tile) stays
@@ -21,65 +22,42 @@ WORKSPACE_BOUND = 1 << 30
 MAX_PAIRS = 2 ** 31 - 1
 
 
-def _host(a, dtype):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(a), dtype)
-
-
-def _mesh_arrays(m):
-    """-> verts (Nv,3) f32, faces (F,3) i64, colors (Nv,3) f32 in [0,1], normals (Nv,3) f32"""
-    if isinstance(m, Mesh):
-        v, f = _host(m.vertices, np.float32), _host(m.faces, np.int64)
-        c = _host(m.visual.vertex_colors[:, :3], np.float32) / np.float32(255)
-        n = _host(m.vertex_normals, np.float32)
-    else:
-        if not 2 <= len(m) <= 4:
-            raise ValueError("a mesh is a vis.Mesh or a tuple (verts, faces[, colors, normals])")
-        v, f = _host(m[0], np.float32), _host(m[1], np.int64)
-        c = _host(m[2], np.float32) if len(m) > 2 and m[2] is not None else np.full_like(v, 102.0 / 255.0)
-        n = _host(m[3], np.float32) if len(m) > 3 and m[3] is not None else np.zeros_like(v)
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-        raise ValueError("verts must be (Nv,3) and faces (F,3), not {} and {}".format(v.shape, f.shape))
-    if c.shape != v.shape or n.shape != v.shape:
-        raise ValueError("colors and normals must have the shape of verts {}, not {} and {}".format(v.shape, c.shape, n.shape))
-    if f.size and (f.min() < 0 or f.max() >= len(v)):
-        raise ValueError("faces index vertices {} .. {} of a mesh with {} vertices".format(f.min(), f.max(), len(v)))
-    return v, f, c, n
-
-
 class MeshScene:
-    """``MeshScene(meshes, labels=None)``: the meshes of a list (each a ``vis.Mesh`` or a tuple ``(verts, faces[, colors,
-    normals])`` of arrays or tensors, colours in [0,1]; a single mesh may come without the list) concatenated on the device:
-    ``verts (Nv,3) f32``, ``faces (F,3) i32``, ``colors (Nv,3) f32`` (``visual.vertex_colors / 255``), ``normals (Nv,3) f32``,
-    ``face_label (F,) i32`` = the instance id of the face's mesh (``labels``, default its place in the list) and ``face_mesh
-    (F,) i32`` = that place.  ``face_offsets`` (host) delimits every mesh's faces.  Face indices are checked here, on the
-    host, before anything is uploaded: the kernels trust them."""
+    """``MeshScene(meshes, labels=None)``: the meshes of a list (each a ``vis.Mesh``, a ``devmesh.DeviceMesh`` or a tuple
+    ``(verts, faces[, colors, normals])`` of arrays or tensors, colours in [0,1]; a single mesh may come without the list)
+    concatenated on the device: ``verts (Nv,3) f32``, ``faces (F,3) i32``, ``colors (Nv,3) f32`` (``visual.vertex_colors /
+    255``), ``normals (Nv,3) f32``, ``face_label (F,) i32`` = the instance id of the face's mesh (``labels``, default its place
+    in the list) and ``face_mesh (F,) i32`` = that place.  ``face_offsets`` (host) delimits every mesh's faces.  Face indices
+    are checked by ``devmesh.device_mesh`` where they are held (host arrays before they are uploaded, device tensors on the
+    device): the kernels trust them."""
 
     def __init__(self, meshes, labels=None, device=None):
-        if isinstance(meshes, Mesh) or (isinstance(meshes, tuple) and len(meshes) and not isinstance(meshes[0], (Mesh, tuple, list))):
+        if isinstance(meshes, (Mesh, DeviceMesh)) or (isinstance(meshes, tuple) and len(meshes)
+                                                      and not isinstance(meshes[0], (Mesh, DeviceMesh, tuple, list))):
             meshes = [meshes]
-        parts = [_mesh_arrays(m) for m in meshes]
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        parts = [device_mesh(m, dev, attributes=True) for m in meshes]
         if not parts:
             raise ValueError("no mesh")
+        if any(p.faces is None for p in parts):
+            raise ValueError("a scene takes meshes with faces, not a triangle soup")
         labels = list(range(len(parts))) if labels is None else [int(x) for x in labels]
         if len(labels) != len(parts):
             raise ValueError("{} labels for {} meshes".format(len(labels), len(parts)))
-        voff = np.cumsum([0] + [len(p[0]) for p in parts])
-        self.face_offsets = [int(x) for x in np.cumsum([0] + [len(p[1]) for p in parts])]
+        voff = np.cumsum([0] + [len(p.verts) for p in parts])
+        self.face_offsets = [int(x) for x in np.cumsum([0] + [p.n_faces for p in parts])]
         if voff[-1] >= 2 ** 31 or self.face_offsets[-1] >= 2 ** 31:
             raise ValueError("more than 2^31 - 1 vertices or faces")
         if self.face_offsets[-1] == 0:
             raise ValueError("the meshes have no face")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         self.device = dev
-        self.verts = up(np.concatenate([p[0] for p in parts]))
-        self.faces = up(np.concatenate([p[1] + o for p, o in zip(parts, voff)]).astype(np.int32))
-        self.colors = up(np.concatenate([p[2] for p in parts]))
-        self.normals = up(np.concatenate([p[3] for p in parts]))
-        self.face_label = up(np.concatenate([np.full(len(p[1]), l, np.int32) for p, l in zip(parts, labels)]))
-        self.face_mesh = up(np.concatenate([np.full(len(p[1]), i, np.int32) for i, p in enumerate(parts)]))
+        self.verts = torch.cat([p.verts for p in parts])
+        self.faces = torch.cat([p.faces + int(o) for p, o in zip(parts, voff)])
+        self.colors = torch.cat([p.colors for p in parts])
+        self.normals = torch.cat([p.normals for p in parts])
+        self.face_label = up(np.concatenate([np.full(p.n_faces, l, np.int32) for p, l in zip(parts, labels)]))
+        self.face_mesh = up(np.concatenate([np.full(p.n_faces, i, np.int32) for i, p in enumerate(parts)]))
         self.n_faces, self.n_meshes = self.face_offsets[-1], len(parts)
 
 
@@ -249,9 +227,7 @@ def cull_mesh(mesh, keep_faces):
     used = np.unique(faces)
     remap = np.full(len(mesh.vertices), -1, np.int64)
     remap[used] = np.arange(len(used))
-    out = Mesh(mesh.vertices[used], remap[faces].reshape(-1, 3), mesh.vertex_normals[used])
-    out.visual.vertex_colors = mesh.visual.vertex_colors[used]
-    return out
+    return mesh.subset(used, remap[faces].reshape(-1, 3))
 
 
 def observed_area(scene, seen):

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import embedding, model, render_rays, vis
+from . import embedding, meshops, model, render_rays, vis
 
 
 class Trainer:
@@ -108,23 +108,14 @@ class Trainer:
         if boxed:
             mesh.apply_transform(transform_np)
         if clean is not None:
-            from . import meshops
-            pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
-            tri = torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int32)).to(self.device)
-            kept_faces, kept, self.last_clean_report = meshops.clean_device(pts, tri, **dict(clean))
-            idx = kept.cpu().numpy().astype(np.int64)
-            mesh = vis.Mesh(mesh.vertices[idx], kept_faces.cpu().numpy().astype(np.int64).reshape(-1, 3), mesh.vertex_normals[idx])
+            mesh, self.last_clean_report = meshops.clean_mesh(mesh, device=self.device, **dict(clean))
         if simplify is not None:
-            from . import meshops
-            pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
-            tri = torch.from_numpy(np.ascontiguousarray(mesh.faces, np.int32)).to(self.device)
-            pts, tri, _, self.last_simplify_report = meshops.simplify(pts, tri, **dict(simplify))
-            if len(tri) == 0:
+            # the lattice normals do not exist at moved vertices: "grid" takes the output faces' own (simplify_mesh's), "field"
+            # replaces them below
+            mesh, self.last_simplify_report = meshops.simplify_mesh(mesh, device=self.device, **dict(simplify))
+            if len(mesh.faces) == 0:
                 print("simplification left no face")
                 return None
-            # the lattice normals do not exist at moved vertices: "grid" takes the output faces' own, "field" replaces them below
-            mesh = vis.Mesh(pts.cpu().numpy().astype(np.float64), tri.cpu().numpy().astype(np.int64).reshape(-1, 3),
-                            meshops.vertex_normals(pts, tri).cpu().numpy().astype(np.float64))
         vertices_pts = torch.from_numpy(np.array(mesh.vertices)).float().to(self.device)
         ret = self.eval_points(vertices_pts) if self.cls_id == 0 else self.eval_points(vertices_pts, inst_id=inst_id)
         if ret is None:
@@ -202,15 +193,8 @@ class Trainer:
         with torch.no_grad():
             if self.cls_id != 0:
                 from . import ops
-                fc = self.fc_occ_map
-                obj_idx = torch.tensor(self.inst_id_to_index[inst_id], device=self.device)
-                shape_code, texture_code = self.shape_codes(obj_idx), self.texture_codes(obj_idx)
-                trunk = torch.cat([t.reshape(1, -1) for n, _, _ in ops.TRUNK_LAYERS
-                                   for t in (fc._linear(n).weight, fc._linear(n).bias)], dim=1).contiguous()
+                trunk, B, brows = self._codenerf_rows(inst_id)
                 packed = ops.pack_weights(trunk)
-                zlat = fc.latent_rows(shape_code.view(1, 1, -1), texture_code.view(1, 1, -1))       # (1,4,32)
-                brows = ops.bias_rows(trunk, zlat[None]).reshape(1, 4, 32).contiguous()
-                B = self.pe.B_layer.weight.reshape(1, 21, 3).contiguous()
                 row = torch.zeros(1, 1, device=points.device, dtype=torch.int32)
                 for k in range(n_chunks):
                     pts = points[k * chunk_size:(k + 1) * chunk_size].float().contiguous()

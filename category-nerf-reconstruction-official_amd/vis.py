@@ -50,6 +50,12 @@ class Mesh:
         ln = np.linalg.norm(n, axis=1, keepdims=True)
         return np.where(ln > 0, n / np.where(ln > 0, ln, 1.0), 0.0)
 
+    def subset(self, vertex_index, faces):
+        """a new Mesh of the vertices ``vertex_index`` in that order, with their normals and colours, and the given faces"""
+        out = Mesh(self.vertices[vertex_index], faces, self.vertex_normals[vertex_index])
+        out.visual.vertex_colors = self.visual.vertex_colors[vertex_index]
+        return out
+
     def apply_translation(self, translation):
         self.vertices = self.vertices + np.asarray(translation, np.float64).reshape(1, 3)
         return self

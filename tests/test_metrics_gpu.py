@@ -115,17 +115,22 @@ def _mc_mesh(D=48, r0=0.85, centre=(0.0, 0.0, 0.0), scale=1.0):
     return m
 
 
+def _device_mesh(mesh, dev):
+    from cnr_amd.devmesh import device_mesh
+    return device_mesh(mesh, dev)
+
+
 def _soup_device(verts32, dev):
     """a soup (F*3,3) f32 both ways the kernels read triangles: unindexed (faces = NULL) and indexed by 0, 1, 2, ..."""
     v = torch.from_numpy(np.ascontiguousarray(verts32, np.float32)).to(dev)
     F = len(v) // 3
-    return (v, None, F), (v, torch.arange(3 * F, device=dev, dtype=torch.int32).view(F, 3), F)
+    return _device_mesh((v, None), dev), _device_mesh((v, torch.arange(3 * F, device=dev, dtype=torch.int32).view(F, 3)), dev)
 
 
 def _sample_points(tri, cum, u, dev):
     from cnr_amd import _C
     out = torch.empty(len(u), 3, device=dev)
-    _C.call("cnr_sample_surface", tri[0], tri[1], tri[2], cum, torch.from_numpy(u).to(dev), len(u), out)
+    _C.call("cnr_sample_surface", tri.verts, tri.faces, tri.n_faces, cum, torch.from_numpy(u).to(dev), len(u), out)
     return out
 
 
@@ -134,7 +139,7 @@ def test_sample_surface_matches_the_restatement(mt, dev):
     v, f, us = K.sampling_random_inputs()
     meshes = [_mc_mesh(33), _mc_mesh(64, 0.6, (0.2, 0.0, 0.1), 3.0), vis.Mesh(v, f)]
     for m, u in zip(meshes, us):
-        tri = mt._mesh_device(m, dev)
+        tri = _device_mesh(m, dev)
         area, cum = mt._area_scan(tri)
         T = K.triangles(m.vertices, m.faces)
         np.testing.assert_allclose(area.cpu().numpy(), K.face_areas(T), rtol=1e-12, atol=0)
@@ -182,21 +187,21 @@ def test_clip_matches_the_restatement(mt, dev):
     for m, c, e in cases:
         T, ext = _random_box(rng, c, e)
         planes = mt.box_planes(T, ext)
-        tri = mt._mesh_device(m, dev)
+        tri = _device_mesh(m, dev)
         out = mt._clip(tri, planes)
         ref = K.clip_box(K.triangles(m.vertices, m.faces), planes)
         assert out is not None and len(ref)
-        got = out[0].double().cpu().numpy().reshape(-1, 3, 3)
+        got = out.verts.double().cpu().numpy().reshape(-1, 3, 3)
         assert K.face_areas(got).sum() == pytest.approx(K.face_areas(ref).sum(), rel=1e-5)
         loc = got.reshape(-1, 3) @ T[:3, :3].T + T[:3, 3]
         assert (np.abs(loc) <= ext / 2 + 1e-5).all()
         again = mt._clip(tri, planes)
-        assert torch.equal(out[0], again[0])
+        assert torch.equal(out.verts, again.verts)
         # the soup itself can be clipped and sampled again
         assert mt._sample(out, 1000, np.random.default_rng(1)).shape == (1000, 3)
     # outside everything: nothing
     T, ext = _random_box(rng, (10.0, 0.0, 0.0), (0.5, 0.5, 0.5))
-    assert mt._clip(mt._mesh_device(_mc_mesh(33), dev), mt.box_planes(T, ext)) is None
+    assert mt._clip(_device_mesh(_mc_mesh(33), dev), mt.box_planes(T, ext)) is None
 
 
 def _check_clip_rows(mt, tri_dev, tri64, planes, general=True):
@@ -209,8 +214,8 @@ def _check_clip_rows(mt, tri_dev, tri64, planes, general=True):
     if general:
         assert closest >= 1e-9 * np.abs(tri64).max(), closest    # the kept / dropped decisions cannot differ (test_metrics_host.py)
     out = mt._clip(tri_dev, planes)
-    assert out is not None and len(ref) and out[2] == len(ref) and out[0].shape == (3 * len(ref), 3)
-    got = out[0].cpu().numpy().reshape(-1, 3, 3)
+    assert out is not None and len(ref) and out.n_faces == len(ref) and out.verts.shape == (3 * len(ref), 3)
+    got = out.verts.cpu().numpy().reshape(-1, 3, 3)
     ref32 = ref.astype(np.float32)
     err = np.abs(got.astype(np.float64) - ref32.astype(np.float64))
     bad = np.flatnonzero((err > np.spacing(np.abs(ref32)).astype(np.float64)).any((1, 2)))
@@ -221,7 +226,7 @@ def _check_clip_rows(mt, tri_dev, tri64, planes, general=True):
           % (len(tri64), len(ref), differ, got.size, closest))
     assert differ * 10 ** 4 <= got.size, (differ, got.size)
     again = mt._clip(tri_dev, planes)
-    assert torch.equal(out[0], again[0])
+    assert torch.equal(out.verts, again.verts)
     return out
 
 
@@ -229,16 +234,16 @@ def _check_clip_rows(mt, tri_dev, tri64, planes, general=True):
 def test_clip_rows_of_random_soups(mt, dev, F, verts, T, ext):
     planes = mt.box_planes(T, ext)
     soup, indexed = _soup_device(verts, dev)
-    assert soup[2] == F
+    assert soup.n_faces == F
     out = _check_clip_rows(mt, soup, K.triangles(verts), planes)
-    assert torch.equal(out[0], _check_clip_rows(mt, indexed, K.triangles(verts), planes)[0])
+    assert torch.equal(out.verts, _check_clip_rows(mt, indexed, K.triangles(verts), planes).verts)
 
 
 def test_clip_rows_of_an_indexed_sphere(mt, dev):
     m = _mc_mesh(48)
     T, ext = K.random_box(np.random.default_rng(22), (0.1, 0.0, -0.2), (1.2, 0.9, 1.0))
-    out = _check_clip_rows(mt, mt._mesh_device(m, dev), K.triangles(m.vertices, m.faces), mt.box_planes(T, ext))
-    assert 1000 < out[2] < len(m.faces)
+    out = _check_clip_rows(mt, _device_mesh(m, dev), K.triangles(m.vertices, m.faces), mt.box_planes(T, ext))
+    assert 1000 < out.n_faces < len(m.faces)
 
 
 def test_clip_rows_for_every_fan_count(mt, dev):
@@ -259,8 +264,8 @@ def test_clip_rows_with_corners_exactly_on_the_planes(mt, dev):
     planes = mt.box_planes(*K.UNIT_BOX)
     for tri in _soup_device(verts, dev):
         out = _check_clip_rows(mt, tri, K.triangles(verts), planes, general=False)
-        assert out[2] == counts.sum()
-        got = out[0].double().cpu().numpy().reshape(-1, 3, 3)
+        assert out.n_faces == counts.sum()
+        got = out.verts.double().cpu().numpy().reshape(-1, 3, 3)
         assert np.array_equal(got, K.clip_box(K.triangles(verts), planes))       # exact input: exact output
         first = np.cumsum(counts) - counts
         assert (got[first[3]] == verts[9]).all()                                 # touched by one corner: that corner three times
@@ -276,9 +281,9 @@ def test_clip_scan_with_more_than_1024_blocks(mt, dev):
     assert F * k > 262144 and (F * k) % 256 != 0 and -(-F * k // 256) > 1024
     for tri in _soup_device(np.tile(verts, (k, 1)), dev):
         big = mt._clip(tri, planes)
-        assert big[2] == k * small[2]
-        assert torch.equal(big[0].view(k, -1), small[0].view(1, -1).expand(k, -1))
-        assert torch.equal(big[0], mt._clip(tri, planes)[0])
+        assert big.n_faces == k * small.n_faces
+        assert torch.equal(big.verts.view(k, -1), small.verts.view(1, -1).expand(k, -1))
+        assert torch.equal(big.verts, mt._clip(tri, planes).verts)
 
 
 def test_face_area_scan_with_more_than_1024_blocks(mt, dev):

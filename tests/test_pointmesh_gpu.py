@@ -192,7 +192,7 @@ def test_sample_faces_equals_the_restatement(mt, dev):
     verts, u_edge = MC.dyadic_sampling_fixture()
     rng = np.random.default_rng(2)
     for soup_verts, u_fixed in ((verts, u_edge), (MC.dyadic_single_face()[0], MC.dyadic_single_face()[1])):
-        tri = mt._triangles((soup_verts, None), dev)
+        tri = cnr_amd.devmesh.device_mesh((soup_verts, None), dev)
         _, cum = mt._area_scan(tri)
         cum_h = cum.cpu().numpy()
         for n in (1, 255, 256, 257, 5000):
@@ -200,7 +200,7 @@ def test_sample_faces_equals_the_restatement(mt, dev):
             if n == 1:
                 u = u_fixed[-1:]                                                                 # a draw beside a prefix boundary
             face = torch.empty(n, device=dev, dtype=torch.int32)
-            _C.call("cnr_sample_faces", cum, tri[2], torch.from_numpy(np.ascontiguousarray(u)).to(dev), n, face)
+            _C.call("cnr_sample_faces", cum, tri.n_faces, torch.from_numpy(np.ascontiguousarray(u)).to(dev), n, face)
             assert np.array_equal(face.cpu().numpy(), P.sample_faces(cum_h, u[:, 0]))
             assert np.array_equal(face.cpu().numpy(), MC.sample_surface(MC.triangles(soup_verts), u)[0])
 
@@ -280,7 +280,8 @@ def test_calc_3d_metric_surface_on_concentric_cubes(mt, dev):
     # the closed form of the recall from the very samples: calc_3d_metric's third draw, in the cube's frame
     rng = np.random.default_rng(1)
     rng.random((N, 3)), rng.random((N, 3))
-    gt_tri = mt._mesh_device(gt, dev)
+    import cnr_amd
+    gt_tri = cnr_amd.devmesh.device_mesh(gt, dev)
     gt_pc = mt._sample(gt_tri, N, rng).double().cpu().numpy()
     exact = _cube_distance((gt_pc - t) @ R, 1.0)
     sure_below, sure_above = (exact < 0.05 - bar).sum(), (exact >= 0.05 + bar).sum()

@@ -61,9 +61,9 @@ def _built(mt, dev, verts, faces):
     """the device's keys, records (F,16) and tile rows (T,8) of a mesh"""
     import cnr_amd
     ix = mt.MeshIndex((verts, faces))
-    tri = mt._triangles((verts, faces), dev)
+    tri = cnr_amd.devmesh.device_mesh((verts, faces), dev)
     keys = torch.empty(ix.faces, device=dev, dtype=torch.int32)
-    cnr_amd._C.call("cnr_pm_index_keys", tri[0], tri[1], tri[2], ix.bbox, keys)
+    cnr_amd._C.call("cnr_pm_index_keys", tri.verts, tri.faces, tri.n_faces, ix.bbox, keys)
     raw = ix.index.cpu().numpy()
     F, T = ix.faces, ix.tiles
     assert len(raw) == X.index_bytes(F) and T == -(-F // TILE)

@@ -20,8 +20,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 SORTS = ("sort_edges", "sort_faces")
 
 
-def stage_times(cnr, verts, faces, conn, reps):
-    """{stage: ms} of meshops.components, the mean over reps after one warm-up call"""
+def stage_times(call, reps):
+    """({stage: ms}, the result) of call(timer) -- meshops.components here, meshops.simplify in tools/time_meshsimplify.py -- as
+    the mean over reps after one warm-up call"""
     acc = {}
     for rep in range(reps + 1):
         marks = []
@@ -32,7 +33,7 @@ def stage_times(cnr, verts, faces, conn, reps):
             marks.append((name, e))
         start = torch.cuda.Event(enable_timing=True)
         start.record()
-        table = cnr.meshops.components(faces, len(verts), verts, connectivity=conn, timer=timer)
+        out = call(timer)
         torch.cuda.synchronize()
         if rep == 0:
             continue
@@ -40,7 +41,7 @@ def stage_times(cnr, verts, faces, conn, reps):
         for name, e in marks:
             acc[name] = acc.get(name, 0.0) + prev.elapsed_time(e)
             prev = e
-    return {k: v / reps for k, v in acc.items()}, table
+    return {k: v / reps for k, v in acc.items()}, out
 
 
 def whole(fn, reps):
@@ -71,7 +72,7 @@ def measure(cnr, name, verts, faces, reps):
     faces_np = faces.cpu().numpy()
     rec["ms_scipy_vertex_host"], rec["scipy_components"] = (round(x, 3) if isinstance(x, float) else x for x in scipy_ms(faces_np, len(verts)))
     for conn in ("edge", "vertex"):
-        stages, table = stage_times(cnr, verts, faces, conn, reps)
+        stages, table = stage_times(lambda timer: cnr.meshops.components(faces, len(verts), verts, connectivity=conn, timer=timer), reps)
         total = sum(stages.values())
         sort = sum(stages[k] for k in SORTS)
         rec[conn] = dict(components=table.n, stages_ms={k: round(v, 3) for k, v in stages.items()}, ms_total=round(total, 3),
@@ -94,29 +95,16 @@ def main():
     a = ap.parse_args()
     import cnr_amd as cnr
     import meshops_cpu as R
-    from scene_synth import analytic_pool, sphere_radius
     assert torch.cuda.is_available(), "time_meshclean needs the GPU"
     dev = torch.device("cuda:0")
     rows = []
     if a.dims:
-        torch.manual_seed(99)
-        cfg = cnr.cfg.synthetic_config(device=str(dev), latent_dim=32, n_bins_cam2surface=4, n_bins=28)
-        gen = torch.Generator().manual_seed(11)
-        ft = cnr.fused.FusedCategoryTrainer(cfg, 1, 4, [analytic_pool(64 * 512, 4, gen)], 512, dev, seed=7, generator=gen)
-        ft.run(a.steps)
-        torch.cuda.synchronize()
-        sd = ft.state_dicts(0)
-        t = cnr.trainer.Trainer(cfg, 3, [0, 1, 2, 3])
-        with torch.no_grad():
-            t.fc_occ_map.load_state_dict(sd["FC_state_dict"])
-            t.pe.B_layer.weight.copy_(sd["PE_state_dict"]["B_layer.weight"])
-            t.shape_codes.weight.copy_(sd["shape_code_state_dict"]["weight"])
-            t.texture_codes.weight.copy_(sd["texture_code_state_dict"]["weight"])
-        t.extent_dict = {k: np.full(3, 2.4 * sphere_radius(k)) for k in range(4)}
+        from time_meshing import trained_trainer
+        t = trained_trainer(cnr, dev, a.steps)
         for D in (int(d) for d in a.dims.split(",")):
             mesh = t.meshing(2, grid_dim=D)
-            d = cnr.meshops.mesh_to_device(mesh, dev)
-            rows.append(measure(cnr, "marching cubes %d^3" % D, d["verts"], d["faces"], a.reps))
+            d = cnr.devmesh.device_mesh(mesh, dev)
+            rows.append(measure(cnr, "marching cubes %d^3" % D, d.verts, d.faces, a.reps))
     if a.ladder:
         for order in ("ascending", "shuffled"):
             v, f = R.ladder(a.ladder, order)

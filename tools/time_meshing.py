@@ -28,22 +28,15 @@ def _ms(fn, reps):
     return a.elapsed_time(b) / reps, out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--dims", default="64,128,256")
-    ap.add_argument("--out", default=None, help="also write the rows as JSON to this file")
-    a = ap.parse_args()
-    import cnr_amd as cnr
+def trained_trainer(cnr, dev, steps):
+    """a CodeNeRF Trainer of four objects whose weights were trained for `steps` fused steps on tests/scene_synth.py
+    (tools/time_meshclean.py meshes the same one)"""
     from scene_synth import analytic_pool, sphere_radius
-    assert torch.cuda.is_available(), "time_meshing needs the GPU"
-    dev = torch.device("cuda:0")
     torch.manual_seed(99)
     cfg = cnr.cfg.synthetic_config(device=str(dev), latent_dim=32, n_bins_cam2surface=4, n_bins=28)
     gen = torch.Generator().manual_seed(11)
     ft = cnr.fused.FusedCategoryTrainer(cfg, 1, 4, [analytic_pool(64 * 512, 4, gen)], 512, dev, seed=7, generator=gen)
-    ft.run(a.steps)
+    ft.run(steps)
     torch.cuda.synchronize()
     sd = ft.state_dicts(0)
     t = cnr.trainer.Trainer(cfg, 3, [0, 1, 2, 3])
@@ -53,6 +46,20 @@ def main():
         t.shape_codes.weight.copy_(sd["shape_code_state_dict"]["weight"])
         t.texture_codes.weight.copy_(sd["texture_code_state_dict"]["weight"])
     t.extent_dict = {k: np.full(3, 2.4 * sphere_radius(k)) for k in range(4)}
+    return t
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--dims", default="64,128,256")
+    ap.add_argument("--out", default=None, help="also write the rows as JSON to this file")
+    a = ap.parse_args()
+    import cnr_amd as cnr
+    assert torch.cuda.is_available(), "time_meshing needs the GPU"
+    dev = torch.device("cuda:0")
+    t = trained_trainer(cnr, dev, a.steps)
     inst = 2
     ext = t.extent_dict[inst]
     scale = torch.from_numpy((ext / np.max(ext / 2)) / (2.0 * t.bound_extent)).float().to(dev)

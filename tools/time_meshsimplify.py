@@ -16,43 +16,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from time_meshclean import stage_times, whole  # noqa: E402  (the per-stage and whole-call timers, shared)
 
 SORTS = ("sort_keys", "sort_rows", "sort_corners", "sort_vertices")
-
-
-def stage_times(cnr, verts, faces, cell, reps):
-    """{stage: ms} of meshops.simplify, the mean over reps after one warm-up call"""
-    acc = {}
-    for rep in range(reps + 1):
-        marks = []
-
-        def timer(name):
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
-        start = torch.cuda.Event(enable_timing=True)
-        start.record()
-        out = cnr.meshops.simplify(verts, faces, cell=cell, timer=timer)
-        torch.cuda.synchronize()
-        if rep == 0:
-            continue
-        prev = start
-        for name, e in marks:
-            acc[name] = acc.get(name, 0.0) + prev.elapsed_time(e)
-            prev = e
-    return {k: v / reps for k, v in acc.items()}, out
-
-
-def whole(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def sphere_volume(D):
@@ -72,7 +38,7 @@ def wavy_sheet(n):
 
 def measure(cnr, S, name, verts, faces, cell, reps, host_faces):
     F, V = len(faces), len(verts)
-    stages, (out_v, out_f, _, report) = stage_times(cnr, verts, faces, cell, reps)
+    stages, (out_v, out_f, _, report) = stage_times(lambda timer: cnr.meshops.simplify(verts, faces, cell=cell, timer=timer), reps)
     total = sum(stages.values())
     sort = sum(stages.get(k, 0.0) for k in SORTS)
     C = report["clusters"]
@@ -118,8 +84,8 @@ def main():
         for voxels in (2, 4):
             rows.append(measure(cnr, S, "marching-cubes sphere %d^3" % D, verts, faces, voxels / (D - 1.0), a.reps, a.host_faces))
     if a.sheet:
-        v, f = wavy_sheet(a.sheet)
-        verts, faces = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+        sheet = cnr.devmesh.device_mesh(wavy_sheet(a.sheet), dev)
+        verts, faces = sheet.verts, sheet.faces
         for cell in (2.0, 8.0):
             rows.append(measure(cnr, S, "wavy sheet %d x %d" % (a.sheet, a.sheet), verts, faces, cell, a.reps, a.host_faces))
         # one giant cluster: every corner in ONE segment, which a single 16-lane group walks

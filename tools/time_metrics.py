@@ -54,8 +54,8 @@ def main():
 
     mesh = cnr.vis.marching_cubes(M.sphere(256, 0.85, 4.0))
     mesh.apply_translation([-0.5, -0.5, -0.5]).apply_scale(2.0)
-    tri = MT._mesh_device(mesh, dev)
-    verts, faces, F = tri
+    tri = cnr.devmesh.device_mesh(mesh, dev)
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     rows["mc256_faces"] = F
     fa_ws = torch.empty(int(_C.load().cnr_face_area_workspace_bytes(F)), device=dev, dtype=torch.uint8)
     area, cum = torch.empty(F, device=dev, dtype=torch.float64), torch.empty(F, device=dev, dtype=torch.float64)

@@ -55,7 +55,7 @@ def _spread_ms(fn, reps):
 
 def _index_row(_C, MT, q, tri, reps):
     """the index's legs and the brute force on the same queries and mesh, one after the other in this process"""
-    verts, faces, F = tri
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
     N, dev = len(q), q.device
     lib = _C.load()
     dist, face = torch.empty(N, device=dev), torch.empty(N, device=dev, dtype=torch.int32)
@@ -104,11 +104,12 @@ def main():
     N = a.queries
     mesh = cnr.vis.marching_cubes(M.sphere(256, 0.85, 4.0))
     mesh.apply_translation([-0.5, -0.5, -0.5]).apply_scale(2.0)
-    whole = MT._mesh_device(mesh, dev)
+    whole = cnr.devmesh.device_mesh(mesh, dev)
     clipped = MT._clip(whole, MT.box_planes(np.eye(4), [1.2, 1.2, 1.0]))
     q = MT.sample_surface(cnr.vis.Mesh(mesh.vertices * 1.02, mesh.faces), N, seed=0)
     rows = {}
-    for name, (verts, faces, F) in (("mc256", whole), ("mc256_clipped", clipped)):
+    for name, tri in (("mc256", whole), ("mc256_clipped", clipped)):
+        verts, faces, F = tri.verts, tri.faces, tri.n_faces
         ws = torch.empty(int(_C.load().cnr_point_mesh_workspace_bytes(N, F)), device=dev, dtype=torch.uint8)
         dist, face = torch.empty(N, device=dev), torch.empty(N, device=dev, dtype=torch.int32)
         near = torch.empty(N, 3, device=dev)
@@ -137,7 +138,7 @@ def main():
     rows["numpy_restatement_cpu"] = dict(queries=2000, faces=2000, s=round(dt, 3), pairs_per_s=float("%.4g" % (4e6 / dt)))
     print("numpy restatement", json.dumps(rows["numpy_restatement_cpu"]), flush=True)
     if a.index:
-        lo, hi = whole[0].amin(0), whole[0].amax(0)
+        lo, hi = whole.verts.amin(0), whole.verts.amax(0)
         g = torch.Generator(device=dev).manual_seed(1)
         centre_q = (lo + hi) / 2 + (torch.rand(N, 3, device=dev, generator=g) * 2 - 1) * (1e-3 / 3 ** 0.5) * float((hi - lo).max()) / 2
         for name, pts, tri in (("mc256", q, whole), ("mc256_clipped", q, clipped), ("mc256_centre", centre_q.contiguous(), whole)):
