@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import _C, loss as loss_mod, ops, stepgraph, trainer as trainer_mod
+from . import _C, loss as loss_mod, ops, raypool, stepgraph, trainer as trainer_mod
 
 
 class BackgroundStep:
@@ -43,18 +43,11 @@ class BackgroundStep:
         self.precision = precision
         self.trainer.fc_occ_map.half = precision == "f16"
         dev = self.device
-        self.pool = dict(rgbs=pool["rgbs"].to(dev)[None].contiguous(), depth=pool["depth"].to(dev)[None].contiguous(),
-                         dirs=pool["dirs"].to(dev)[None].contiguous(), T=pool["T_wc"].to(dev)[None].contiguous())
-        self.pool_rows = self.pool["depth"].shape[1]
-        assert self.pool_rows >= 2 * self.R
-        self.perm = torch.empty(1, self.pool_rows, device=dev, dtype=torch.int32)
-        self._perm_gen = torch.Generator(device=dev)
-        self._perm_gen.manual_seed(0xB6 + 7919 * int(seed))
-        # epoch shuffle: cnr_epoch_perm (one launch) unless CNR_EPOCH_PERM=torch asks for torch.randperm (a dozen launches)
-        self._torch_perm = os.environ.get("CNR_EPOCH_PERM", "kernel") == "torch"
-        self._perm_seed, self._epoch = 0xB6 + 7919 * int(seed), 0
         self.d_state = torch.zeros(3, device=dev, dtype=torch.int64)
-        self._zero = torch.zeros(1, device=dev, dtype=torch.int64)
+        # one class, no ray shards; the per-epoch tables (max depth and mask counts of every slice: src/scene_cateogries.py:486,
+        # src/render_rays.py:66-95 are pool-row properties) for the fused tier only, where no step computes them
+        self.pool = raypool.RayPool([dict(pool, T=pool["T_wc"])], dev, self.R, seed=0xB6 + 7919 * int(seed), min_depth=cfg.min_depth,
+                                    indices=False, tables=precision == "fused")
         self.seed = int(seed) + 101
         self.params = list(self.trainer.fc_occ_map.parameters()) + list(self.trainer.pe.parameters())
         # one flat buffer for the parameters and one for their gradients (the modules' tensors become views): the optimiser is
@@ -82,29 +75,19 @@ class BackgroundStep:
         if precision != "fused":
             self._loss = torch.zeros((), device=dev)
             self.losses = torch.zeros(3, device=dev)       # depth / colour / opacity terms of the last step (src/loss.py:18-74)
-        self.cursor = 0
         self.steps_done = 0
         self._sched = stepgraph.StepGraphs([self], 3)
         self._reshuffle()
 
+    perm = property(lambda self: self.pool.perm)
+    pool_rows = property(lambda self: self.pool.rows)
+    cursor = property(lambda self: self.pool.cursor)
+
     def _reshuffle(self):
-        """src/scene_cateogries.py:439-449 as a new permutation; cursor back to 0.  Fused tier: the max depth of every slice of
-        the epoch in one launch (cnr_slice_maxdepth; src/scene_cateogries.py:486 needs it per batch), so that no step computes it."""
-        if self._torch_perm:
-            self.perm[0].copy_(torch.randperm(self.pool_rows, device=self.device, generator=self._perm_gen))
-            self.d_state[0:1].copy_(self._zero)
-        else:     # one launch: the keyed bijection of cnr_epoch_perm, and the cursor back to row 0
-            _C.call("cnr_epoch_perm", self.perm, self.pool_rows, 1, self._perm_seed, self._epoch, None, self.d_state, 0)
-            self._epoch += 1
-        self.cursor = 0
-        if self.precision == "fused":
-            _C.call("cnr_slice_maxdepth", self.pool["depth"], self.perm, self.pool_rows, 1, self.R, self.n_slices, self.slice_max)
-            # ... and its mask counts (src/render_rays.py:66-95 are pool-row properties): the composite / loss launch reads its
-            # slice's entry instead of every block counting the batch's 1200 labels first
-            _C.call("cnr_slice_maskcounts", self.pool["rgbs"], self.pool["depth"], self.perm, self.pool_rows, 1, self.R,
-                    self.n_slices, float(self.cfg.min_depth), self.counts_tab)
-            if self.sample_in_tail:
-                self._sample()      # the epoch's first batch; every later one is drawn by the previous step's last launch
+        """the pool's epoch end; with the sampler in the tail, the epoch's first batch (the steps' last launches draw the others)"""
+        self.pool.reshuffle(self.d_state)
+        if self.precision == "fused" and self.sample_in_tail:
+            self._sample()
 
     def record(self, slot=None, par=0):
         """sample -> PE -> OccupancyMap -> composite + losses -> backward -> AdamW -> advance (all stream-ordered).  (One state
@@ -113,9 +96,7 @@ class BackgroundStep:
             return self._body_fused()
         cfg, t = self.cfg, self.trainer
         self.gflat.zero_()
-        b = ops.sample_rays(self.pool["rgbs"], self.pool["depth"], self.pool["dirs"], self.pool["T"], self.n1, self.n2,
-                            cfg.surface_eps, cfg.stop_eps, min_bound=cfg.min_depth, world_frame=True, seed=self.seed,
-                            d_state=self.d_state, rays=self.R, out=self.bufs, perm=self.perm)
+        b = self._sample()
         alpha, color = t.fc_occ_map(t.pe(b["pts"][0]))
         loss, ld, _ = loss_mod.step_batch_loss(alpha[None], color[None], b["gt_depth"], b["gt_rgb"], b["labels"],
                                                b["depth_mask"], b["z"])
@@ -152,9 +133,6 @@ class BackgroundStep:
         self.dw_chunk = int(os.environ.get('CNR_BG_DW_CHUNK', '384'))
         self.nblk, self.nchunk = int(lib.cnr_bg_blocks(M)), int(lib.cnr_bg_dw_chunks(M, self.dw_chunk))
         self.gscale = float(2 ** round(math.log2(max(self.R, 2))))      # power-of-two loss scale of the f16 gradient chain
-        self.n_slices = self.pool_rows // self.R
-        self.slice_max = torch.zeros(1, self.n_slices, device=dev)
-        self.counts_tab = torch.zeros(self.n_slices, 2, 4, device=dev)
         self._packed_for = None          # version of self.flat the fragment images were packed from
         f = lambda *sh, dt=torch.float32: torch.empty(*sh, device=dev, dtype=dt)
         self.fb = dict(packed=f(int(lib.cnr_bg_pack_bytes()), dt=torch.uint8), sigma=f(1, self.R, self.S),
@@ -182,7 +160,7 @@ class BackgroundStep:
         """forward -> composite + losses + their gradient + backward -> weight gradients -> reduce + AdamW + fragment refresh + loss
         values + the NEXT step's sampler: four launches, nothing under autograd (train.py:113-121,172-184 for the background; six
         launches with CNR_BG_FUSE_RENDER=0 CNR_BG_SAMPLE_IN_TAIL=0, bit-equal)."""
-        cfg, o = self.cfg, self.fb
+        cfg, o, pool = self.cfg, self.fb, self.pool
         b = self.bufs if self.sample_in_tail else self._sample()      # (in the tail: drawn by the previous step, or by _reshuffle)
         scale, M = float(self.trainer.pe._scale), self.M
         _C.call("cnr_bg_forward", b["pts"], self.flat, o["packed"], scale, M, o["sigma"], o["rgbs"], o["act"], o["eimg"])
@@ -191,7 +169,7 @@ class BackgroundStep:
             # d sigma / d colour round trip less); the step state then moves in the weight-gradient launch
             _C.call_struct("cnr_bg_backward_render", pts=b["pts"], theta=self.flat, packed=o["packed"], scale=scale, R=self.R,
                            S=self.S, sigma=o["sigma"], rgb=o["rgbs"], z=b["z"], gt_depth=b["gt_depth"], gt_rgb=b["gt_rgb"],
-                           labels=b["labels"], depth_mask=b["depth_mask"], counts_tab=self.counts_tab, d_state=self.d_state,
+                           labels=b["labels"], depth_mask=b["depth_mask"], counts_tab=pool.counts_tab, d_state=self.d_state,
                            color_scaling=5.0, opacity_scaling=10.0, grad_scale=self.gscale, act=o["act"], dpre=o["dpre"],
                            records=o["records"], depth=o["depth"], var=o["var"], rgb_render=o["rgb"], opacity=o["opa"], d_sigma=None, d_rgb=None,
                            loss_workspace=o["rl_ws"], loss_workspace_bytes=o["rl_ws"].numel())
@@ -199,7 +177,7 @@ class BackgroundStep:
         else:
             _C.call("cnr_render_loss", o["sigma"], o["rgbs"], b["z"], b["gt_depth"], b["gt_rgb"], b["labels"], b["depth_mask"],
                     5.0, 10.0, self.gscale, o["dsig"], o["drgb"], o["depth"], o["var"], o["rgb"], o["opa"], 1, self.R, self.S,
-                    o["rl_ws"], o["rl_ws"].numel(), self.counts_tab, self.d_state)
+                    o["rl_ws"], o["rl_ws"].numel(), pool.counts_tab, self.d_state)
             _C.call("cnr_bg_backward", b["pts"], self.flat, o["packed"], scale, M, o["dsig"], o["drgb"], o["rgbs"], o["act"],
                     o["dpre"], o["records"], self.d_state, self.R)
             _C.call("cnr_bg_dw", o["act"], o["dpre"], o["eimg"], M, self.dw_chunk, o["partials"], None, 0)
@@ -208,11 +186,11 @@ class BackgroundStep:
                            partials=o["partials"], chunks=self.nchunk, records=o["records"], nrec=self.nblk, grad_scale=self.gscale,
                            lr=cfg.learning_rate, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=cfg.weight_decay,
                            packed=o["packed"], rl_workspace=o["rl_ws"], rl_R=0 if self.fuse_render else self.R, losses=o["losses"],
-                           flags=o["flags"], rgbs=self.pool["rgbs"], depth=self.pool["depth"], dirs_c=self.pool["dirs"],
-                           T=self.pool["T"], seed=int(self.seed), offset=0, d_state=self.d_state, pool_rows=self.pool_rows,
-                           max_bound=self.slice_max, max_bound_slices=self.n_slices, world_frame=1, R=self.R, n1=self.n1,
+                           flags=o["flags"], rgbs=pool.rgbs, depth=pool.depth, dirs_c=pool.dirs,
+                           T=pool.T, seed=int(self.seed), offset=0, d_state=self.d_state, pool_rows=pool.rows,
+                           max_bound=pool.slice_max, max_bound_slices=pool.n_slices, world_frame=1, R=self.R, n1=self.n1,
                            n2=self.n2, eps=float(cfg.surface_eps), stop_eps=float(cfg.stop_eps), min_bound=float(cfg.min_depth),
-                           perm=self.perm, z=b["z"], pts=b["pts"], origins=None, dirs_o=None, gt_rgb=b["gt_rgb"],
+                           perm=pool.perm, z=b["z"], pts=b["pts"], origins=None, dirs_o=None, gt_rgb=b["gt_rgb"],
                            gt_depth=b["gt_depth"], depth_mask=b["depth_mask"], labels=b["labels"])
         else:
             _C.call("cnr_bg_tail", self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, o["partials"], self.nchunk, o["records"],
@@ -220,12 +198,13 @@ class BackgroundStep:
                     o["rl_ws"], 0 if self.fuse_render else self.R, o["losses"], o["flags"])
 
     def _sample(self):
-        """a2-a6 for the step at the device cursor (cnr_sample_rays, world frame, per-epoch max-depth table) into self.bufs"""
-        cfg = self.cfg
-        return ops.sample_rays(self.pool["rgbs"], self.pool["depth"], self.pool["dirs"], self.pool["T"], self.n1, self.n2,
-                               cfg.surface_eps, cfg.stop_eps, min_bound=cfg.min_depth, world_frame=True, seed=self.seed,
-                               d_state=self.d_state, rays=self.R, out=self.bufs, perm=self.perm, max_bound=self.slice_max,
-                               max_bound_slices=self.n_slices)
+        """a2-a6 for the step at the device cursor (cnr_sample_rays, world frame) into self.bufs; the slice's max depth out of the
+        per-epoch table where the pool keeps one (the fused tier), else computed by the sampler"""
+        cfg, pool = self.cfg, self.pool
+        return ops.sample_rays(pool.rgbs, pool.depth, pool.dirs, pool.T, self.n1, self.n2, cfg.surface_eps, cfg.stop_eps,
+                               min_bound=cfg.min_depth, world_frame=True, seed=self.seed, d_state=self.d_state, rays=self.R,
+                               out=self.bufs, perm=pool.perm, max_bound=pool.slice_max,
+                               max_bound_slices=0 if pool.slice_max is None else pool.n_slices)
 
     def repack(self):
         """Fused tier: rebuild the f16 fragment images from ``self.flat`` (cnr_bg_pack).  Needed once before the first step and
@@ -246,12 +225,12 @@ class BackgroundStep:
     def before_step(self):
         if self.precision == "fused" and (self._packed_for is None or self._packed_for != self.flat._version):
             self.repack()
-        if self.cursor >= self.pool_rows - self.R:
+        if self.pool.due():
             self._reshuffle()
-        return -(-(self.pool_rows - self.R - self.cursor) // self.R)       # steps before the next reshuffle
+        return self.pool.steps_left()
 
     def advance(self, U=1):
-        self.cursor += U * self.R
+        self.pool.advance(U)
         self.steps_done += U
         if self.precision == "fused":
             self._packed_for = self.flat._version     # (the steps' own updates: kernels do not bump torch's version counter)

@@ -28,13 +28,6 @@ inline int set_max_dynamic_lds(DeviceOnce& once, const void* fn, int bytes) {
   if (dev < 64) once.mask.fetch_or(bit, std::memory_order_release);
   return 0;
 }
-// true exactly once per device (for one-time device-side tables in static device storage)
-inline bool first_on_device(DeviceOnce& once) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev >= 64) return true;
-  const uint64_t bit = 1ull << dev;
-  return (once.mask.fetch_or(bit, std::memory_order_acq_rel) & bit) == 0;
-}
 }  // namespace cnr
 
 // fp32 trunk blob offsets (floats) -- see CNR_TRUNK_PARAMS in cnr_hip.h

@@ -16,11 +16,9 @@ import os
 
 import torch
 
-from . import _C, ops, parallel, stepgraph
+from . import _C, ops, parallel, raypool, stepgraph
 from .embedding import UNIDIRS
 from .ops import LATENT_LAYERS, TRUNK_LAYERS, TRUNK_PARAMS
-
-_LAT_FANIN_TARGET = ops._LATENT_TARGETS  # (w_off, b_off, ld) of the trunk layer each latent slot feeds
 
 
 class ParamLayout:
@@ -91,7 +89,7 @@ class FusedCategoryTrainer:
 
     def __init__(self, cfg, n_cls, n_obj, pools, rays_per_step, device, seed=0, generator=None,
                  grad_scale=None, bwd_blocks=0, process_group=None, use_graph=True, split_graph=False,
-                 fuse_render=True, split_weights=None, shard=None, n_cls_global=None, class_ids=None,
+                 fuse_render=True, shard=None, n_cls_global=None, class_ids=None,
                  check_every=0, world_frame=None, dp_rank=None, dp_world=None, one_launch=None, unroll=16,
                  precise_geometry=None):
         # n_obj: one count for every class, or one per (local) class -- the reference's categories differ (train.py:92-96).  The
@@ -111,25 +109,18 @@ class FusedCategoryTrainer:
         # the code tables are an AdamW group of their own in the reference (train.py:40,54-64); the shipped configs give both
         # groups the same values
         self.code_lr, self.code_wd = float(cfg.code_learning_rate), float(cfg.code_weight_decay)
-        # ---- sharding ---------------------------------------------------------------------------------------------
+        # ---- shard plan -------------------------------------------------------------------------------------------
         self.pg = process_group
-        pg_world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
-        pg_rank = 0 if process_group is None else torch.distributed.get_rank(process_group)
-        # (dp_rank / dp_world without a process group: one rank of a ray-sharded world, the gradient exchange left to the
-        #  caller -- tests emulate N ranks in one process this way)
-        self.world = int(dp_world) if dp_world is not None else pg_world
-        self.rank = int(dp_rank) if dp_rank is not None else pg_rank
-        self.shard = shard if shard is not None else ("ray" if self.world > 1 else None)
-        assert self.shard in (None, "ray", "class")
-        self.ray_world = self.world if self.shard == "ray" else 1       # ranks that share one class's rays
-        self.ray_rank = self.rank if self.shard == "ray" else 0
-        self.Rg = self.R * self.ray_world                                # rows of a global slice
-        if self.shard == "class":
-            self.n_cls_global = int(n_cls_global) if n_cls_global is not None else n_cls * self.world
-            self.class_ids = list(class_ids) if class_ids is not None else list(range(self.rank, self.n_cls_global, self.world))
-            assert len(self.class_ids) == n_cls
-        else:
-            self.n_cls_global, self.class_ids = n_cls, list(range(n_cls))
+        plan = parallel.shard_plan(process_group, shard, n_cls, self.R, dp_rank, dp_world, n_cls_global, class_ids)
+        self.world, self.rank, self.shard, self.ray_world, self.ray_rank = plan.world, plan.rank, plan.shard, plan.ray_world, plan.ray_rank
+        self.n_cls_global, self.class_ids, self._rng = plan.n_cls_global, plan.class_ids, plan.rng_map
+        self.grad_exchange = self.shard == "ray" and self.world > 1
+        # the field backward leaves per-workgroup records + the fixed-point table; ONE later launch reduces them next to
+        # the latent backward: with AdamW and the epilogue when no gradient exchange follows (cnr_step_tail: single GPU,
+        # class sharding), gradient only when rays are sharded (cnr_step_grad: the all-reduce comes between gradient and
+        # optimiser)
+        self.use_records, self.fused_tail = True, not self.grad_exchange
+        # ---- parameters and optimiser buffers -----------------------------------------------------------------------
         theta_all, self.lay = init_params(self.n_cls_global, self.L, n_obj, generator, "cpu")
         theta0 = theta_all[self.class_ids].contiguous()
         for c, k in enumerate(n_obj_list):          # code rows beyond a class's own objects: unused, kept at zero
@@ -145,10 +136,37 @@ class FusedCategoryTrainer:
         # ... plus (<= 15 objects per class with the 8-wave backward, <= 4 otherwise) the int64 fixed-point table of the per-object bias-row sums
         # that the field backward fills with integer atomics for cnr_step_tail
         n_th, n_db = self.theta.numel(), n_cls * n_obj * 128
-        # the field backward leaves per-workgroup records + the fixed-point table; ONE later launch reduces them next to
-        # the latent backward: with AdamW and the epilogue when no gradient exchange follows (cnr_step_tail: single GPU,
-        # class sharding), gradient only when rays are sharded (cnr_step_grad: the all-reduce comes between gradient and
-        # optimiser)
+        fix_off = (n_th + n_db + 3) // 4 * 4                      # 16-byte aligned
+        self._gbuf = torch.zeros(fix_off + 2 * 8 * n_db, device=self.device)  # 8 copies
+        self.rows_fix = self._gbuf[fix_off:].view(torch.int64)
+        self.grad = self._gbuf[:self.theta.numel()].view_as(self.theta)
+        self.dbias = self._gbuf[n_th:n_th + n_db].view(n_cls * n_obj, 4, 32)
+        self.exp_avg = torch.zeros_like(self.theta)
+        self.exp_avg_sq = torch.zeros_like(self.theta)
+        # device-side step state {pool cursor, rng step, optimiser step}, two copies: step k reads copy k & 1 and its
+        # last kernel writes copy (k + 1) & 1 -- no kernel ever writes a state another kernel of the same step reads
+        self.d_state2 = torch.zeros(2, 3, device=self.device, dtype=torch.int64)
+        self.seed = int(seed) + 1
+        self.grad_scale = float(grad_scale) if grad_scale else float(2 ** round(math.log2(max(plan.Rg, 2))))
+        self.bufs = {}
+        self.losses = torch.zeros(3, n_cls, device=self.device)
+        self.flags = torch.zeros(n_cls, device=self.device, dtype=torch.int32)
+        self.clamp = torch.zeros(n_cls, device=self.device, dtype=torch.int32)
+        self.check_every = int(check_every)
+        # ---- pool ---------------------------------------------------------------------------------------------------
+        # device-resident pools stacked over classes: (C, Npool, ...).  A class that trains in the WORLD frame (the
+        # reference does that for single-object categories: origin_dirs_W on T_wc, src/scene_cateogries.py:427-432) keeps
+        # inv(T_wc) in the pose slot: the sampler's origin_dirs_O inverts it back (rigid, so exact to fp32 rounding)
+        if world_frame is None:
+            world_frame = [k == 1 and "T_wc" in p for k, p in zip(n_obj_list, pools)]
+        self.world_frame = [bool(world_frame)] * n_cls if isinstance(world_frame, (bool, int)) else [bool(w) for w in world_frame]
+        self.pool = raypool.RayPool(
+            [dict(p, T=torch.linalg.inv(p["T_wc"]) if wf else p["T_co"]) for p, wf in zip(pools, self.world_frame)], self.device,
+            plan.Rg, self.ray_world, self.ray_rank, self.R, seed=0x5EED + 7919 * int(seed),
+            class_ids=torch.tensor(self.class_ids, device=self.device, dtype=torch.int32), min_depth=cfg.min_depth)
+        if self.shard == "class" and self.pg is not None and self.world > 1:
+            parallel.check_same_epochs(self.pool_rows, self.Rg, self.pg, self.world, self.device)
+        # ---- dispatch choice ----------------------------------------------------------------------------------------
         # Forward + render / loss + the whole backward in ONE launch (cnr_field_train, the 8-wave kernel's record path): a ray takes
         # 16 / 32 / 64 / 128 padded sample slots; taken when at least 60 % of them are real samples (S = 10, 16, 20-32, 39-64,
         # 77-128), else two calls, whose extra forward costs less than the dead lanes would.  CNR_ONE_LAUNCH=0 keeps the two calls.
@@ -164,89 +182,29 @@ class FusedCategoryTrainer:
             one = True              # (rays of up to 16 samples get a 32-slot tile of their own there: cnr_field_train_blocks)
         else:
             one = one and fuse_render and self.S <= 128 and self.S >= 0.6 * slots
-        self.use_records = True
-        self.grad_exchange = self.shard == "ray" and self.world > 1
-        self.fused_tail = not self.grad_exchange and self.use_records
-        fix_off = (n_th + n_db + 3) // 4 * 4                      # 16-byte aligned
-        self._gbuf = torch.zeros(fix_off + 2 * 8 * n_db, device=self.device)  # 8 copies
-        self.rows_fix = self._gbuf[fix_off:].view(torch.int64)
-        self.grad = self._gbuf[:self.theta.numel()].view_as(self.theta)
-        self.exp_avg = torch.zeros_like(self.theta)
-        self.exp_avg_sq = torch.zeros_like(self.theta)
-        # device-resident pools stacked over classes: (C, Npool, ...).  A class that trains in the WORLD frame (the
-        # reference does that for single-object categories: origin_dirs_W on T_wc, src/scene_cateogries.py:427-432) keeps
-        # inv(T_wc) in the pose slot: the sampler's origin_dirs_O inverts it back (rigid, so exact to fp32 rounding)
-        if world_frame is None:
-            world_frame = [k == 1 and "T_wc" in p for k, p in zip(n_obj_list, pools)]
-        self.world_frame = [bool(world_frame)] * n_cls if isinstance(world_frame, (bool, int)) else [bool(w) for w in world_frame]
-        # Pools of different lengths (every real scene: a category's pool is the sum of its instances' crop areas,
-        # src/scene_cateogries.py:164-260) are padded to the longest; a padding row is never referenced, because the step
-        # reaches the pool only through the permutation `perm`, which _reshuffle fills per class from the class's OWN rows
-        self.pool_rows_cls = [int(p["depth"].shape[0]) for p in pools]
-        self.pool_rows = max(self.pool_rows_cls)
-        self.ragged = min(self.pool_rows_cls) != self.pool_rows
-
-        def padded(t):
-            t = t.to(self.device)
-            if t.shape[0] == self.pool_rows:
-                return t
-            return torch.cat([t, t[:1].expand(self.pool_rows - t.shape[0], *t.shape[1:])])
-        st = lambda k: torch.stack([padded(p[k]) for p in pools]).contiguous()
-        T = torch.stack([padded(torch.linalg.inv(p["T_wc"]) if wf else p["T_co"]) for p, wf in zip(pools, self.world_frame)])
-        self.pool = dict(rgbs=st("rgbs"), depth=st("depth"), dirs=st("dirs"), T=T.contiguous(), indices=st("indices"))
-        assert min(self.pool_rows_cls) >= 2 * self.Rg, "every class's pool must hold two slices of rays"
-        if self.shard == "class" and self.pg is not None and self.world > 1:
-            # the per-epoch OR of the empty flags is a collective issued at every reshuffle: all ranks must reshuffle in the
-            # same steps, i.e. hold pools of the same length and take the same rays per step -- checked here, where a
-            # mismatch is a message instead of a hang at the first epoch end
-            mine = torch.tensor([self.pool_rows, self.Rg], dtype=torch.int64,
-                                device=self.device if torch.distributed.get_backend(self.pg) == "nccl" else "cpu")
-            every = [torch.zeros_like(mine) for _ in range(self.world)]
-            torch.distributed.all_gather(every, mine, group=self.pg)
-            every = [tuple(int(v) for v in t.tolist()) for t in every]
-            if len(set(every)) != 1:
-                raise ValueError(f"class shards need the same pool length and rays per step on every rank, got (pool_rows, rays) = {every}")
-        # device-side step state {pool cursor, rng step, optimiser step}, two copies: step k reads copy k & 1 and its
-        # last kernel writes copy (k + 1) & 1 -- no kernel ever writes a state another kernel of the same step reads
-        self.d_state2 = torch.zeros(2, 3, device=self.device, dtype=torch.int64)
-        # epoch shuffle as an index permutation (C, pool_rows): the pool itself never moves.  Drawn from a generator of
-        # its own so that every rank of a sharded run draws the same permutations, whatever else uses the default one
-        self.perm = torch.empty(n_cls, self.pool_rows, device=self.device, dtype=torch.int32)
-        self._perm_gen = torch.Generator(device=self.device)
-        self._perm_gen.manual_seed(0x5EED + 7919 * int(seed))
-        self._cursor0 = torch.tensor([self.ray_rank * self.R], device=self.device, dtype=torch.int64)
-        # epoch shuffle: cnr_epoch_perm (one launch; the order is a function of seed, epoch and global class id) unless
-        # CNR_EPOCH_PERM=torch asks for torch.randperm from one generator, as rounds 1-3 did (a dozen launches per epoch end)
-        self._torch_perm = os.environ.get("CNR_EPOCH_PERM", "kernel") == "torch"
-        assert not (self.ragged and self._torch_perm), "pools of different lengths need the kernel permutation (cnr_epoch_perm)"
-        # ragged pools: each class walks its OWN epochs (a reshuffle whenever i_batch >= N_c - n, src/scene_cateogries.py:439-449);
-        # per class the epoch it is in and the slice of that epoch the next filled permutation row starts with
-        self._cls_epoch = [0] * n_cls
-        self._cls_slice = [0] * n_cls
-        self._perm_scratch = torch.empty(self.pool_rows, device=self.device, dtype=torch.int32) if self.ragged else None
-        self._perm_seed, self._epoch, self._cursor0_host = 0x5EED + 7919 * int(seed), 0, self.ray_rank * self.R
-        self._class_ids_dev = torch.tensor(self.class_ids, device=self.device, dtype=torch.int32)
-        # per-epoch tables, one entry per LOCAL slice (index = device cursor / R): the max depth of the (global) slice
-        # (scene_cateogries.py:486) and the mask counts + any-class-empty flags of the (global) slice
-        # (render_rays.py:66-95) -- no step computes a maximum or counts a mask
-        self.n_gslices = self.pool_rows // self.Rg
-        self.n_slices = self.n_gslices * self.ray_world
-        self.slice_max = torch.zeros(n_cls, self.n_slices, device=self.device)
-        self.counts_tab = torch.zeros(self.n_slices, n_cls + 1, 4, device=self.device)
-        self.cursor = 0
-        self.seed = int(seed) + 1
-        self.grad_scale = float(grad_scale) if grad_scale else float(2 ** round(math.log2(max(self.Rg, 2))))
         # workgroups per class of the field kernels (0 = this default): every workgroup copies the class's 61 KB operand image in
         # and leaves a 58 KB gradient record, so with several classes per GPU fewer, longer-running workgroups per class win --
         # 256 in total, one per CU, in one round.  Measured (2048 x 64 per class, M rays/s; 256 per class -> 256 / C per class):
         # 2 classes 39.5 -> 43.1, 3: 41.2 (= at 170), 4: 43.7 -> 47.7 (48.7 at 128), 8: 50.9 (at 64) -> 53.7, 16: 46.4 -> 57.0
         # (241 MB of records per step -> 15 MB); 1.5 rounds (2 x 192) is the worst choice: 33.5
         self.bwd_blocks = int(bwd_blocks) if int(bwd_blocks) > 0 else max(4, 256 // max(n_cls, 1))
-        self.bufs = {}
-        self.losses = torch.zeros(3, n_cls, device=self.device)
-        self.flags = torch.zeros(n_cls, device=self.device, dtype=torch.int32)
-        self.clamp = torch.zeros(n_cls, device=self.device, dtype=torch.int32)
-        self.check_every = int(check_every)
+        self._nwg = int(_C.load().cnr_field_bwd_pipe_blocks(self.R, self.S, 4, self.bwd_blocks))
+        # Precise geometry branch (default ON): the layers between the sample and the x10 occupancy logit as three f16
+        # products per fragment, Wh xh + Wl xh + Wh xl (include/cnr_hip.h, cnr_pack_weights_lo).  Plain f16 operands hold
+        # north_star's 1e-3 on the occupancy only at initialisation (6.7e-4); after 400 / 5000 training steps they give
+        # 1.8e-3 / 2.0e-3 (the logit reaches hundreds), the three-product form 2e-6 (tests/test_trained_parity_gpu.py,
+        # DESIGN.md section 3.3).  precise_geometry=False / CNR_PRECISE_GEOMETRY=0: the plain-f16 forward, for the cost
+        # comparison only.
+        self.precise = bool(int(os.environ.get("CNR_PRECISE_GEOMETRY", "1"))) if precise_geometry is None \
+            else bool(precise_geometry)
+        # forward + render/loss in one launch where the shape allows (S a multiple of 32 up to 128), else two launches
+        self._rl_blocks = int(_C.load().cnr_field_fwd_render_blocks(self.R, self.S)) if fuse_render else 0
+        # ... and forward + render / loss + the whole backward in ONE launch (``one``, decided above): no second forward, no
+        # d sigma / d colour round trip
+        self._ft_blocks = int(_C.load().cnr_field_train_blocks(self.R, self.S, self.bwd_blocks, n_obj)) if (one and fuse_render) else 0
+        if self._ft_blocks:
+            self._nwg = self._ft_blocks
+        # ---- graphs -------------------------------------------------------------------------------------------------
         # run(n): `unroll` (even) steps per hipGraph launch.  Consecutive graph launches leave ~8 us of idle GPU between them
         # (measured, rocprofv3 kernel trace: the kernels INSIDE a graph follow each other without a gap), which is 12 % of a
         # 65 us step; the steps before the last of such a launch keep their loss values / flags in these slots
@@ -255,26 +213,6 @@ class FusedCategoryTrainer:
         self._flags_hist = torch.zeros(self.unroll - 1, n_cls, device=self.device, dtype=torch.int32)
         self._out_slot = None       # capture of a multi-step graph: which history slot the step being recorded writes
         self._last_multi = 0        # steps in the last launch that left their values in the history slots
-        self.dbias = self._gbuf[n_th:n_th + n_db].view(n_cls * n_obj, 4, 32)
-        self._nwg = int(_C.load().cnr_field_bwd_pipe_blocks(self.R, self.S, 4, self.bwd_blocks))
-        # Precise geometry branch (default ON): the layers between the sample and the x10 occupancy logit as three f16
-        # products per fragment, Wh xh + Wl xh + Wh xl (include/cnr_hip.h, cnr_pack_weights_lo).  Plain f16 operands hold
-        # north_star's 1e-3 on the occupancy only at initialisation (6.7e-4); after 400 / 5000 training steps they give
-        # 1.8e-3 / 2.0e-3 (the logit reaches hundreds), the three-product form 2e-6 (tests/test_trained_parity_gpu.py,
-        # DESIGN.md section 3.3).  precise_geometry=False / CNR_PRECISE_GEOMETRY=0: the plain-f16 forward, for the cost
-        # comparison only.  (split_weights: the former name of the option.)
-        if precise_geometry is None:
-            precise_geometry = split_weights
-        self.precise = bool(int(os.environ.get("CNR_PRECISE_GEOMETRY", "1"))) if precise_geometry is None \
-            else bool(precise_geometry)
-        self.split_weights = self.precise
-        # forward + render/loss in one launch where the shape allows (S a multiple of 32 up to 128), else two launches
-        self._rl_blocks = int(_C.load().cnr_field_fwd_render_blocks(self.R, self.S)) if fuse_render else 0
-        # ... and forward + render / loss + the whole backward in ONE launch (``one``, decided above): no second forward, no
-        # d sigma / d colour round trip
-        self._ft_blocks = int(_C.load().cnr_field_train_blocks(self.R, self.S, self.bwd_blocks, n_obj)) if (one and fuse_render) else 0
-        if self._ft_blocks:
-            self._nwg = self._ft_blocks
         self.use_graph = use_graph
         self.split_graph = bool(split_graph)     # the two-graph form of the distributed step, for single-GPU tests
         self.steps_done = 0
@@ -282,6 +220,18 @@ class FusedCategoryTrainer:
         self._sched = stepgraph.StepGraphs([self], 2, self.unroll, groups=not split, single=self._split_step if split else None)
         self.graphs = self._sched.graphs         # parity -> graph (or (front, back) pair), (parity, U) -> graph of U steps
         self._reshuffle()
+
+    # ---- the pool's values under the names tests and tools read them by (the pool's own tensors: in-place writes land) ----------
+    perm = property(lambda self: self.pool.perm)
+    pool_rows = property(lambda self: self.pool.rows)
+    pool_rows_cls = property(lambda self: self.pool.rows_cls)
+    ragged = property(lambda self: self.pool.ragged)
+    cursor = property(lambda self: self.pool.cursor)
+    counts_tab = property(lambda self: self.pool.counts_tab)
+    slice_max = property(lambda self: self.pool.slice_max)
+    n_slices = property(lambda self: self.pool.n_slices)
+    n_gslices = property(lambda self: self.pool.n_gslices)
+    Rg = property(lambda self: self.pool.Rg)
 
     # ---- one step, eager (also the body that gets captured) ------------------------------------------
     @property
@@ -303,8 +253,7 @@ class FusedCategoryTrainer:
     def _step_front(self):
         """param prep ... latent backward: everything up to the (optional) gradient all-reduce."""
         C, R, S, n_obj, L = self.C, self.R, self.S, self.n_obj, self.L
-        cfg, v, lay = self.cfg, self.lay.views(self.theta), self.lay
-        gv = self.lay.views(self.grad)
+        cfg, lay, pool = self.cfg, self.lay, self.pool
         o = self.bufs
         if "zl" not in o:
             kw = dict(device=self.device, dtype=torch.float32)
@@ -326,7 +275,6 @@ class FusedCategoryTrainer:
             o["bwd_ws"] = torch.empty(_C.field_bwd_workspace_bytes(C, self.bwd_blocks), device=self.device,
                                       dtype=torch.uint8)
         zl, brows, packed = o["zl"], o["brows"], o["packed"]
-        lat_args = (lay.total, lay.latW[0], lay.latb[0], lay.shape[0], lay.tex[0], L, n_obj, C)
         # B, dtrunk, dB: class 0's slice of the flat (C, P) buffers + the class stride P (no gather / scatter copies)
         P = lay.total
         Bc = self.theta[0, lay.B[0]:lay.B[1]]
@@ -338,11 +286,10 @@ class FusedCategoryTrainer:
         # latent layers (per-object bias rows) | f16 operand image of the trunk | a2-a6: slice the device pool at
         # the device cursor, transform, sample (the slice's max depth comes out of self.slice_max, which _reshuffle
         # filled for the whole epoch)
-        b = ops.step_prologue(self.theta, lay, L, n_obj, packed, zl, brows, self._gbuf, self.pool["rgbs"],
-                              self.pool["depth"], self.pool["dirs"], self.pool["T"], self.n1, self.n2, cfg.surface_eps,
-                              cfg.stop_eps, cfg.min_depth, self.seed, self.d_state2[self.parity], R, self.bufs,
-                              self.slice_max, self.pool["indices"], self.perm, max_bound_slices=self.n_slices,
-                              rng=self._rng_map(), packed_lo=o["packed_lo"])
+        b = ops.step_prologue(self.theta, lay, L, n_obj, packed, zl, brows, self._gbuf, pool.rgbs, pool.depth, pool.dirs, pool.T,
+                              self.n1, self.n2, cfg.surface_eps, cfg.stop_eps, cfg.min_depth, self.seed,
+                              self.d_state2[self.parity], R, self.bufs, pool.slice_max, pool.indices, pool.perm,
+                              max_bound_slices=pool.n_slices, rng=self._rng, packed_lo=o["packed_lo"])
         ray_row = b["ray_row"]
         lo = o["packed_lo"]
         # the loss gradient of a ray carries 1 / (GLOBAL mask count of its class) out of counts_tab: ray shards add up to
@@ -456,9 +403,16 @@ class FusedCategoryTrainer:
 
     # ---- the branch interface of stepgraph.StepGraphs (with ``parity`` and ``steps_done``) ------------------------------
     def before_step(self):
-        if self.cursor >= self.pool_rows - self.Rg:    # epoch end: reshuffle (i_batch >= N - n, scene_cateogries.py:439-449)
+        if self.pool.due():
             self._reshuffle()
-        return -(-(self.pool_rows - self.Rg - self.cursor) // self.Rg)     # steps before the next reshuffle
+        return self.pool.steps_left()
+
+    def _reshuffle(self):
+        """The pool's epoch end on the state copy the next step reads; the only communication is, with class shards, one
+        all-reduce (MAX) of the (slices, 3) empty flags per epoch (no ray shards there: the tables were written in place)."""
+        self.pool.reshuffle(self.d_state2[self.parity])
+        if self.shard == "class" and self.pg is not None and self.world > 1:
+            parallel.allreduce_any_(self.pool.counts_tab[:, self.C, :3], self.pg)
 
     def record(self, slot, par):
         keep, self.parity, self._out_slot = self.parity, par, slot
@@ -468,26 +422,13 @@ class FusedCategoryTrainer:
     def advance(self, U=1):
         before = self.steps_done
         self.parity ^= U & 1
-        self.cursor += U * self.Rg
+        self.pool.advance(U)
         self.steps_done += U
         self._last_multi = U - 1                       # steps of this launch that left their values in the history slots
         if self.check_every and self.steps_done // self.check_every != before // self.check_every:
             self.check_flags()
 
     _pre_step, _post_step = before_step, advance       # (the names the emulated ranks of tests/test_multigpu_gpu.py step by)
-
-    def _rng_map(self):
-        """(first global class, class stride, global rays per class, first ray of this rank): the Philox counter of a ray
-        is its index in the GLOBAL batch, so shards draw what a single GPU would (include/cnr_hip.h, cnr_step_prologue)."""
-        if self.shard == "class":
-            ids = self.class_ids
-            stride = ids[1] - ids[0] if len(ids) > 1 else 1
-            if all(ids[k] == ids[0] + k * stride for k in range(len(ids))):
-                return (ids[0], stride, self.R, 0)
-            return (0, 0, 0, 0)       # irregular ownership: local indices (still a valid stream, just not the single-GPU one)
-        if self.shard == "ray":
-            return (0, 1, self.Rg, self.ray_rank * self.R)
-        return (0, 0, 0, 0)
 
     def check_flags(self):
         """The reference exits on a loss above 1e5 (src/render_rays.py:87-89); the step itself never syncs, so the
@@ -559,65 +500,6 @@ class FusedCategoryTrainer:
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / iters
-
-    def _reshuffle(self):
-        """New permutation, cursor back to this rank's first row (scene_cateogries.py:439-449), and the epoch's tables:
-        per GLOBAL slice of world * R rows the max depth (cnr_slice_maxdepth) and the mask counts + any-class-empty flags
-        (cnr_slice_maskcounts), each entry repeated for the ray ranks that share the slice (the kernels index by their own
-        cursor / R).  All on the device; the only communication is, with class shards, one all-reduce (MAX) of the
-        (slices, 3) empty flags per epoch."""
-        C, ng, w = self.C, self.n_gslices, self.ray_world
-        if self._torch_perm:
-            for cg in range(self.n_cls_global):    # every rank draws every class's permutation: same epoch everywhere
-                p = torch.randperm(self.pool_rows, device=self.device, generator=self._perm_gen)
-                if cg in self.class_ids:
-                    self.perm[self.class_ids.index(cg)].copy_(p)
-            self.d_state2[self.parity, 0:1].copy_(self._cursor0)
-        elif self.ragged:
-            self._ragged_perm()
-        else:
-            # one launch: a keyed bijection per (seed, epoch, GLOBAL class id) -- a rank computes its own classes' orders, every
-            # rank that holds a class gets the same one -- and the cursor of the current state copy back to this rank's first row
-            _C.call("cnr_epoch_perm", self.perm, self.pool_rows, C, self._perm_seed, self._epoch, self._class_ids_dev,
-                    self.d_state2[self.parity], int(self._cursor0_host))
-            self._epoch += 1
-        self.cursor = 0
-        direct = w == 1        # no ray shards: the tables go straight into the buffers the kernels read
-        smax = self.slice_max if direct else torch.empty(C, ng, device=self.device)
-        _C.call("cnr_slice_maxdepth", self.pool["depth"], self.perm, self.pool_rows, C, self.Rg, ng, smax)
-        tab = self.counts_tab if direct else torch.empty(ng, C + 1, 4, device=self.device)
-        _C.call("cnr_slice_maskcounts", self.pool["rgbs"], self.pool["depth"], self.perm, self.pool_rows, C, self.Rg, ng,
-                float(self.cfg.min_depth), tab)
-        if self.shard == "class" and self.pg is not None and self.world > 1:
-            parallel.allreduce_any_(tab[:, C, :3], self.pg)
-        if not direct:
-            self.slice_max.copy_(smax.repeat_interleave(w, dim=1))
-            self.counts_tab.copy_(tab.repeat_interleave(w, dim=0))
-
-    def _ragged_perm(self):
-        """Pools of different lengths.  The reference gives every category its own cursor: class c takes slices of n rows and
-        reshuffles ITS pool when i_batch >= N_c - n (src/scene_cateogries.py:436-449), i.e. after k_c = ceil(N_c / n) - 1 slices.
-        The step's kernels share one device cursor, so the permutation row of class c is laid out as what that class will read
-        over the next K = max_c k_c steps: the rest of its current epoch's order, then as many further epochs of ITS OWN pool
-        (each a keyed bijection of (seed, class epoch, global class id) on [0, N_c): cnr_epoch_perm) as fit.  Where a class is
-        in its epoch carries over to the next call.  Host work per (longest-class) epoch, nothing per step."""
-        Rg = self.Rg
-        K = -(-self.pool_rows // Rg) - 1               # steps until the host reshuffles again (= the longest class's epoch)
-        for c, N in enumerate(self.pool_rows_cls):
-            k_c = -(-N // Rg) - 1                      # slices per epoch of this class
-            row, filled = self.perm[c], 0
-            while filled < K:
-                _C.call("cnr_epoch_perm", self._perm_scratch, N, 1, self._perm_seed, self._cls_epoch[c],
-                        self._class_ids_dev[c:c + 1], None, 0)
-                take = min(k_c - self._cls_slice[c], K - filled)
-                a = self._cls_slice[c] * Rg
-                row[filled * Rg:(filled + take) * Rg].copy_(self._perm_scratch[a:a + take * Rg])
-                filled += take
-                self._cls_slice[c] += take
-                if self._cls_slice[c] == k_c:
-                    self._cls_slice[c], self._cls_epoch[c] = 0, self._cls_epoch[c] + 1
-            row[K * Rg:].zero_()                       # never read (the host reshuffles after K slices); kept in range
-        self.d_state2[self.parity, 0:1].copy_(self._cursor0)
 
     # ---- reference-named export ------------------------------------------------------------------------
     def state_dicts(self, c=0):

@@ -10,6 +10,7 @@ one contiguous buffer and not a call per tensor.  North-star wording ("all-reduc
 gradients only") is a subset: the shared MLP / PE gradients must be in the buffer too, or replicas diverge.
 """
 import os
+import types
 
 import torch
 import torch.distributed as dist
@@ -47,17 +48,6 @@ def shard_pool(pool, rank, world):
     return {k: v[lo:hi].contiguous() for k, v in pool.items()}
 
 
-def allreduce_mean_(flat_grad, group, prescaled=True):
-    """Sum the flat gradient over ranks (one collective).  prescaled: each rank's gradient already carries the
-    1/world factor (the fused trainer folds it into the loss kernel), so the sum IS the mean."""
-    if group is None:
-        return flat_grad
-    dist.all_reduce(flat_grad, op=dist.ReduceOp.SUM, group=group)
-    if not prescaled:
-        flat_grad.div_(dist.get_world_size(group))
-    return flat_grad
-
-
 def allreduce_sum_(flat_grad, group):
     """ONE collective on the flat gradient of all classes: with ray shards every rank's gradient already carries
     1 / (global mask count), so the sum over ranks IS the gradient of the whole batch."""
@@ -79,6 +69,48 @@ def allreduce_any_(flags, group):
 def class_shard(n_cls_global, rank, world):
     """Classes rank ``rank`` owns: ``rank, rank + world, ...`` (classes share nothing: no gradient ever crosses ranks)."""
     return list(range(rank, n_cls_global, world))
+
+
+def shard_plan(process_group, shard, n_cls, R, dp_rank=None, dp_world=None, n_cls_global=None, class_ids=None):
+    """Who trains what in a sharded category step (the two ways: fused.FusedCategoryTrainer), for ``n_cls`` LOCAL classes of ``R``
+    rays per step on this rank: world, rank, shard, ray_world / ray_rank (the ranks that share one class's rays, and this one
+    among them), Rg (rows of a global slice), n_cls_global, class_ids (global ids of the local classes), rng_map.  (dp_rank /
+    dp_world without a process group: one rank of a sharded world, the exchange left to the caller -- tests emulate ranks so.)"""
+    p = types.SimpleNamespace()
+    p.world = int(dp_world) if dp_world is not None else 1 if process_group is None else dist.get_world_size(process_group)
+    p.rank = int(dp_rank) if dp_rank is not None else 0 if process_group is None else dist.get_rank(process_group)
+    p.shard = shard if shard is not None else ("ray" if p.world > 1 else None)
+    assert p.shard in (None, "ray", "class")
+    p.ray_world, p.ray_rank = (p.world, p.rank) if p.shard == "ray" else (1, 0)
+    p.Rg = R * p.ray_world
+    if p.shard == "class":
+        p.n_cls_global = int(n_cls_global) if n_cls_global is not None else n_cls * p.world
+        p.class_ids = list(class_ids) if class_ids is not None else class_shard(p.n_cls_global, p.rank, p.world)
+        assert len(p.class_ids) == n_cls
+    else:
+        p.n_cls_global, p.class_ids = n_cls, list(range(n_cls))
+    # rng_map = (first global class, class stride, global rays per class, first ray of this rank): the Philox counter of a ray
+    # is its index in the GLOBAL batch, so shards draw what a single GPU would (include/cnr_hip.h, cnr_step_prologue).
+    # Irregular class ownership: local indices (still a valid stream, just not the single-GPU one)
+    ids = p.class_ids
+    stride = ids[1] - ids[0] if len(ids) > 1 else 1
+    p.rng_map = (0, 0, 0, 0)
+    if p.shard == "class" and all(ids[k] == ids[0] + k * stride for k in range(len(ids))):
+        p.rng_map = (ids[0], stride, R, 0)
+    elif p.shard == "ray":
+        p.rng_map = (0, 1, p.Rg, p.ray_rank * R)
+    return p
+
+
+def check_same_epochs(pool_rows, Rg, group, world, device):
+    """Class shards OR their empty flags in a collective at every reshuffle, so all ranks must reshuffle in the same steps: the same
+    pool length and rays per step.  Checked when the trainer is built: a message instead of a hang at the first epoch end."""
+    mine = torch.tensor([pool_rows, Rg], dtype=torch.int64, device=device if dist.get_backend(group) == "nccl" else "cpu")
+    every = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(every, mine, group=group)
+    every = [tuple(int(v) for v in t.tolist()) for t in every]
+    if len(set(every)) != 1:
+        raise ValueError(f"class shards need the same pool length and rays per step on every rank, got (pool_rows, rays) = {every}")
 
 
 def params_in_sync(flat_params, group, atol=0.0):

@@ -28,14 +28,13 @@ torch.cuda.synchronize()
 res = {"inside": [], "clear": []}
 for rep in range(12):
     for name, kk in (("inside", k), ("clear", 40)):
-        left = -(-(tr.pool_rows - tr.Rg - tr.cursor) // tr.Rg)
+        left = tr.pool.steps_left()
         while left != kk:          # walk to kk steps in front of the epoch end
             tr.run(1)
-            left = -(-(tr.pool_rows - tr.Rg - tr.cursor) // tr.Rg)
+            left = tr.pool.steps_left()
             if left <= 0:
                 tr.run(1)
-                left = -(-(tr.pool_rows - tr.Rg - tr.cursor) // tr.Rg)
-        tr.run(20 if name == "clear" else 0) if False else None
+                left = tr.pool.steps_left()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         tr.run(20)
