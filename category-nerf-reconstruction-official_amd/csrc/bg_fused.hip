@@ -467,8 +467,7 @@ __global__ __launch_bounds__(256, 2) void bg_bwd_kernel(BgBwdArgs a) {
     // is composited by both; the tile that holds its FIRST sample accounts for its renders and loss terms.
     const int S = a.S;
     const float* t = a.counts_tab + (size_t)(a.cursor ? a.cursor[0] / a.R : 0) * 8;      // (slices, C + 1 = 2, 4), C = 1
-    const float wd = t[4] != 0.f ? 0.f : 1.0f / (t[0] + 1e-10f), wc = t[5] != 0.f ? 0.f : 1.0f / (t[1] + 1e-10f),
-                wo = t[6] != 0.f ? 0.f : 1.0f / (t[2] + 1e-10f);
+    const cnr_rl::MaskWeights mw = cnr_rl::mask_weights(t[0], t[1], t[2], t[4] != 0.f, t[5] != 0.f, t[6] != 0.f);
     if (threadIdx.x < TS) {   // columns 3..15 of the out_color image, rows beyond M, sample positions
       const int s = threadIdx.x, m = m0 + s;
       _Float16* o = reinterpret_cast<_Float16*>(OCimg + s * ST_OC);
@@ -485,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void bg_bwd_kernel(BgBwdArgs a) {
       const size_t base = (size_t)ray * S;
       const cnr_rl::RayOut q = cnr_rl::ray_small(a.sigma, a.rgb, a.z, base, S, lane, a.gt_depth[ray], a.gt_rgb[ray * 3 + 0],
                                                  a.gt_rgb[ray * 3 + 1], a.gt_rgb[ray * 3 + 2], a.labels[ray], a.depth_mask[ray],
-                                                 wd, wc, wo, a.color_scaling, a.opacity_scaling, a.grad_scale);
+                                                 mw.wd, mw.wc, mw.wo, a.color_scaling, a.opacity_scaling, a.grad_scale);
       const bool owner = (int64_t)base >= m0;                  // the ray's first sample lies in this tile
       if (owner) {
         ld += q.ld; lc += q.lc; lo += q.lo;
@@ -510,8 +509,7 @@ __global__ __launch_bounds__(256, 2) void bg_bwd_kernel(BgBwdArgs a) {
     if (lane == 0) { lsum[3 * w + 0] = ld; lsum[3 * w + 1] = lc; lsum[3 * w + 2] = lo; }
     if (blockIdx.x == 0 && threadIdx.x == 0) {   // the normalisers and the empty-mask bits (cnr_rl::finish_class reads them)
       float* hdr = a.rl_partials + (size_t)gridDim.x * 3;
-      hdr[0] = wd; hdr[1] = wc; hdr[2] = wo;
-      hdr[3] = (float)((t[4] != 0.f ? 2 : 0) | (t[5] != 0.f ? 4 : 0) | (t[6] != 0.f ? 8 : 0));
+      hdr[0] = mw.wd; hdr[1] = mw.wc; hdr[2] = mw.wo; hdr[3] = (float)cnr_rl::mask_flags(t[4] != 0.f, t[5] != 0.f, t[6] != 0.f);
     }
   } else if (threadIdx.x < TS) {
     // ---- upstream: dPre of out_color = d rgb * rgb (1 - rgb); 10 x d sigma; sample positions ----------------------------

@@ -326,9 +326,8 @@ __global__ __launch_bounds__(256) void mask_counts_kernel(const uint8_t* __restr
   const int c = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float a = 0.f, b = 0.f, d = 0.f;
   for (int r = threadIdx.x; r < R; r += 256) {
-    const uint8_t lab = labels[(size_t)c * R + r];
-    const bool mo = lab != 0, ms = lab != 2, md = depth_mask[(size_t)c * R + r] != 0;
-    a += (md && mo) ? 1.f : 0.f; b += mo ? 1.f : 0.f; d += ms ? 1.f : 0.f;
+    const cnr_rl::MaskBits m = cnr_rl::mask_bits(labels[(size_t)c * R + r], depth_mask[(size_t)c * R + r] != 0);
+    a += m.md ? 1.f : 0.f; b += m.mo ? 1.f : 0.f; d += m.ms ? 1.f : 0.f;
   }
   a = cnr::wave_sum(a); b = cnr::wave_sum(b); d = cnr::wave_sum(d);
   if (lane == 0) { cnt[wv] = a; cnt[4 + wv] = b; cnt[8 + wv] = d; }
@@ -342,9 +341,10 @@ __global__ __launch_bounds__(256) void mask_counts_kernel(const uint8_t* __restr
 // registers (cnr_field_fwd + cnr_render_loss write and re-read 16 B per sample between two launches).  A wave owns
 // whole rays: K = S / 32 consecutive tiles, lane (half 0) = sample; the exclusive-cumprod runs as a 32-lane scan per
 // tile with the transmittance carried from tile to tile, the backward's suffix sums the other way.  The forward, the
-// losses and their gradients are render_loss.hip's expressions; sums over lanes run over 32-lane tiles instead of 64-lane
+// losses and their gradients are render_loss.hip's expressions (render_common.h: ray_forward, ray_loss), the masks and the
+// weights its very functions (mask_bits, mask_weights); sums over lanes run over 32-lane tiles instead of 64-lane
 // chunks, so those agree to summation order, not bitwise.  The composite BACKWARD is fp32 throughout here, with the
-// exclusive suffix sum as (inclusive - own term): render_loss.hip and composite.hip take it from the next lane and form
+// exclusive suffix sum as (inclusive - own term): render_common.h's ray_backward takes it from the next lane and forms
 // g, the sum and d occ in double.  With alpha as input, the only input here, occ (1 - occ) takes the 1 / f back, so the two
 // differ by an ulp of term_i g_i per sample -- below this path's f16 operand error by orders of magnitude.  grid (blocks, C); block b of class c writes loss partial (c, b) -- nb = gridDim.x for
 // finish_class.
@@ -406,9 +406,8 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
         if (i / nw != cc || lw[i] == 0xffffffffu) continue;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const unsigned int lab = (lw[i] >> (8 * j)) & 0xffu, dm = (mw[i] >> (8 * j)) & 0xffu;
-          const bool mo = lab != 0, ms = lab != 2, md = dm != 0;
-          a += (md && mo) ? 1.f : 0.f; b += mo ? 1.f : 0.f; d += ms ? 1.f : 0.f;
+          const cnr_rl::MaskBits m = cnr_rl::mask_bits((lw[i] >> (8 * j)) & 0xffu, ((mw[i] >> (8 * j)) & 0xffu) != 0);
+          a += m.md ? 1.f : 0.f; b += m.mo ? 1.f : 0.f; d += m.ms ? 1.f : 0.f;
         }
       }
       a = cnr::wave_sum(a); b = cnr::wave_sum(b); d = cnr::wave_sum(d);  // counts: exact in fp32 in any order
@@ -439,9 +438,8 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
     for (int cc = 0; cc < C; ++cc) {
       float a = 0.f, b = 0.f, d = 0.f;
       for (int r = threadIdx.x; r < R; r += 256) {
-        const uint8_t lab = labels[(size_t)cc * R + r];
-        const bool mo = lab != 0, ms = lab != 2, md = depth_mask[(size_t)cc * R + r] != 0;
-        a += (md && mo) ? 1.f : 0.f; b += mo ? 1.f : 0.f; d += ms ? 1.f : 0.f;
+        const cnr_rl::MaskBits m = cnr_rl::mask_bits(labels[(size_t)cc * R + r], depth_mask[(size_t)cc * R + r] != 0);
+        a += m.md ? 1.f : 0.f; b += m.mo ? 1.f : 0.f; d += m.ms ? 1.f : 0.f;
       }
       a = cnr::wave_sum(a); b = cnr::wave_sum(b); d = cnr::wave_sum(d);
       __syncthreads();
@@ -455,9 +453,7 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
     __syncthreads();
   }
   FR_T(2);
-  const float wd = empty_d ? 0.f : 1.0f / (nd + 1e-10f);
-  const float wc = empty_c ? 0.f : 1.0f / (nc + 1e-10f);
-  const float wo = empty_o ? 0.f : 1.0f / (no + 1e-10f);
+  const cnr_rl::MaskWeights wts = cnr_rl::mask_weights(nd, nc, no, empty_d, empty_c, empty_o);
   const float* cf = reinterpret_cast<const float*>(smem + PK_OFF_CONST);
   float Bh[33];
   {
@@ -522,10 +518,11 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
       if (opacity_out) opacity_out[ray] = so;
       if (rgb_out) { rgb_out[ray * 3 + 0] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
     }
-    // ---- losses of this ray and their gradients w.r.t. its renders (loss.hip, same expressions) --------------------
-    const uint8_t lab = labels[ray];
-    const bool mo = lab != 0, ms = lab != 2, md = (depth_mask[ray] != 0) && mo;
-    const float fd = md ? 1.f : 0.f, fo = mo ? 1.f : 0.f, fs = ms ? 1.f : 0.f;
+    // ---- losses of this ray and their gradients w.r.t. its renders: cnr_rl::ray_loss's expressions, written out.  This unit
+    // contracts multiply-adds, and the fp32 backward below adds products of these gradients: which of two products the compiler
+    // fuses into such a sum depends on the flags of the multiplies that formed them, so the text stays in the kernel.
+    const cnr_rl::MaskBits m = cnr_rl::mask_bits(labels[ray], depth_mask[ray] != 0);
+    const float fd = m.md ? 1.f : 0.f, fo = m.mo ? 1.f : 0.f, fs = m.ms ? 1.f : 0.f;
     const float rd = sd - gt_depth[ray];
     const float info = 1.0f / (sqrtf(sv) + 1e-4f);
     const float rc0 = sr - gt_rgb[ray * 3 + 0], rc1 = sg - gt_rgb[ray * 3 + 1], rc2 = sb - gt_rgb[ray * 3 + 2];
@@ -533,11 +530,11 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
     ld += fabsf(rd) * fd * info;
     lc += (fabsf(rc0) + fabsf(rc1) + fabsf(rc2)) * fo;
     lo += fabsf(ro) * fs;
-    const float dD = grad_scale * sgn(rd) * fd * info * wd;
-    const float dR = grad_scale * color_scaling * sgn(rc0) * fo * wc;
-    const float dG = grad_scale * color_scaling * sgn(rc1) * fo * wc;
-    const float dBl = grad_scale * color_scaling * sgn(rc2) * fo * wc;
-    const float dO = grad_scale * opacity_scaling * sgn(ro) * fs * wo;
+    const float dD = grad_scale * sgn(rd) * fd * info * wts.wd;
+    const float dR = grad_scale * color_scaling * sgn(rc0) * fo * wts.wc;
+    const float dG = grad_scale * color_scaling * sgn(rc1) * fo * wts.wc;
+    const float dBl = grad_scale * color_scaling * sgn(rc2) * fo * wts.wc;
+    const float dO = grad_scale * opacity_scaling * sgn(ro) * fs * wts.wo;
     // ---- composite backward, last tile first, suffix sum carried across tiles ---------------------------------------
     float suf_carry = 0.0f;
 #pragma unroll
@@ -569,8 +566,7 @@ __global__ __launch_bounds__(256, 2) void field_fwd_render_kernel(
         (cnt[threadIdx.x * 4] + cnt[threadIdx.x * 4 + 1]) + (cnt[threadIdx.x * 4 + 2] + cnt[threadIdx.x * 4 + 3]);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     float* hdr = partials + (size_t)C * nb * 3 + (size_t)c * 4;
-    hdr[0] = wd; hdr[1] = wc; hdr[2] = wo;
-    hdr[3] = (float)((empty_d ? 2 : 0) | (empty_c ? 4 : 0) | (empty_o ? 8 : 0));
+    hdr[0] = wts.wd; hdr[1] = wts.wc; hdr[2] = wts.wo; hdr[3] = (float)cnr_rl::mask_flags(empty_d, empty_c, empty_o);
   }
 }
 }  // namespace

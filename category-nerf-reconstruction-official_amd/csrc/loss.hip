@@ -7,8 +7,10 @@
 //   - "loss explode" (render_rays.py:87-89, exit(-1) there) is reported in flags[c] bit 0.
 // One 256-thread block per class.
 #include "adamw_common.h"
+#include "render_common.h"
 
 namespace {
+using namespace cnr_rl;
 __device__ __forceinline__ float block_sum(float v, float* sm /*[4]*/) {
   v = cnr::wave_sum(v);
   __syncthreads();
@@ -16,7 +18,6 @@ __device__ __forceinline__ float block_sum(float v, float* sm /*[4]*/) {
   __syncthreads();
   return sm[0] + sm[1] + sm[2] + sm[3];
 }
-__device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
 __global__ __launch_bounds__(256) void loss_kernel(
     const float* __restrict__ depth, const float* __restrict__ var, const float* __restrict__ rgb,
@@ -32,49 +33,30 @@ __global__ __launch_bounds__(256) void loss_kernel(
   for (int cc = 0; cc < C; ++cc) {
     float a = 0.f, b = 0.f, d = 0.f;
     for (int r = threadIdx.x; r < R; r += 256) {
-      const uint8_t lab = labels[(size_t)cc * R + r];
-      const bool mo = lab != 0, ms = lab != 2, md = depth_mask[(size_t)cc * R + r] != 0;
-      a += (md && mo) ? 1.f : 0.f; b += mo ? 1.f : 0.f; d += ms ? 1.f : 0.f;
+      const MaskBits m = mask_bits(labels[(size_t)cc * R + r], depth_mask[(size_t)cc * R + r] != 0);
+      a += m.md ? 1.f : 0.f; b += m.mo ? 1.f : 0.f; d += m.ms ? 1.f : 0.f;
     }
     a = block_sum(a, sm); b = block_sum(b, sm); d = block_sum(d, sm);
     empty_d |= (a == 0.f); empty_c |= (b == 0.f); empty_o |= (d == 0.f);
     if (cc == c) { nd = a; nc = b; no = d; }
   }
-  const float wd = empty_d ? 0.f : 1.0f / (nd + 1e-10f);
-  const float wc = empty_c ? 0.f : 1.0f / (nc + 1e-10f);
-  const float wo = empty_o ? 0.f : 1.0f / (no + 1e-10f);
-  // ---- per-ray residuals, gradients ------------------------------------------------------------
+  const MaskWeights mw = mask_weights(nd, nc, no, empty_d, empty_c, empty_o);
+  // ---- per-ray residuals, gradients (render_common.h; the terms are accumulated here, in this file's contraction mode) ----
   float ld = 0.f, lc = 0.f, lo = 0.f;
   for (int r = threadIdx.x; r < R; r += 256) {
     const size_t i = (size_t)c * R + r;
-    const uint8_t lab = labels[i];
-    const bool mo = lab != 0, ms = lab != 2, md = (depth_mask[i] != 0) && mo;
-    const float rd = depth[i] - gt_depth[i];
-    const float info = 1.0f / (sqrtf(var[i]) + 1e-4f);
-    const float fd = md ? 1.f : 0.f, fo = mo ? 1.f : 0.f, fs = ms ? 1.f : 0.f;
-    ld += fabsf(rd) * fd * info;
-    d_depth[i] = grad_scale * sgn(rd) * fd * info * wd;
-    float cs = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float rc = rgb[i * 3 + k] - gt_rgb[i * 3 + k];
-      cs += fabsf(rc);
-      d_rgb[i * 3 + k] = grad_scale * color_scaling * sgn(rc) * fo * wc;
-    }
-    lc += cs * fo;
-    const float ro = opacity[i] - fo;
-    lo += fabsf(ro) * fs;
-    d_opacity[i] = grad_scale * opacity_scaling * sgn(ro) * fs * wo;
+    const Renders q{depth[i], var[i], opacity[i], rgb[i * 3 + 0], rgb[i * 3 + 1], rgb[i * 3 + 2]};
+    const RayLoss l = ray_loss(q, gt_depth[i], gt_rgb[i * 3 + 0], gt_rgb[i * 3 + 1], gt_rgb[i * 3 + 2], labels[i],
+                               depth_mask[i] != 0, mw.wd, mw.wc, mw.wo, color_scaling, opacity_scaling, grad_scale);
+    ld += l.ad * l.info; lc += l.ac * l.fo; lo += l.ao * l.fs;
+    d_depth[i] = l.dD;
+    d_rgb[i * 3 + 0] = l.dR; d_rgb[i * 3 + 1] = l.dG; d_rgb[i * 3 + 2] = l.dBl;
+    d_opacity[i] = l.dO;
   }
-  ld = block_sum(ld, sm) * wd; lc = block_sum(lc, sm) * wc; lo = block_sum(lo, sm) * wo;
+  ld = block_sum(ld, sm) * mw.wd; lc = block_sum(lc, sm) * mw.wc; lo = block_sum(lo, sm) * mw.wo;
   if (threadIdx.x == 0) {
     losses[0 * C + c] = ld; losses[1 * C + c] = lc; losses[2 * C + c] = lo;
-    int32_t fl = 0;
-    if (ld > 100000.f || lc > 100000.f || lo > 100000.f) fl |= 1;
-    if (empty_d) fl |= 2;
-    if (empty_c) fl |= 4;
-    if (empty_o) fl |= 8;
-    flags[c] = fl;
+    flags[c] = mask_flags(empty_d, empty_c, empty_o) | ((ld > 100000.f || lc > 100000.f || lo > 100000.f) ? 1 : 0);
   }
 }
 

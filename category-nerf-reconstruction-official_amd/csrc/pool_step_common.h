@@ -66,8 +66,8 @@ __device__ __forceinline__ RowStats select_rows(const StepArgs& a, float* red, c
       const float d = depth[row];
       const uint8_t lab = rgbs[row * 4 + 3];
       mx = fmaxf(mx, d);
-      const bool mo = lab != 0, ms = lab != 2, md = d > a.min_bound;
-      c_d += (md && mo) ? 1 : 0; c_o += mo ? 1 : 0; c_s += ms ? 1 : 0;
+      const cnr_rl::MaskBits m = cnr_rl::mask_bits(lab, d > a.min_bound);
+      c_d += m.md ? 1 : 0; c_o += m.mo ? 1 : 0; c_s += m.ms ? 1 : 0;
     }
     mx = cnr::wave_max(mx);
     for (int off = 32; off > 0; off >>= 1) {
@@ -85,14 +85,9 @@ __device__ __forceinline__ RowStats select_rows(const StepArgs& a, float* red, c
     n_bad += red[32 + i];
   }
   // a zero mask count zeroes that term and its gradient (render_rays.py:67-72 with one class), flags as cnr_render_loss's
-  RowStats rs;
-  rs.mb = mb;
-  rs.wd = n_d == 0.f ? 0.f : 1.0f / (n_d + 1e-10f);
-  rs.wc = n_o == 0.f ? 0.f : 1.0f / (n_o + 1e-10f);
-  rs.wo = n_s == 0.f ? 0.f : 1.0f / (n_s + 1e-10f);
-  rs.flag = (n_d == 0.f ? 2 : 0) | (n_o == 0.f ? 4 : 0) | (n_s == 0.f ? 8 : 0) | (n_bad != 0.f ? 32 : 0);
+  const cnr_rl::MaskWeights mw = cnr_rl::mask_weights(n_d, n_o, n_s, n_d == 0.f, n_o == 0.f, n_s == 0.f);
   __syncthreads();      // (RED is reused by the caller)
-  return rs;
+  return {mb, mw.wd, mw.wc, mw.wo, cnr_rl::mask_flags(n_d == 0.f, n_o == 0.f, n_s == 0.f) | (n_bad != 0.f ? 32 : 0)};
 }
 
 // a2-a5 of owner o's R rays into its workspace, one wave per ray (sample_common.h; z without fused multiply-adds: the

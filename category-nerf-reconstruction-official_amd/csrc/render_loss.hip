@@ -11,15 +11,14 @@
 // finishes" ticket inside the main kernel was measured 3x slower than three separate launches: the agent-scope
 // release fence it needs writes the 8 XCD L2s back once per wave.)
 //
-// Same arithmetic, expression for expression, as composite.hip + loss.hip (the modular path): d sigma / d colour
-// are bit-identical to cnr_composite_fwd -> cnr_loss_fwd_bwd -> cnr_composite_bwd, the loss values agree to
+// The arithmetic is render_common.h's, the very functions composite.hip + loss.hip (the modular path) call: d sigma /
+// d colour are bit-identical to cnr_composite_fwd -> cnr_loss_fwd_bwd -> cnr_composite_bwd, the loss values agree to
 // summation order.  Block = 16 waves, one ray per wave at a time.
 #include "adamw_common.h"
 #include "render_common.h"
 
-// no fused multiply-add contraction in this file: composite.hip and render_loss.hip evaluate the same expressions and
-// must round them the same way whatever the surrounding code looks like (the one-launch form is tested bitwise
-// against the three-call form)
+// no fused multiply-add contraction in this file: the loss terms are accumulated here as ray_small accumulates them (the
+// one-launch form is tested bitwise against the three-call form)
 #pragma clang fp contract(off)
 
 namespace {
@@ -47,9 +46,8 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
   for (int cc = 0; cc < (counts_tab ? 0 : C); ++cc) {
     float a = 0.f, b = 0.f, d = 0.f;
     for (int r = threadIdx.x; r < R; r += RL_THREADS) {
-      const uint8_t lab = labels[(size_t)cc * R + r];
-      const bool mo = lab != 0, ms = lab != 2, md = depth_mask[(size_t)cc * R + r] != 0;
-      a += (md && mo) ? 1.f : 0.f; b += mo ? 1.f : 0.f; d += ms ? 1.f : 0.f;
+      const MaskBits m = mask_bits(labels[(size_t)cc * R + r], depth_mask[(size_t)cc * R + r] != 0);
+      a += m.md ? 1.f : 0.f; b += m.mo ? 1.f : 0.f; d += m.ms ? 1.f : 0.f;
     }
     a = cnr::wave_sum(a); b = cnr::wave_sum(b); d = cnr::wave_sum(d);
     __syncthreads();
@@ -61,9 +59,7 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
     empty_d |= (a == 0.f); empty_c |= (b == 0.f); empty_o |= (d == 0.f);
     if (cc == c) { nd = a; nc = b; no = d; }
   }
-  const float wd = empty_d ? 0.f : 1.0f / (nd + 1e-10f);
-  const float wc = empty_c ? 0.f : 1.0f / (nc + 1e-10f);
-  const float wo = empty_o ? 0.f : 1.0f / (no + 1e-10f);
+  const MaskWeights mw = mask_weights(nd, nc, no, empty_d, empty_c, empty_o);
 
   const int nchunk = (S + 63) / 64;
   float ld = 0.f, lc = 0.f, lo = 0.f;  // this wave's loss partials (lane 0)
@@ -75,7 +71,7 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
     if (nchunk == 1) {
       // ---- S <= 64: the whole ray sits in one register per lane; sigmoid, scan and loads happen once (render_common.h) --
       const RayOut q = ray_small(sigmas, colors, z, base, S, lane, gt_depth[ray], gt_rgb[ray * 3 + 0], gt_rgb[ray * 3 + 1],
-                                 gt_rgb[ray * 3 + 2], labels[ray], depth_mask[ray], wd, wc, wo, color_scaling, opacity_scaling,
+                                 gt_rgb[ray * 3 + 2], labels[ray], depth_mask[ray], mw.wd, mw.wc, mw.wo, color_scaling, opacity_scaling,
                                  grad_scale);
       if (lane == 0) {
         if (depth_out) depth_out[ray] = q.sd;
@@ -91,93 +87,19 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
       }
       continue;
     }
-    // ---- forward composite ----------------------------------------------------------------------------------
+    // ---- S > 64: forward composite, the ray's loss terms and their gradients, backward composite (render_common.h) ----------
     float carry_in[RL_MAX_CHUNKS];
-    float carry = 1.0f;
-    float sd = 0.f, so = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
-    for (int ch = 0; ch < nchunk; ++ch) {
-      carry_in[ch] = carry;
-      const int s = ch * 64 + lane;
-      const bool live = s < S;
-      const float occ = live ? sigmoid_exact(sigmas[base + s]) : 0.0f;
-      const float f = live ? (1.0f - occ + 1e-10f) : 1.0f;
-      const float incl = incl_prod(f, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      const float term = occ * (carry * excl);
-      if (live) {
-        const float zz = z[base + s];
-        const float* cp = colors + (base + s) * 3;
-        sd += term * zz; so += term;
-        sr += term * cp[0]; sg += term * cp[1]; sb += term * cp[2];
-      }
-      carry *= __shfl(incl, 63, 64);
-    }
-    sd = cnr::wave_sum(sd); so = cnr::wave_sum(so);
-    sr = cnr::wave_sum(sr); sg = cnr::wave_sum(sg); sb = cnr::wave_sum(sb);
-    float sv = 0.f;  // var = sum term (z - depth)^2 (two-pass form, as the reference)
-    for (int ch = 0; ch < nchunk; ++ch) {
-      const int s = ch * 64 + lane;
-      const bool live = s < S;
-      const float occ = live ? sigmoid_exact(sigmas[base + s]) : 0.0f;
-      const float f = live ? (1.0f - occ + 1e-10f) : 1.0f;
-      const float incl = incl_prod(f, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      if (live) { const float dz = z[base + s] - sd; sv += occ * carry_in[ch] * excl * dz * dz; }
-    }
-    sv = cnr::wave_sum(sv);
+    const Renders q = ray_forward<true>(sigmas, colors, z, nullptr, base, S, 0, lane, carry_in);
     if (lane == 0) {
-      if (depth_out) depth_out[ray] = sd;
-      if (var_out) var_out[ray] = sv;
-      if (opacity_out) opacity_out[ray] = so;
-      if (rgb_out) { rgb_out[ray * 3 + 0] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
+      if (depth_out) depth_out[ray] = q.sd;
+      if (var_out) var_out[ray] = q.sv;
+      if (opacity_out) opacity_out[ray] = q.so;
+      if (rgb_out) { rgb_out[ray * 3 + 0] = q.sr; rgb_out[ray * 3 + 1] = q.sg; rgb_out[ray * 3 + 2] = q.sb; }
     }
-    // ---- losses of this ray and their gradients w.r.t. its renders (loss.hip, same expressions) -----------------------
-    const uint8_t lab = labels[ray];
-    const bool mo = lab != 0, ms = lab != 2, md = (depth_mask[ray] != 0) && mo;
-    const float fd = md ? 1.f : 0.f, fo = mo ? 1.f : 0.f, fs = ms ? 1.f : 0.f;
-    const float rd = sd - gt_depth[ray];
-    const float info = 1.0f / (sqrtf(sv) + 1e-4f);
-    const float rc0 = sr - gt_rgb[ray * 3 + 0], rc1 = sg - gt_rgb[ray * 3 + 1], rc2 = sb - gt_rgb[ray * 3 + 2];
-    const float ro = so - fo;
-    ld += fabsf(rd) * fd * info;
-    lc += (fabsf(rc0) + fabsf(rc1) + fabsf(rc2)) * fo;
-    lo += fabsf(ro) * fs;
-    const float dD = grad_scale * sgn(rd) * fd * info * wd;
-    const float dR = grad_scale * color_scaling * sgn(rc0) * fo * wc;
-    const float dG = grad_scale * color_scaling * sgn(rc1) * fo * wc;
-    const float dBl = grad_scale * color_scaling * sgn(rc2) * fo * wc;
-    const float dO = grad_scale * opacity_scaling * sgn(ro) * fs * wo;
-    // ---- backward composite (back to front, suffix sum carried across chunks) ------------------------------------
-    double suf_carry = 0.0;
-    for (int ch = nchunk - 1; ch >= 0; --ch) {
-      const int s = ch * 64 + lane;
-      const bool live = s < S;
-      const float occ = live ? sigmoid_exact(sigmas[base + s]) : 0.0f;
-      const float f = live ? (1.0f - occ + 1e-10f) : 1.0f;
-      const float incl = incl_prod(f, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      const float T = carry_in[ch] * excl;
-      const float term = occ * T;
-      double g = 0.0;  // g, the suffix sum and d occ in double, as composite.hip
-      if (live) {
-        const float* cp = colors + (base + s) * 3;
-        g = (double)dD * (double)z[base + s] + (double)dR * (double)cp[0] + (double)dG * (double)cp[1] +
-            (double)dBl * (double)cp[2] + (double)dO;
-      }
-      const double tg = (double)term * g;
-      const double incl_suf = incl_suffix_sum(tg, lane);
-      const double suf = excl_suffix(incl_suf, lane) + suf_carry;
-      if (live) {
-        const double docc = (double)T * g - suf / (double)f;
-        d_sigmas[base + s] = (float)(docc * (double)occ * (1.0 - (double)occ));
-        float* dc = d_colors + (base + s) * 3;
-        dc[0] = term * dR; dc[1] = term * dG; dc[2] = term * dBl;
-      }
-      suf_carry += __shfl(incl_suf, 0, 64);
-    }
+    const RayLoss l = ray_loss(q, gt_depth[ray], gt_rgb[ray * 3 + 0], gt_rgb[ray * 3 + 1], gt_rgb[ray * 3 + 2], labels[ray],
+                               depth_mask[ray] != 0, mw.wd, mw.wc, mw.wo, color_scaling, opacity_scaling, grad_scale);
+    ld += l.ad * l.info; lc += l.ac * l.fo; lo += l.ao * l.fs;
+    ray_backward(sigmas, colors, z, nullptr, l.dD, l.dR, l.dG, l.dBl, l.dO, d_sigmas, d_colors, base, S, 0, lane, carry_in);
   }
   // ---- loss values: block partials, summed in block order by the last block to finish --------------------------------
   if (lane == 0) { wsum[wv] = ld; wsum[RL_WAVES + wv] = lc; wsum[2 * RL_WAVES + wv] = lo; }
@@ -191,8 +113,7 @@ __global__ __launch_bounds__(RL_THREADS) void render_loss_kernel(
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // the normalisers and the empty-mask bits, for the finish kernel
     float* hdr = partials + (size_t)C * nb * 3 + (size_t)c * 4;
-    hdr[0] = wd; hdr[1] = wc; hdr[2] = wo;
-    hdr[3] = (float)((empty_d ? 2 : 0) | (empty_c ? 4 : 0) | (empty_o ? 8 : 0));
+    hdr[0] = mw.wd; hdr[1] = mw.wc; hdr[2] = mw.wo; hdr[3] = (float)mask_flags(empty_d, empty_c, empty_o);
   }
 }
 

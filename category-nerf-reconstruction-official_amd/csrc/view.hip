@@ -14,6 +14,7 @@
 // no fused multiply-add contraction) so that they agree on every hit.
 #include "cnr_common.h"
 #include "geom_common.h"
+#include "render_common.h"
 
 #pragma clang fp contract(off)
 
@@ -359,8 +360,6 @@ __global__ __launch_bounds__(256) void scatter_active_kernel(const float* __rest
   color[idx * 3 + 0] = color_c[j * 3 + 0]; color[idx * 3 + 1] = color_c[j * 3 + 1]; color[idx * 3 + 2] = color_c[j * 3 + 2];
 }
 
-__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // the number of elements of the ascending run zs[0..S) that are < v (strict) or <= v
 __device__ __forceinline__ int count_below(const float* zs, int S, float v, bool or_equal) {
   int lo = 0, hi = S;
@@ -408,7 +407,7 @@ __global__ __launch_bounds__(64) void composite_kernel(const float* __restrict__
     for (int j = 1; j < KMAX; ++j) if (j == k) sg = segs[j];
     const int64_t g = (int64_t)sg * S + i;
     zin[idx] = z[g];
-    occ[idx] = sigmoid_exact(sigma[g]);
+    occ[idx] = cnr_rl::sigmoid_exact(sigma[g]);
   }
   __syncthreads();
   // merged rank by (z, segment, sample): own index plus a binary search in every other segment

@@ -313,7 +313,7 @@ def composite_bwd_case(NR, S, in_is_occ, regime, upstream="all"):
 
 
 def composite_closed_form(alpha, color, z, dd, dr, do, dt, in_is_occ):
-    """numpy float64 evaluation of the closed form in csrc/composite.hip's header comment -> d_alpha (NR, S):
+    """numpy float64 evaluation of the closed form in csrc/render_common.h's comment on the ray compositor -> d_alpha (NR, S):
     d occ_i = T_i g_i - Suf_i / f_i with g_i = dD z_i + dC.c_i + dO + d_term_i and Suf_i = sum_{k>i} term_k g_k"""
     n = lambda t: None if t is None else t.detach().double().numpy()
     a, c, zz, dd, dr, do, dt = n(alpha), n(color), n(z), n(dd), n(dr), n(do), n(dt)

@@ -239,7 +239,9 @@ def test_full_size_against_oracle_and_properties(cnr, dev, C, R, S, L):
 
 @pytest.mark.parametrize("C,R,S,empty", [(1, 2048, 64, False), (2, 300, 16, False), (3, 130, 200, False),
                                         (2, 257, 64, True), (1, 9, 65, False), (2, 5, 129, False),
-                                        (1, 5, 512, False)])
+                                        (1, 5, 512, False),
+                                        # one sample; one lane short of a chunk; exactly two full chunks; seven chunks
+                                        (1, 3, 1, False), (1, 4, 63, False), (2, 3, 128, False), (2, 2, 448, True)])
 def test_render_loss_single_launch_equals_three_calls(cnr, dev, C, R, S, empty):
     """cnr_render_loss == cnr_composite_fwd -> cnr_loss_fwd_bwd -> cnr_composite_bwd: gradients and renders
     bit-identical (same expressions), loss values to fp32 summation order, flags equal; a second launch on
