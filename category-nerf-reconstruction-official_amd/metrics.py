@@ -9,6 +9,9 @@ samples, accuracy / completion in cm and the completion ratio at 5 cm in %; the 
 csrc/point_mesh.hip), and ``calc_3d_metric_surface`` the same score with every distance taken to the other
 mesh instead of to samples of it, plus precision / recall / F-score and normal consistency.  ``MeshIndex`` (opt-in,
 csrc/point_mesh_index.hip) answers the same queries bit for bit through a tile-box index that skips most of the mesh.
+``winding_number`` is the generalized winding number of a mesh about arbitrary points (``cnr_winding_number``,
+csrc/winding.hip), on which ``inside``, ``signed_distance`` and ``volume_iou`` rest; ``mesh_orientation``
+tells whether a mesh's normals point outward.  The reference has none of these.
 
 Differences from the reference, all deliberate:
 * the ground truth is an argument (``mesh_gt``, default ``mesh_ref``); the reference reads a module-level ``mesh_gt`` and uses
@@ -25,7 +28,8 @@ from .devmesh import DeviceMesh, device_mesh, require_finite
 
 __all__ = ["accuracy", "completion", "accuracy_ratio", "completion_ratio", "chamfer", "nn_dist", "dist_stats",
            "sample_surface", "oriented_bounds", "box_planes", "slice_box", "calc_3d_metric", "depth_l1", "depth_l1_images",
-           "point_mesh_distance", "sample_surface_faces", "calc_3d_metric_surface", "MeshIndex"]
+           "point_mesh_distance", "sample_surface_faces", "calc_3d_metric_surface", "MeshIndex", "winding_number",
+           "mesh_orientation", "inside", "signed_distance", "volume_iou"]
 
 
 def _device():
@@ -238,6 +242,134 @@ def point_mesh_distance(points, mesh, closest=False, check=True, index=None):
         require_finite(q, "point_mesh_distance")
         require_finite(tri.verts, "point_mesh_distance")
     return _point_mesh(q, tri, closest)
+
+
+# ---- inside and outside ------------------------------------------------------------------------------------------------
+def _winding(q, tri):
+    """w (nq,) f64 of device points about a DeviceMesh with at least one face (the callers refuse an empty one by name)"""
+    verts, faces, F = tri.verts, tri.faces, tri.n_faces
+    nq, dev = len(q), q.device
+    ws = _C.workspace(_C.load().cnr_winding_workspace_bytes(nq, F), dev, "cnr_winding_number")
+    w = torch.empty(nq, device=dev, dtype=torch.float64)
+    _C.call("cnr_winding_number", q, nq, verts, faces, F, w, ws)
+    return w
+
+
+def _winding_inputs(points, mesh, check, what):
+    q = _points(points)
+    tri = device_mesh(mesh, q.device, check=check, what=what)
+    if tri.n_faces < 1:
+        raise ValueError(f"{what} of a mesh without faces")
+    if check:
+        require_finite(q, what)
+        require_finite(tri.verts, what)
+    return q, tri
+
+
+def winding_number(points, mesh, check=True):
+    """The generalized winding number (Jacobson et al. 2013) of a triangle mesh about every point (cnr_winding_number,
+    csrc/winding.hip): the sum over all faces of the signed solid angle, divided by 4 pi, brute force in fp64.
+    `mesh` and `check` as for point_mesh_distance.  -> (n,) f64 device tensor: +1 inside a closed mesh whose right-hand normals
+    point outward (-1 when they point inward, as vis.marching_cubes' do), 0 outside; on an open mesh it falls off smoothly across a hole, and
+    is thresholded at 0.5.  A point in the plane of a face gets nothing from that face, so on the surface itself the value
+    is the mean of the two sides.  A mesh whose faces are not consistently oriented has no meaningful winding number."""
+    q, tri = _winding_inputs(points, mesh, check, "winding_number")
+    return _winding(q, tri)
+
+
+def _signed_volume(verts, faces):
+    """sum over the faces of (a - c0) . ((b - c0) x (c - c0)) in fp64, c0 the centre of the vertices' box; tensors on any device"""
+    v = verts.double()
+    c = v - 0.5 * (v.amin(0) + v.amax(0))
+    c = c.view(-1, 3, 3) if faces is None else c[faces.long()]
+    return (c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum()
+
+
+def mesh_orientation(mesh):
+    """+1 when the mesh's right-hand normals point outward, -1 when inward: the sign (>= 0 -> +1) of the fp64 signed volume
+    sum_f (a - c0) . ((b - c0) x (c - c0)) about the centre c0 of the vertices' box, in torch on the device.  Exact for a closed
+    mesh; for an open one it is a heuristic (a bowl seen from far outside its box centre can fool it), and it does not detect
+    faces that are not consistently oriented.  vis.marching_cubes' meshes (Trainer.meshing's) are inward, loaded ground truths
+    usually outward."""
+    tri = device_mesh(mesh, what="mesh_orientation")
+    if tri.n_faces < 1:
+        raise ValueError("mesh_orientation of a mesh without faces")
+    return _orientation_sign("auto", tri)
+
+
+def _orientation_sign(orientation, tri):
+    if orientation == "auto":
+        return 1 if float(_signed_volume(tri.verts, tri.faces)) >= 0 else -1
+    if orientation in ("outward", "inward"):
+        return 1 if orientation == "outward" else -1
+    raise ValueError(f'orientation must be "auto", "outward" or "inward", not {orientation!r}')
+
+
+def _inside(q, tri, threshold, orientation):
+    s = _orientation_sign(orientation, tri)
+    w = _winding(q, tri)
+    return (w if s > 0 else -w) > threshold
+
+
+def inside(points, mesh, threshold=0.5, orientation="auto", check=True):
+    """-> (n,) bool device tensor: s w > threshold with w = winding_number(points, mesh) and s = +1 for orientation="outward",
+    -1 for "inward", mesh_orientation(mesh) for "auto".  `mesh` and `check` as for point_mesh_distance."""
+    q, tri = _winding_inputs(points, mesh, check, "inside")
+    return _inside(q, tri, threshold, orientation)
+
+
+def signed_distance(points, mesh, threshold=0.5, orientation="auto", closest=False, index=None, check=True):
+    """point_mesh_distance with the distance negated where inside(points, mesh, threshold, orientation): negative is inside.
+    -> (sdist (n,) f32, face (n,) i32[, closest (n,3) f32]); the magnitude, the face and the closest point are
+    point_mesh_distance's bit for bit, with or without `index` (which is passed through; the winding number itself is always
+    taken over all faces of `mesh`, so `mesh` is read also when index is a MeshIndex)."""
+    q, tri = _winding_inputs(points, mesh, check, "signed_distance")
+    out = point_mesh_distance(q, tri, closest=closest, check=False, index=index)     # both were checked above
+    flag = _inside(q, tri, threshold, orientation)
+    return (torch.where(flag, -out[0], out[0]),) + tuple(out[1:])
+
+
+def _box_points(u, box, meshes):
+    """the (N,3) uniforms u (f64, host) scaled in fp64 into the box, rounded to fp32 once -> (points f32 host, box volume)"""
+    if box is None:
+        lo = np.min([m.verts.amin(0).double().cpu().numpy() for m in meshes], 0)
+        hi = np.max([m.verts.amax(0).double().cpu().numpy() for m in meshes], 0)
+        return (lo + u * (hi - lo)).astype(np.float32), float(np.prod(hi - lo))
+    extents = np.asarray(box[1], np.float64).reshape(3)
+    Ti = np.linalg.inv(np.asarray(box[0], np.float64).reshape(4, 4))    # box_planes' box: |local| <= extents / 2 at inv(transform)
+    return (((u - 0.5) * extents) @ Ti[:3, :3].T + Ti[:3, 3]).astype(np.float32), float(np.prod(extents))
+
+
+def volume_iou(mesh_a, mesh_b, N=100000, seed=0, box=None, points=None, threshold=0.5, orientation=("auto", "auto")):
+    """Volumetric intersection over union of two meshes by counting: N points numpy.random.default_rng(seed).random((N,3)),
+    scaled in fp64 and rounded to fp32 once, fill the axis-aligned box of both meshes' vertices (box=None) or the oriented box
+    box=(transform, extents) as oriented_bounds returns it (the one box_planes(transform, extents) describes); points= takes
+    explicit points instead.  Each is classified by inside(., mesh, threshold, orientation[k]).
+    -> dict(iou, intersection, union, inside_a, inside_b, n (exact integer counts; iou = nan when union == 0), volume_a, volume_b
+    (the inside share times the box volume; nan with points=, which have no box), orientation_a, orientation_b (+1 / -1 as used)).
+    Open meshes are welcome (the winding number closes a hole smoothly); inconsistently oriented ones are not."""
+    dev = _device()
+    a = device_mesh(mesh_a, dev, what="volume_iou")
+    b = device_mesh(mesh_b, dev, what="volume_iou")
+    for m in (a, b):
+        if m.n_faces < 1:
+            raise ValueError("volume_iou of a mesh without faces")
+        require_finite(m.verts, "volume_iou")
+    if points is not None:
+        q, volume = _points(points, dev), float("nan")
+        require_finite(q, "volume_iou")
+    else:
+        if int(N) < 1:
+            raise ValueError("volume_iou needs N >= 1 points")
+        host, volume = _box_points(np.random.default_rng(seed).random((int(N), 3)), box, (a, b))
+        q = torch.from_numpy(host).to(dev)
+    sa, sb = _orientation_sign(orientation[0], a), _orientation_sign(orientation[1], b)
+    ia = _inside(q, a, threshold, "outward" if sa > 0 else "inward")
+    ib = _inside(q, b, threshold, "outward" if sb > 0 else "inward")
+    n = len(q)
+    na, nb, inter, union = (int(v) for v in torch.stack([ia.sum(), ib.sum(), (ia & ib).sum(), (ia | ib).sum()]).cpu())
+    return dict(iou=inter / union if union else float("nan"), intersection=inter, union=union, inside_a=na, inside_b=nb, n=n,
+                volume_a=na / n * volume, volume_b=nb / n * volume, orientation_a=sa, orientation_b=sb)
 
 
 def _unit_face_normals(tri):

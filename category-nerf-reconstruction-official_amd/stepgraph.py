@@ -13,8 +13,12 @@ A step owner is a BRANCH.  The driver asks four things of it and touches nothing
 Graph keys: ``parity`` for one step, ``(parity, U)`` for a group of U.  A group is even, so it leaves the parameter / state
 ping-pong where it found it, and it never crosses an epoch end of any branch: the reshuffles are host-launched."""
 import contextlib
+import gc
+import threading
 
 import torch
+
+_CAPTURE_LOCK = threading.Lock()
 
 
 def group_sizes(U0):
@@ -55,10 +59,22 @@ class StepGraphs:
 
     # ---- the three touch points of the device (a host test replaces them with recorders) ----------------------------------------
     def capture(self, fn, pool=None):
-        """record (not run) what ``fn`` launches; returns the object whose ``replay()`` runs it"""
+        """record (not run) what ``fn`` launches; returns the object whose ``replay()`` runs it.  A step owner and its driver
+        refer to each other, so a discarded owner -- its graphs and their memory pool with it -- lives until the cycle collector
+        finds it.  If that happens inside a capture, the graphs are destroyed and their memory freed under a capturing
+        stream, which the runtime does not allow (the process aborts).  Older torch collected in front of every capture; torch 2.10 does
+        so only with torch.compiler.config.force_cudagraph_gc: collect here, and hold the collector off until the capture ends."""
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=pool):
-            fn()
+        with _CAPTURE_LOCK:                            # gc.disable() is process-wide: one capture at a time owns the switch
+            gc.collect()
+            enabled = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g, pool=pool):
+                    fn()
+            finally:
+                if enabled:
+                    gc.enable()
         return g
 
     def fork(self):

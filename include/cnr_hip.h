@@ -860,6 +860,22 @@ int cnr_pm_query_keys(const float* q, int64_t nq, const float* bbox, int* keys_o
 int64_t cnr_point_mesh_indexed_workspace_bytes(int64_t nq, int64_t F);
 int cnr_point_mesh_dist_indexed(const float* q, int64_t nq, const int* qkeys, const int64_t* qorder, const void* index, int64_t F,
                                 float* dist_out, int* face_out, float* closest_out, void* workspace, void* stream);
+/* Generalized winding number (Jacobson et al. 2013), exact and brute force (tests/winding_cpu.py restates it).
+ * q (nq,3) f32; the triangle forms of cnr_face_area_scan (faces == NULL: a soup).  w_out (nq,) f64 = (sum over all faces of t) /
+ * 6.283185307179586, +1 inside a closed mesh whose right-hand normals point outward.  Per (query, face) pair, in fp64 of the
+ * fp32 inputs without contraction, every operation one rounding, dot(u,v) = (u.x v.x + u.y v.y) + u.z v.z, difference first:
+ * A = a - q, B = b - q, C = c - q; la = sqrt(dot(A,A)), lb, lc likewise; X = B x C, each component two products and one
+ * subtraction; det = dot(A,X); den = ((la lb) lc + dot(A,B) lc) + (dot(B,C) la + dot(C,A) lb); t = atan2(det, den) (Van Oosterom
+ * and Strackee: the signed solid angle is 2 t), and t = 0 when det == 0 exactly (the query in the face's plane, on the face or
+ * not; an exactly degenerate face).  Sum order: within a face chunk the terms are added in face order onto a running fp64 sum
+ * that starts at 0, the chunks' sums are added in chunk order.  Inputs must be finite.
+ * nq >= 1, 1 <= F < 2^31; workspace >= cnr_winding_workspace_bytes(nq, F) = chunks * align256(8 nq), where chunks is the number
+ * of face chunks of the grid (query blocks of 512, whole tiles of 256 faces per chunk, about 2048 workgroups): per chunk nq
+ * partial sums (f64).  The chunk count depends on nq, so the result of one query may differ in the last bits between batch
+ * sizes.  No atomics, no allocation, no host synchronisation; bit-identical run to run. */
+int64_t cnr_winding_workspace_bytes(int64_t nq, int64_t F);
+int cnr_winding_number(const float* q, int64_t nq, const float* verts, const int* faces, int64_t F, double* w_out,
+                       void* workspace, void* stream);
 
 /* ---- Category registration on point clouds: src/category_registration.py, src/utils.py:189-366.  DESIGN.md §3.9.  The
  * contracts of the metric kernels hold: caller-allocated outputs, workspace queries, no float atomics, fixed reduction

@@ -1,7 +1,7 @@
 """3-D metrics of the reconstructed meshes (metric/eval_3D_obj.py's command line and output files), on cnr_amd.metrics:
 
     python tools/eval_3d_obj.py --data_dir Datasets/Replica --log_dir logs/Replica [--log_dir_ref DIR] [--iteration 10000]
-                                [--clean keep_largest=1,...] [--surface [--index]]
+                                [--clean keep_largest=1,...] [--surface [--index]] [--volume [N]]
 
 For every scene of the dataset (the last component of --data_dir: Replica or ScanNet) whose <log_dir>/<scene>/scene_mesh exists,
 every object mesh iteration_<it>_obj<id>.obj written by train.py is scored against its ground-truth mesh in
@@ -16,7 +16,13 @@ the --iteration one), scenes without a scene_mesh directory are skipped, and the
 cnr_amd.meshops.clean_mesh as name=value pairs, e.g. keep_largest=1 or min_area_fraction=0.01,weld=0.
 --surface (default off) adds cnr_amd.metrics.calc_3d_metric_surface per object and in the mean: the same samples measured
 against the other MESH (accuracy, completion, completion ratio), precision / recall / F-score at 5 cm and normal
-consistency; written to <log_dir>/<scene>/eval_mesh/metrics_3D_obj_surface.json."""
+consistency; written to <log_dir>/<scene>/eval_mesh/metrics_3D_obj_surface.json.
+--volume [N] (default off; N = 100 000 points when not given) adds cnr_amd.metrics.volume_iou of the reconstruction and the
+ground truth per object and in the mean, counted in mesh_ref's oriented box, the one accuracy is clipped to (so what the
+reconstruction has outside that box counts for nothing); each mesh's orientation is found by mesh_orientation.  Written to
+<log_dir>/<scene>/eval_mesh/metrics_3D_obj_volume.json.  An object with no point inside either mesh has no IoU: it is printed
+as "none", written as null and left out of the mean (objects_in_mean counts the rest).  The background (id 0), a room seen
+from inside, has no volume to compare; it is never listed (see above), so it gets no IoU either."""
 import argparse
 import csv
 import json
@@ -36,6 +42,11 @@ SCANNET_BG = [-1, 0, 1, 3, 16, 41, 232, 21, 161, 128, 21]
 SCANNET_SCENES = ["scene0013_02", "scene0059_00", "scene0066_00", "scene0281_00"]
 SURFACE_COLUMNS = ["accuracy_cm", "completion_cm", "completion_ratio", "precision", "recall", "fscore",
                    "normal_consistency_acc", "normal_consistency_comp", "normal_consistency"]
+VOLUME_COLUMNS = ["iou", "volume_a", "volume_b"]
+
+
+def _fmt(value):
+    return "none" if value is None else "%.4f" % value
 
 
 def concatenate(meshes):
@@ -97,9 +108,10 @@ def main(argv=None):
     ap.add_argument("--clean", default=None, help="drop floaters first: clean_mesh options as name=value,... e.g. keep_largest=1,min_faces=20 (default: off)")
     ap.add_argument("--surface", action="store_true", help="also score against the meshes themselves: point-to-mesh distances, F-score, normal consistency (default: off)")
     ap.add_argument("--index", action="store_true", help="with --surface: take the point-to-mesh distances through a tile-box index of each mesh; the same numbers, faster on large meshes (default: off)")
+    ap.add_argument("--volume", nargs="?", type=int, const=100000, default=None, metavar="N", help="also the volumetric IoU of reconstruction and ground truth from N points (100000 when N is not given) in the crop box, by winding numbers (default: off)")
     args = ap.parse_args(argv)
     from cnr_amd.meshops import clean_mesh, parse_clean_options
-    from cnr_amd.metrics import calc_3d_metric, calc_3d_metric_surface
+    from cnr_amd.metrics import calc_3d_metric, calc_3d_metric_surface, oriented_bounds, volume_iou
     clean = parse_clean_options(args.clean) if args.clean else None
     from cnr_amd.vis import load_mesh
 
@@ -123,7 +135,7 @@ def main(argv=None):
         output_path = os.path.join(exp_dir, "eval_mesh")
         os.makedirs(output_path, exist_ok=True)
         metrics_3D = [[] for _ in range(3)]
-        surface = {}
+        surface, volume = {}, {}
         for obj_id in get_obj_ids(mesh_dir, args.iteration):
             if obj_id == 0:
                 N = 200000
@@ -151,6 +163,11 @@ def main(argv=None):
                 if row is not None:
                     surface[obj_id] = row
                     print("surface obj %d: " % obj_id + "  ".join("%s %.4f" % (k, row[k]) for k in SURFACE_COLUMNS))
+            if args.volume is not None:
+                volume[obj_id] = row = volume_iou(mesh_rec, mesh_gt, N=args.volume, box=oriented_bounds(mesh_ref))
+                if row["union"] == 0:           # no point inside either mesh: no IoU (None: JSON has no nan), not in the mean
+                    row["iou"] = None
+                print("volume obj %d: " % obj_id + "  ".join("%s %s" % (k, _fmt(row[k])) for k in VOLUME_COLUMNS))
         metrics_3D = np.array(metrics_3D)
         np.save(os.path.join(output_path, "metrics_3D_obj.npy"), metrics_3D)
         print("metrics 3D obj \n Acc | Comp | Comp Ratio 5cm \n", metrics_3D.mean(axis=1) if metrics_3D.size else metrics_3D)
@@ -159,6 +176,13 @@ def main(argv=None):
             with open(os.path.join(output_path, "metrics_3D_obj_surface.json"), "w") as f:
                 json.dump(dict(objects={str(k): v for k, v in surface.items()}, mean=mean), f, indent=1)
             print("surface mean: " + "  ".join("%s %.4f" % (k, mean[k]) for k in SURFACE_COLUMNS))
+        if args.volume is not None:
+            scored = [r for r in volume.values() if r["iou"] is not None]
+            mean = {k: float(np.mean([r[k] for r in scored])) for k in VOLUME_COLUMNS} if scored else {}
+            with open(os.path.join(output_path, "metrics_3D_obj_volume.json"), "w") as f:
+                json.dump(dict(points=args.volume, objects={str(k): v for k, v in volume.items()}, mean=mean,
+                               objects_in_mean=len(scored)), f, indent=1, allow_nan=False)
+            print("volume mean: " + ("  ".join("%s %.4f" % (k, mean[k]) for k in VOLUME_COLUMNS) if scored else "no objects"))
         print("-----------------------------------------")
         print("finish exp ", exp)
 
