@@ -1095,6 +1095,7 @@ extern "C" int cnr_bg_tail_sample(const cnr_bg_tail_sample_args* p, void* stream
       !p->labels || p->R <= 0 || p->n1 < 0 || p->n2 <= 0 || p->pool_rows < p->R)
     return CNR_E_ARG;
   if (p->n2 > 128) return CNR_E_SHAPE;
+  if ((int64_t)p->n1 + p->n2 > 256) return CNR_E_SHAPE;   // in-kernel draws: four uniform column blocks per step (cnr_sample_rays)
   if (p->max_bound_slices < 0 || (p->max_bound_slices > 1 && !p->max_bound)) return CNR_E_ARG;
   const cnr_sample::SampleArgs sa{p->rgbs, p->depth, p->dirs_c, p->T, nullptr, nullptr, p->seed, p->offset, p->d_state,
                                   p->pool_rows, p->max_bound, p->world_frame, 1, p->R, p->n1, p->n2, p->eps, p->stop_eps,

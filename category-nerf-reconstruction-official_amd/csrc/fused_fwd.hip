@@ -691,6 +691,7 @@ extern "C" int cnr_step_prologue(const cnr_step_prologue_args* a, void* stream) 
     if (R <= 0 || n1 < 0 || n2 <= 0) return CNR_E_ARG;
     if (n2 > 128) return CNR_E_SHAPE;
     if ((a->u == nullptr) != (a->g == nullptr)) return CNR_E_ARG;
+    if (!a->u && (int64_t)n1 + n2 > 256) return CNR_E_SHAPE;   // in-kernel draws: four uniform column blocks per step (cnr_sample_rays)
     if (a->pool_rows < 0 || (a->pool_rows > 0 && (!a->d_state || a->pool_rows < R))) return CNR_E_ARG;
     if (a->ray_row && !a->pool_indices) return CNR_E_ARG;
     if (a->perm && a->pool_rows == 0) return CNR_E_ARG;

@@ -170,6 +170,9 @@ extern "C" int cnr_sample_rays(const uint8_t* rgbs, const float* depth, const fl
   if (C <= 0 || R <= 0 || n1 < 0 || n2 <= 0) return CNR_E_ARG;
   if (n2 > 128) return CNR_E_SHAPE;
   if ((u == nullptr) != (g == nullptr)) return CNR_E_ARG;
+  // in-kernel draws: a step owns four Philox high words (its Gaussians' and uniform column blocks 0..3) -- a fifth block would
+  // read the next step's first
+  if (!u && (int64_t)n1 + n2 > 256) return CNR_E_SHAPE;
   if (pool_rows < 0 || (pool_rows > 0 && (!d_state || pool_rows < R))) return CNR_E_ARG;
   if (ray_row && (!pool_indices || n_obj <= 0)) return CNR_E_ARG;
   if (perm && pool_rows == 0) return CNR_E_ARG;

@@ -59,7 +59,13 @@ int cnr_camera_rays(float* dirs, int W, int H, float fx, float fy, float cx, flo
  * One pool slice of R rays (per class; C slices batched).  Inputs:
  *   rgbs  (C,R,4) u8  [r,g,b,state]      depth (C,R)      dirs_c (C,R,3)     T (C,R,4,4)
  *   u     (C,R,n1+n2) uniform [0,1) draws, g (C,R,n2) N(0,(eps/3)^2) draws  (parity mode), or both
- *         NULL with `seed`/`offset` != 0 for in-kernel Philox draws (perf mode).
+ *         NULL with `seed`/`offset` != 0 for in-kernel Philox draws (perf mode).  n2 <= 128 in either mode.  In-kernel draws
+ *         need S = n1 + n2 <= 256 as well (CNR_E_SHAPE beyond, here and in cnr_step_prologue / cnr_bg_tail_sample; nothing is
+ *         launched): lane l of the ray with Philox index i draws from Philox4x32-10(key = seed) at the counter
+ *         (low 64 bits i * 64 + l, high 64 bits h).  With o = offset + 4 * d_state[1] (d_state[1] counted only with pool_rows > 0):
+ *         h = o ^ 0x9E3779B97F4A7C15 gives the Gaussian draws of elements l (words 0, 1) and l + 64 (words 2, 3);
+ *         h = o + 1 + b, word 0, gives the uniform draw of column 64 b + l.  A step owns the four high words o + 1 .. o + 4,
+ *         so a fifth column block (S > 256) would be the next step's first.  Recorded draws have no such limit.
  *   world_frame: 0 -> origin_dirs_O (T is T_CO, inverted in-kernel, sim3 closed form is NOT assumed:
  *         a general 3x3 inverse is used), 1 -> origin_dirs_W (T is T_WC).
  *   max_bound (C,) : per-class max(depth) over the slice (reference :486); computed by
@@ -85,7 +91,7 @@ int cnr_sample_rays(const uint8_t* rgbs, const float* depth, const float* dirs_c
                     void* stream);
 /* Device-resident step state int64[3] = {pool cursor (rows), rng step, optimiser step}.  With pool_rows > 0
  * the four pool pointers above are the BASES of (C, pool_rows, ...) pools and the slice starts at row
- * d_state[0] (src/scene_cateogries.py:422-431's i_batch); the Philox offset advances by d_state[1].
+ * d_state[0] (src/scene_cateogries.py:422-431's i_batch); the Philox offset advances by 4 * d_state[1].
  * cnr_step_advance adds (add_rows, 1, 1): a captured hipGraph of the train step replays unchanged.
  * perm (C,pool_rows) i32, optional with pool_rows > 0: row r of the slice is pool row perm[c][cursor + r] -- the
  * per-epoch reshuffle (src/scene_cateogries.py:439-449) becomes a new permutation instead of moving the pool. */
