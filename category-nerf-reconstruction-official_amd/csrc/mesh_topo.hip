@@ -45,6 +45,19 @@
 //                             rep[perm[j]] = perm[head of j's run] -- the lowest input index of the run when the sort was stable.
 //   cnr_mesh_remap_faces      out[3 f + k] = remap[faces[3 f + k]]; keep[f] = 0 when drop_degenerate and two corners coincide,
 //                             else 1.
+//
+// Orientation repair: a LINK is a run of exactly two equal keys (degenerate faces' keys all -1), rel = 1 when
+// both faces run the edge the same way.
+//   cnr_mesh_orient_keys      cnr_mesh_edge_keys with a degenerate face's three keys -1.
+//   cnr_mesh_orient_union     words[i] = i << 1, then unite_parity (mesh_topo_common.h) over the links.
+//   cnr_mesh_orient_flatten   jump_parity sweeps; labels[i] = root, flip0[i] = i's parity relative to the root.
+//   cnr_mesh_orient_check     bad[patch] |= 1 where a link has flip0[f] ^ flip0[g] != rel; counts[patch] = (edge slots in no run of
+//                             two, links with rel == 1); then flip0 = 0 in bad patches.
+//   cnr_mesh_orient_stats     per patch: its vertex box and its count of flip0 by integer atomics (exact minima / maxima on an
+//                             order-preserving image of the floats, sums of integers: any order gives the same); then over the
+//                             faces stably sorted by patch the per-face terms, and ONE WAVE PER PATCH sums them; the order of
+//                             operations stands at orient_face_term_kernel and orient_patch_sum_kernel below.
+//   cnr_mesh_orient_apply     flip = flip0 ^ sign[patch], a flipped (a, b, d) becomes (a, d, b).
 #include "cnr_common.h"
 #include "geom_common.h"
 #include "mesh_topo_common.h"
@@ -521,7 +534,280 @@ __global__ __launch_bounds__(MT_BLOCK) void remap_faces_kernel(const int* __rest
   }
 }
 
-#define MT_LAUNCH(kernel, n, ...)                                                                              \
+// ---- orientation repair -------------------------------------------------------------------------
+__device__ __forceinline__ bool face_degenerate(int a, int b, int c) { return a == b || b == c || c == a; }
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_keys_kernel(const int* __restrict__ faces, int64_t F, int64_t* __restrict__ keys) {
+  MT_GRID_STRIDE(f, F) {
+    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+    const bool dead = face_degenerate(a, b, c);
+    keys[3 * f] = dead ? -1 : ccl::edge_key(a, b);
+    keys[3 * f + 1] = dead ? -1 : ccl::edge_key(b, c);
+    keys[3 * f + 2] = dead ? -1 : ccl::edge_key(c, a);
+  }
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_init_kernel(int* __restrict__ W, int64_t n) {
+  MT_GRID_STRIDE(i, n) W[i] = (int)i << 1;
+}
+
+// sorted position j belongs to a run of exactly two equal keys >= 0
+__device__ __forceinline__ bool in_pair(const int64_t* __restrict__ keys, int64_t E, int64_t j, bool* head) {
+  const int64_t k = keys[j];
+  if (k < 0) return false;
+  const bool prev = j > 0 && keys[j - 1] == k, next = j + 1 < E && keys[j + 1] == k;
+  *head = next;
+  if (prev == next) return false;                              // alone, or inside a longer run
+  return next ? !(j + 2 < E && keys[j + 2] == k) : !(j >= 2 && keys[j - 2] == k);
+}
+
+// the link whose run begins at sorted position j: faces f < g and rel = 1 when both run the edge the same way
+__device__ __forceinline__ bool link_at(const int64_t* __restrict__ keys, const int64_t* __restrict__ perm, const int* __restrict__ faces,
+                                        int64_t E, int64_t j, int* f, int* g, int* rel, int* e) {
+  bool head;
+  if (!in_pair(keys, E, j, &head) || !head) return false;
+  const int64_t s0 = perm[j], s1 = perm[j + 1];
+  if (!in_range(s0, E) || !in_range(s1, E)) {
+    *e |= 2;
+    return false;
+  }
+  *f = (int)(s0 / 3), *g = (int)(s1 / 3);
+  *rel = slot_ascends(faces, s0) == slot_ascends(faces, s1) ? 1 : 0;
+  return true;
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_union_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ perm,
+                                                                const int* __restrict__ faces, int64_t E, int F, int* W, int* err) {
+  // A wave takes 64 neighbouring sorted positions (coalesced), but the waves take their chunks in a scattered order: chunk
+  // (w * odd) mod 2^k is a bijection of [0, 2^k), 2^k >= the number of chunks.  Neighbouring positions are neighbouring faces in
+  // a mesh that was written out along its surface, and waves that run at the same time would otherwise hang face after face
+  // under its predecessor -- one long chain that every later find has to walk (the ascending ladder of tools/time_meshorient.py).
+  // The order of the unions does not change their result.
+  int e = 0;
+  const int64_t chunks = (E + 63) / 64, waves = (int64_t)gridDim.x * MT_WAVES;
+  int64_t pow2 = 1;
+  while (pow2 < chunks) pow2 <<= 1;
+  for (int64_t w = (int64_t)blockIdx.x * MT_WAVES + (threadIdx.x >> 6); w < pow2; w += waves) {
+    const int64_t chunk = (int64_t)(((uint64_t)w * 0x9E3779B1ull) & (uint64_t)(pow2 - 1));
+    const int64_t j = chunk * 64 + (threadIdx.x & 63);
+    if (chunk >= chunks || j >= E) continue;
+    int f, g, rel;
+    if (!link_at(keys, perm, faces, E, j, &f, &g, &rel, &e)) continue;
+    int fe = 0;
+    ccl::unite_parity(W, g, f, rel, F, &fe);
+    e |= fe;
+  }
+  if (e) atomicOr(err, e);
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_sweep_kernel(int* W, int64_t n, int s, int* flags) {
+  if (s > 0 && __hip_atomic_load(flags + s - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+  bool open = false;
+  MT_GRID_STRIDE(i, n) open |= !ccl::jump_parity(W, (int)i);
+  if (open) atomicOr(flags + s, 1);
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_split_kernel(const int* __restrict__ W, int64_t n, int* __restrict__ labels,
+                                                                uint8_t* __restrict__ flip0) {
+  MT_GRID_STRIDE(i, n) {
+    const int w = W[i];
+    labels[i] = w >> 1;
+    flip0[i] = (uint8_t)(w & 1);
+  }
+}
+
+// counts[2 c + 0] += the edge slots of patch c that lie in no run of two (boundary or non-manifold: the patch is not closed),
+// counts[2 c + 1] += its links with rel == 1; bad[c] |= 1 when a link contradicts flip0.  Lanes keep the counts of the patch they
+// met last, as edge_stats_kernel does.
+__global__ __launch_bounds__(MT_BLOCK) void orient_check_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ perm,
+                                                                const int* __restrict__ faces, int64_t E,
+                                                                const int* __restrict__ face_patch, int C,
+                                                                const uint8_t* __restrict__ flip0, int* bad, int* counts, int* err) {
+  int cur = -1, acc[2] = {0, 0}, e = 0;
+  MT_GRID_STRIDE(j, E) {
+    if (keys[j] < 0) continue;
+    const int64_t s = perm[j];
+    if (!in_range(s, E)) {
+      e |= 2;
+      continue;
+    }
+    const int c = face_patch[s / 3];
+    if (c < 0 || c >= C) continue;
+    bool head;
+    const bool pair = in_pair(keys, E, j, &head);
+    int f, g, rel = 0;
+    if (pair && head && link_at(keys, perm, faces, E, j, &f, &g, &rel, &e)) {
+      if ((flip0[f] ^ flip0[g]) != rel) atomicOr(bad + c, 1);
+    }
+    if (c != cur) {
+      if (cur >= 0)
+        for (int q = 0; q < 2; ++q)
+          if (acc[q]) atomicAdd(counts + 2 * cur + q, acc[q]);
+      cur = c, acc[0] = acc[1] = 0;
+    }
+    acc[0] += pair ? 0 : 1;
+    acc[1] += rel;
+  }
+  wave_add<2>(counts, cur, acc);
+  if (e) atomicOr(err, e);
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_clear_kernel(const int* __restrict__ face_patch, const int* __restrict__ bad, int64_t F,
+                                                                int C, uint8_t* __restrict__ flip0) {
+  MT_GRID_STRIDE(f, F) {
+    const int c = face_patch[f];
+    if (c >= 0 && c < C && bad[c] != 0) flip0[f] = 0;
+  }
+}
+
+// a float as an int that orders the same way (an involution: the same function decodes), so that the exact minima and maxima of a
+// patch's box can be taken by INTEGER atomics -- their result does not depend on their order; -0 sorts below +0
+__device__ __forceinline__ int float_order(int bits) { return bits >= 0 ? bits : bits ^ 0x7fffffff; }
+__device__ __forceinline__ int order_of_float(float x) { return float_order(__float_as_int(x)); }
+__device__ __forceinline__ float float_of_order(int k) { return __int_as_float(float_order(k)); }
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_box_init_kernel(int* __restrict__ box, int64_t C) {
+  MT_GRID_STRIDE(i, 6 * C) box[i] = order_of_float(i % 6 < 3 ? INFINITY : -INFINITY);
+}
+
+// per face f of patch c: n_flip0[c] += flip0[f] and, with verts, box[c] = min / max with the face's corners (box (C,6) int =
+// float_order of lo.xyz, hi.xyz).  A wave whose live lanes all hold the same patch combines them over the butterfly first and
+// issues one set of atomics; the trip count is the same for every lane of a block, so every lane takes part in the shuffles.
+__global__ __launch_bounds__(MT_BLOCK) void orient_gather_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                 const int* __restrict__ face_patch, const uint8_t* __restrict__ flip0,
+                                                                 int64_t F, int C, int* box, int* n_flip0) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t base = (int64_t)blockIdx.x * MT_BLOCK; base < F; base += (int64_t)gridDim.x * MT_BLOCK) {
+    const int64_t f = base + threadIdx.x;
+    int c = f < F ? face_patch[f] : -1;
+    const bool live = c >= 0 && c < C;
+    int fl = live && flip0[f] != 0 ? 1 : 0;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (live && verts) {
+      const float* p0 = verts + 3 * (int64_t)faces[3 * f];
+      const float* p1 = verts + 3 * (int64_t)faces[3 * f + 1];
+      const float* p2 = verts + 3 * (int64_t)faces[3 * f + 2];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = fminf(fminf(p0[a], p1[a]), p2[a]);
+        hi[a] = fmaxf(fmaxf(p0[a], p1[a]), p2[a]);
+      }
+    }
+    const uint64_t alive = __ballot(live);
+    if (alive == 0) continue;                                  // the whole wave
+    const int lead = __ffsll((unsigned long long)alive) - 1;
+    const int c0 = __shfl(c, lead, 64);
+    const bool uniform = __ballot(live && c != c0) == 0;
+    if (uniform) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) {
+        fl += __shfl_xor(fl, d, 64);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
+          hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64));
+        }
+      }
+    }
+    if (uniform ? lane == lead : live) {
+      if (fl) atomicAdd(n_flip0 + c, fl);
+      if (verts) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          atomicMin(box + 6 * (int64_t)c + a, order_of_float(lo[a]));
+          atomicMax(box + 6 * (int64_t)c + 3 + a, order_of_float(hi[a]));
+        }
+      }
+    }
+  }
+}
+
+// per sorted position j, face (a, b, d) = order[j] with b and d swapped when flip0 is set,
+// c = 0.5 * ((double)lo + (double)hi) per axis of the patch's fp32 vertex box:
+//   pa = (double)a - c, pb = (double)b - c, pd = (double)d - c (per axis),
+//   cx = pb.y pd.z - pb.z pd.y, cy = pb.z pd.x - pb.x pd.z, cz = pb.x pd.y - pb.y pd.x (each product rounded, then the difference),
+//   term = (pa.x cx + pa.y cy) + pa.z cz;  a degenerate face's term is +0.0.
+// Swapping b and d negates cx, cy, cz and with them the term exactly, so a flipped patch's sum is the exact negative.
+__global__ __launch_bounds__(MT_BLOCK) void orient_face_term_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                                    const int64_t* __restrict__ order, const int* __restrict__ sorted_patch,
+                                                                    const uint8_t* __restrict__ flip0, const int* __restrict__ box,
+                                                                    int64_t F, int C, double* __restrict__ wterm) {
+  MT_GRID_STRIDE(j, F) {
+    const int64_t f = order[j];
+    const int c = sorted_patch[j];
+    double term = 0.0;
+    if (in_range(f, F) && c >= 0 && c < C) {
+      const int ia = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+      if (!face_degenerate(ia, i1, i2)) {
+        const bool fl = flip0[f] != 0;
+        const float* a = verts + 3 * (int64_t)ia;
+        const float* b = verts + 3 * (int64_t)(fl ? i2 : i1);
+        const float* d = verts + 3 * (int64_t)(fl ? i1 : i2);
+        const int* bc = box + 6 * (int64_t)c;
+        double cc[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cc[k] = 0.5 * ((double)float_of_order(bc[k]) + (double)float_of_order(bc[3 + k]));
+        const double ax = (double)a[0] - cc[0], ay = (double)a[1] - cc[1], az = (double)a[2] - cc[2];
+        const double bx = (double)b[0] - cc[0], by = (double)b[1] - cc[1], bz = (double)b[2] - cc[2];
+        const double dx = (double)d[0] - cc[0], dy = (double)d[1] - cc[1], dz = (double)d[2] - cc[2];
+        const double cx = by * dz - bz * dy, cy = bz * dx - bx * dz, cz = bx * dy - by * dx;
+        term = (ax * cx + ay * cy) + az * cz;
+      }
+    }
+    wterm[j] = term;
+  }
+}
+
+// ONE WAVE PER PATCH over run = [lower_bound(sorted_patch, c), lower_bound(sorted_patch, c + 1)): n_faces[c] = its length;
+// lane l takes the run's positions l, l + 64, l + 128, ... in that (ascending) order from acc = 0.0: acc = acc + term; then the
+// lanes combine over the fixed tree of distances 32, 16, 8, 4, 2, 1: a[l] = a[l] + a[l ^ d];
+// lane 0: s = acc, sign[c] = outward and the patch is orientable and s < 0, signed_volume[c] = (sign ? -s : s) / 6,
+// n_flipped[c] = sign ? n_faces - n_flip0 : n_flip0.  wterm == NULL: the counts only, sign = 0.
+__global__ __launch_bounds__(MT_BLOCK) void orient_patch_sum_kernel(const double* __restrict__ wterm, const int* __restrict__ sorted_patch,
+                                                                    const int* __restrict__ n_flip0, const int* __restrict__ bad,
+                                                                    int64_t F, int C, int outward, int* __restrict__ n_faces,
+                                                                    int* __restrict__ n_flipped, uint8_t* __restrict__ sign,
+                                                                    double* __restrict__ volume) {
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * MT_WAVES + (threadIdx.x >> 6);
+  if (c >= C) return;                                          // the whole wave; no barrier below
+  const int64_t j0 = lower_bound_i32(sorted_patch, F, (int)c), j1 = lower_bound_i32(sorted_patch, F, (int)c + 1);
+  double acc = 0.0;
+  // CW_AHEAD positions of the lane at a time, their loads in flight together; the additions stay in ascending order of position
+  for (int64_t j = j0 + lane; wterm && j < j1; j += 64 * CW_AHEAD) {
+    double w[CW_AHEAD];
+#pragma unroll
+    for (int u = 0; u < CW_AHEAD; ++u) w[u] = j + 64 * u < j1 ? wterm[j + 64 * u] : 0.0;
+#pragma unroll
+    for (int u = 0; u < CW_AHEAD; ++u)
+      if (j + 64 * u < j1) acc = acc + w[u];
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc = acc + __shfl_xor(acc, d, 64);
+  if (lane == 0) {
+    const int n = (int)(j1 - j0), nf = n_flip0[c];
+    const bool neg = wterm && outward && bad[c] == 0 && acc < 0.0;
+    n_faces[c] = n;
+    n_flipped[c] = neg ? n - nf : nf;
+    sign[c] = neg ? 1 : 0;
+    if (volume) volume[c] = (neg ? -acc : acc) / 6.0;
+  }
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void orient_apply_kernel(const int* __restrict__ faces, int64_t F, const int* __restrict__ face_patch,
+                                                                int C, const uint8_t* __restrict__ flip0, const uint8_t* __restrict__ sign,
+                                                                int* __restrict__ out_faces, uint8_t* __restrict__ flip) {
+  MT_GRID_STRIDE(f, F) {
+    const int c = face_patch[f];
+    const int a = faces[3 * f], b = faces[3 * f + 1], d = faces[3 * f + 2];
+    const bool dead = face_degenerate(a, b, d);
+    const bool fl = !dead && ((flip0[f] != 0) != (c >= 0 && c < C && sign[c] != 0));
+    out_faces[3 * f] = a, out_faces[3 * f + 1] = fl ? d : b, out_faces[3 * f + 2] = fl ? b : d;
+    flip[f] = fl ? 1 : 0;
+  }
+}
+
+#define MT_LAUNCH(kernel, n, ...)                                                                            \
   do {                                                                                                         \
     hipLaunchKernelGGL(kernel, dim3(mt_grid(n)), dim3(MT_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__);         \
     CNR_LAUNCH_CHECK();                                                                                        \
@@ -737,5 +1023,87 @@ extern "C" int cnr_mesh_remap_faces(const int* faces, int64_t F, const int* rema
   if (!faces || !remap || !out_faces || !keep) return CNR_E_ARG;
   if (F < 1 || F > INDEX_LIMIT / 3) return CNR_E_SHAPE;
   MT_LAUNCH(remap_faces_kernel, F, faces, F, remap, drop_degenerate, out_faces, keep);
+  return CNR_OK;
+}
+
+// ---- orientation repair ----------------------------------------------------------------------------------------------------
+extern "C" int cnr_mesh_orient_keys(const int* faces, int64_t F, int64_t* keys, void* stream) {
+  if (!faces || !keys) return CNR_E_ARG;
+  if (F < 1 || F > INDEX_LIMIT / 3) return CNR_E_SHAPE;
+  MT_LAUNCH(orient_keys_kernel, F, faces, F, keys);
+  return CNR_OK;
+}
+
+extern "C" int cnr_mesh_orient_union(const int64_t* sorted_keys, const int64_t* perm, const int* faces, int64_t F, int* words, int* err,
+                                     void* stream) {
+  if (!sorted_keys || !perm || !faces || !words || !err) return CNR_E_ARG;
+  if (F < 1 || F > INDEX_LIMIT / 3) return CNR_E_SHAPE;
+  MT_LAUNCH(orient_init_kernel, F, words, F);
+  MT_LAUNCH(orient_union_kernel, 3 * F, sorted_keys, perm, faces, 3 * F, (int)F, words, err);
+  return CNR_OK;
+}
+
+extern "C" int cnr_mesh_orient_flatten(int* words, int64_t F, void* workspace, int* labels, uint8_t* flip0, int* err, void* stream) {
+  if (!words || !workspace || !labels || !flip0 || !err) return CNR_E_ARG;
+  if (F < 1 || F > INDEX_LIMIT / 3) return CNR_E_SHAPE;
+  const int sweeps = ccl::sweeps_for(F);
+  int* flags = (int*)workspace;
+  hipError_t e = hipMemsetAsync(flags, 0, (size_t)sweeps * 4, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  for (int s = 0; s < sweeps; ++s) MT_LAUNCH(orient_sweep_kernel, F, words, F, s, flags);
+  hipLaunchKernelGGL(flatten_verify_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const int*)flags, sweeps, err);
+  CNR_LAUNCH_CHECK();
+  MT_LAUNCH(orient_split_kernel, F, (const int*)words, F, labels, flip0);
+  return CNR_OK;
+}
+
+extern "C" int cnr_mesh_orient_check(const int64_t* sorted_keys, const int64_t* perm, const int* faces, int64_t F, const int* face_patch,
+                                     int64_t C, uint8_t* flip0, int* bad, int* counts, int* err, void* stream) {
+  if (!sorted_keys || !perm || !faces || !face_patch || !flip0 || !bad || !counts || !err) return CNR_E_ARG;
+  if (F < 1 || F > INDEX_LIMIT / 3 || C < 1 || C > F) return CNR_E_SHAPE;
+  hipError_t e = hipMemsetAsync(bad, 0, (size_t)C * 4, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemsetAsync(counts, 0, (size_t)C * 8, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(orient_check_kernel, dim3(grid_of(3 * F, MT_BLOCK, ES_GRID_CAP)), dim3(MT_BLOCK), 0, (hipStream_t)stream, sorted_keys,
+                     perm, faces, 3 * F, face_patch, (int)C, (const uint8_t*)flip0, bad, counts, err);
+  CNR_LAUNCH_CHECK();
+  MT_LAUNCH(orient_clear_kernel, F, face_patch, (const int*)bad, F, (int)C, flip0);
+  return CNR_OK;
+}
+
+// workspace: boxes (C <= F, 6) int | terms (F) f64 | flip0 counts (C <= F) int
+extern "C" int64_t cnr_mesh_orient_stats_workspace_bytes(int64_t F) {
+  if (F < 1 || F > INDEX_LIMIT / 3) return CNR_E_SHAPE;
+  return align256(F * 24) + align256(F * 8) + align256(F * 4);
+}
+
+extern "C" int cnr_mesh_orient_stats(const float* verts, const int* faces, const int64_t* order, const int* sorted_patch,
+                                     const int* face_patch, int64_t F, int64_t V, int64_t C, const uint8_t* flip0, const int* bad,
+                                     int outward, void* workspace, int* n_faces, int* n_flipped, uint8_t* sign, double* signed_volume,
+                                     void* stream) {
+  if (!faces || !order || !sorted_patch || !face_patch || !flip0 || !bad || !workspace || !n_faces || !n_flipped || !sign) return CNR_E_ARG;
+  if (verts && !signed_volume) return CNR_E_ARG;
+  if (!sizes_ok(F, V) || C < 1 || C > F) return CNR_E_SHAPE;
+  int* box = (int*)workspace;
+  double* wterm = verts ? (double*)((char*)workspace + align256(F * 24)) : nullptr;
+  int* n_flip0 = (int*)((char*)workspace + align256(F * 24) + align256(F * 8));
+  hipError_t e = hipMemsetAsync(n_flip0, 0, (size_t)C * 4, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  if (verts) MT_LAUNCH(orient_box_init_kernel, 6 * C, box, C);
+  MT_LAUNCH(orient_gather_kernel, F, verts, faces, face_patch, flip0, F, (int)C, box, n_flip0);
+  if (verts) MT_LAUNCH(orient_face_term_kernel, F, verts, faces, order, sorted_patch, flip0, (const int*)box, F, (int)C, wterm);
+  hipLaunchKernelGGL(orient_patch_sum_kernel, dim3((unsigned)((C + MT_WAVES - 1) / MT_WAVES)), dim3(MT_BLOCK), 0, (hipStream_t)stream,
+                     (const double*)wterm, sorted_patch, (const int*)n_flip0, bad, F, (int)C, outward, n_faces, n_flipped, sign,
+                     verts ? signed_volume : (double*)nullptr);
+  CNR_LAUNCH_CHECK();
+  return CNR_OK;
+}
+
+extern "C" int cnr_mesh_orient_apply(const int* faces, int64_t F, const int* face_patch, int64_t C, const uint8_t* flip0,
+                                     const uint8_t* sign, int* out_faces, uint8_t* flip, void* stream) {
+  if (!faces || !face_patch || !flip0 || !sign || !out_faces || !flip) return CNR_E_ARG;
+  if (F < 1 || F > INDEX_LIMIT / 3 || C < 1 || C > F) return CNR_E_SHAPE;
+  MT_LAUNCH(orient_apply_kernel, F, faces, F, face_patch, (int)C, flip0, sign, out_faces, flip);
   return CNR_OK;
 }

@@ -1,6 +1,7 @@
 """The mesh as a graph, on the device (csrc/mesh_topo.hip): welding of coincident vertices, connected
 components by edge or by vertex with their table (faces, vertices, area, bounding box, boundary / non-manifold edges,
-watertightness), compaction of a face selection, and ``clean_mesh``: dropping the floaters of a marching-cubes mesh.  And making
+watertightness), compaction of a face selection, ``clean_mesh``: dropping the floaters of a marching-cubes mesh, and ``orient``:
+consistent winding per patch and outward patches.  And making
 it smaller (csrc/mesh_simplify.hip): ``simplify``, uniform vertex clustering with quadric placement, and
 ``vertex_normals``.
 
@@ -178,6 +179,111 @@ def components(faces, n_vertices, verts=None, connectivity="edge", timer=None):
                           watertight=(edge_counts == 0).all(dim=1), labels=labels)
 
 
+class MeshOrientation:
+    """The result of ``orient``.  faces (F,3) i32: the input with corners 1 and 2 swapped where flip (F,) u8 is set;
+    face_patch (F,) i32; n patches, numbered by their smallest face ``first`` (n,) i32.  Per patch: n_faces (n,) i32,
+    orientable (n,) bool, closed (n,) bool (every edge of its non-degenerate faces occurs exactly twice), inconsistent_edges
+    (n,) i32 (links whose two faces ran the edge in the same direction in the INPUT), n_flipped (n,) i32, signed_volume (n,) f64
+    after repair (None without verts)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def table(self):
+        """one line per patch, for printing"""
+        cols = {k: getattr(self, k).cpu().numpy() for k in ("first", "n_faces", "orientable", "closed", "inconsistent_edges",
+                                                           "n_flipped")}
+        vol = self.signed_volume.cpu().numpy() if self.signed_volume is not None else np.full(self.n, np.nan)
+        lines = ["%5s %9s %9s %10s %6s %12s %9s %16s" % ("id", "first", "faces", "orientable", "closed", "inconsistent", "flipped",
+                                                        "signed_volume")]
+        for c in range(self.n):
+            lines.append("%5d %9d %9d %10s %6s %12d %9d %16.9g" % (c, cols["first"][c], cols["n_faces"][c],
+                                                                 "yes" if cols["orientable"][c] else "no",
+                                                                 "yes" if cols["closed"][c] else "no", cols["inconsistent_edges"][c],
+                                                                 cols["n_flipped"][c], vol[c]))
+        return "\n".join(lines)
+
+
+def orient(faces, n_vertices, verts=None, outward=None, timer=None):
+    """Orientation repair (trimesh's ``fix_normals``) -> MeshOrientation.  Two faces are LINKED when they are
+    the only two on an undirected edge; patches are the connected components under links (a non-manifold edge joins nothing,
+    a face with two equal corners is a patch of its own and is never flipped).  Within an orientable patch every face is
+    brought to the winding of the patch's smallest face; a patch that cannot be oriented (a Moebius band) is left as it is and
+    flagged.  With verts (V,3) f32 and outward (default: verts is not None), a patch whose fp64 signed volume about the centre
+    of its vertex box is negative is flipped as a whole: exact for a closed patch, for an open one the heuristic of
+    ``metrics.mesh_orientation``.  Integer work plus one fixed-order fp64 sum per patch: bit-identical run to run.
+    timer(name), when given, is called after every stage."""
+    V = int(n_vertices)
+    if outward is None:
+        outward = verts is not None
+    if outward and verts is None:
+        raise ValueError("orient: outward=True needs verts")
+    f = check_faces(faces, V, "orient")
+    F, dev = f.shape[0], f.device
+    mark = timer or (lambda name: None)
+    if verts is not None:
+        if tuple(verts.shape) != (V, 3):
+            raise ValueError(f"verts must have the shape ({V},3), not {tuple(verts.shape)}")
+        verts = verts.float().contiguous()
+    if F == 0:
+        z32 = torch.zeros(0, device=dev, dtype=torch.int32)
+        zb = torch.zeros(0, device=dev, dtype=torch.bool)
+        return MeshOrientation(n=0, faces=f, flip=torch.zeros(0, device=dev, dtype=torch.uint8), face_patch=z32, first=z32.clone(),
+                               n_faces=z32.clone(), orientable=zb, closed=zb.clone(), inconsistent_edges=z32.clone(),
+                               n_flipped=z32.clone(),
+                               signed_volume=torch.zeros(0, device=dev, dtype=torch.float64) if verts is not None else None)
+    mark("check")
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    keys = torch.empty(3 * F, device=dev, dtype=torch.int64)
+    _C.call("cnr_mesh_orient_keys", f, F, keys)
+    mark("edge_keys")
+    skeys, perm = torch.sort(keys, stable=True)
+    mark("sort_edges")
+    words = torch.empty(F, device=dev, dtype=torch.int32)
+    _C.call("cnr_mesh_orient_union", skeys, perm, f, F, words, err)
+    mark("union")
+    labels = torch.empty(F, device=dev, dtype=torch.int32)
+    flip0 = torch.empty(F, device=dev, dtype=torch.uint8)
+    ws = _C.workspace(_C.load().cnr_mesh_flatten_workspace_bytes(F), dev, "cnr_mesh_orient_flatten")
+    _C.call("cnr_mesh_orient_flatten", words, F, ws, labels, flip0, err)
+    mark("flatten")
+    roots = _roots(labels, None, F)
+    _raise_if_set(err, "orient")
+    C = len(roots)
+    face_patch = torch.empty(F, device=dev, dtype=torch.int32)
+    _C.call("cnr_mesh_assign", labels, None, F, roots, C, face_patch, err)
+    mark("roots_assign")
+    bad = torch.empty(C, device=dev, dtype=torch.int32)
+    counts = torch.empty(C, 2, device=dev, dtype=torch.int32)
+    _C.call("cnr_mesh_orient_check", skeys, perm, f, F, face_patch, C, flip0, bad, counts, err)
+    mark("check_links")
+    spatch, order = torch.sort(face_patch, stable=True)
+    mark("sort_faces")
+    n_faces = torch.empty(C, device=dev, dtype=torch.int32)
+    n_flipped = torch.empty(C, device=dev, dtype=torch.int32)
+    sign = torch.empty(C, device=dev, dtype=torch.uint8)
+    volume = torch.empty(C, device=dev, dtype=torch.float64) if verts is not None else None
+    ws = _C.workspace(_C.load().cnr_mesh_orient_stats_workspace_bytes(F), dev, "cnr_mesh_orient_stats")
+    _C.call("cnr_mesh_orient_stats", verts, f, order, spatch, face_patch, F, V, C, flip0, bad, 1 if outward else 0, ws, n_faces,
+            n_flipped, sign, volume)
+    mark("patch_stats")
+    out = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    flip = torch.empty(F, device=dev, dtype=torch.uint8)
+    _C.call("cnr_mesh_orient_apply", f, F, face_patch, C, flip0, sign, out, flip)
+    mark("apply")
+    _raise_if_set(err, "orient")
+    return MeshOrientation(n=C, faces=out, flip=flip, face_patch=face_patch, first=roots, n_faces=n_faces, orientable=bad == 0,
+                           closed=counts[:, 0] == 0, inconsistent_edges=counts[:, 1].contiguous(), n_flipped=n_flipped,
+                           signed_volume=volume)
+
+
+def orient_mesh(mesh, outward=True, device=None):
+    """``orient`` on a ``vis.Mesh`` -> (mesh, MeshOrientation): the same vertices and per-vertex attributes, the repaired faces."""
+    d = device_mesh(mesh, device, what="orient_mesh")
+    out = orient(d.faces, len(d.verts), verts=d.verts, outward=outward)
+    return mesh.subset(np.arange(len(d.verts), dtype=np.int64), out.faces.cpu().numpy().astype(np.int64).reshape(-1, 3)), out
+
+
 def compact(faces, n_vertices, keep_face, reindex=True):
     """The faces with keep_face (F,) set, in their old order, re-indexed to the vertices they use in their old order (the rule of
     raster.cull_mesh) -> (faces (F',3) i32, vertex_map (V,) i32 with -1 = dropped, kept_vertices (V',) i32 ascending); gather
@@ -290,7 +396,8 @@ def weld(verts, faces=None, cell=0.0, drop_degenerate=True):
     return kept, out, remap
 
 
-_weld = weld                        # (clean_mesh's option of the same name shadows the function)
+_weld = weld                        # (clean_mesh's options of the same names shadow the functions)
+_orient = orient
 
 
 def select_components(table, keep_largest=None, min_faces=0, min_area=0.0, min_diag=0.0, min_area_fraction=0.0, largest_by="area"):
@@ -330,9 +437,10 @@ def select_components(table, keep_largest=None, min_faces=0, min_area=0.0, min_d
 
 
 def clean_device(verts, faces, weld=None, connectivity="edge", keep_largest=None, min_faces=0, min_area=0.0, min_diag=0.0,
-                 min_area_fraction=0.0, largest_by="area"):
+                 min_area_fraction=0.0, largest_by="area", orient=False):
     """clean_mesh on device tensors: verts (V,3) f32, faces (F,3) i32 -> (faces (F',3) i32 re-indexed, kept_vertices (V',) i32
-    into the INPUT vertices, report).  weld: None (no welding), 0.0 (exact) or a cell size."""
+    into the INPUT vertices, report).  weld: None (no welding), 0.0 (exact) or a cell size.  orient=True runs
+    ``orient(..., outward=True)`` on what the component filter kept; report["orientation"] is its MeshOrientation."""
     V = len(verts)
     verts = verts.float().contiguous()
     f = check_faces(faces, V, "clean_mesh")
@@ -349,6 +457,9 @@ def clean_device(verts, faces, weld=None, connectivity="edge", keep_largest=None
     else:
         keep_face = torch.from_numpy(keep_c).to(f.device)[table.face_component.long()]
         out_f, _, kept = compact(f, len(verts), keep_face)
+    if orient:
+        report["orientation"] = _orient(out_f, len(kept), verts=verts.index_select(0, kept.long()), outward=True)
+        out_f = report["orientation"].faces
     if kept0 is not None:
         kept = kept0.index_select(0, kept.long())
     report.update(faces_out=int(len(out_f)), vertices_out=int(len(kept)))
@@ -356,16 +467,17 @@ def clean_device(verts, faces, weld=None, connectivity="edge", keep_largest=None
 
 
 def clean_mesh(mesh, weld=None, connectivity="edge", keep_largest=None, min_faces=0, min_area=0.0, min_diag=0.0,
-               min_area_fraction=0.0, largest_by="area", device=None):
+               min_area_fraction=0.0, largest_by="area", device=None, orient=False):
     """A ``vis.Mesh`` without its floaters -> (mesh, report).  Optionally weld first (None / 0.0 = exact / cell size), split into
     components by `connectivity`, keep those with n_faces >= min_faces, area >= min_area, bounding-box diagonal >= min_diag and
     area >= min_area_fraction x the total area, and of those the keep_largest largest by `largest_by`; ties go to the lower
     component id, and the result is never empty unless the input is.  Positions, normals and colours of the kept vertices are
     the input's (float64 positions stay float64: the device sees their fp32 roundings, the output gathers the originals).
-    report: dict(components=MeshComponents, kept=(n,) bool, n_components, n_kept, faces_in/out, vertices_in/out)."""
+    orient=True then repairs the orientation of what is left (``orient``, outward patches).
+    report: dict(components=MeshComponents, kept=(n,) bool, n_components, n_kept, faces_in/out, vertices_in/out[, orientation])."""
     d = device_mesh(mesh, device, what="clean_mesh")
     out_f, kept, report = clean_device(d.verts, d.faces, weld, connectivity, keep_largest, min_faces, min_area, min_diag,
-                                       min_area_fraction, largest_by)
+                                       min_area_fraction, largest_by, orient)
     return mesh.subset(kept.cpu().numpy().astype(np.int64), out_f.cpu().numpy().astype(np.int64).reshape(-1, 3)), report
 
 
@@ -383,10 +495,18 @@ def _parse_options(text, kinds, flag):
     return out
 
 
+def _flag(text):
+    if text.lower() in ("1", "true", "yes"):
+        return True
+    if text.lower() in ("0", "false", "no"):
+        return False
+    raise ValueError(f"cannot read {text!r} as a flag (1 / 0)")
+
+
 def parse_clean_options(text):
     """the tools' ``--clean`` string, e.g. "keep_largest=1,min_faces=20,weld=0" -> the dict of clean_mesh options"""
     return _parse_options(text, dict(weld=float, connectivity=str, keep_largest=int, min_faces=int, min_area=float, min_diag=float,
-                                     min_area_fraction=float, largest_by=str), "--clean")
+                                     min_area_fraction=float, largest_by=str, orient=_flag), "--clean")
 
 
 # ---- simplification: uniform vertex clustering with quadric placement (csrc/mesh_simplify.hip, DESIGN.md section 3.19) -------

@@ -272,7 +272,8 @@ def winding_number(points, mesh, check=True):
     `mesh` and `check` as for point_mesh_distance.  -> (n,) f64 device tensor: +1 inside a closed mesh whose right-hand normals
     point outward (-1 when they point inward, as vis.marching_cubes' do), 0 outside; on an open mesh it falls off smoothly across a hole, and
     is thresholded at 0.5.  A point in the plane of a face gets nothing from that face, so on the surface itself the value
-    is the mean of the two sides.  A mesh whose faces are not consistently oriented has no meaningful winding number."""
+    is the mean of the two sides.  A mesh whose faces are not consistently oriented has no meaningful winding number
+    (meshops.orient repairs one; inside, signed_distance and volume_iou take orientation="repair")."""
     q, tri = _winding_inputs(points, mesh, check, "winding_number")
     return _winding(q, tri)
 
@@ -297,12 +298,24 @@ def mesh_orientation(mesh):
     return _orientation_sign("auto", tri)
 
 
+def _repair(orientation, tri):
+    """orientation="repair": the mesh through meshops.orient(..., outward=True) (DESIGN.md §3.22), then treated as "outward";
+    any other orientation: as it is.  -> (orientation, DeviceMesh)"""
+    if orientation != "repair":
+        return orientation, tri
+    from . import meshops
+    if tri.faces is None:
+        raise ValueError('orientation="repair" needs an indexed mesh, not a triangle soup (weld it first)')
+    fixed = meshops.orient(tri.faces, len(tri.verts), verts=tri.verts, outward=True)
+    return "outward", DeviceMesh(tri.verts, fixed.faces, tri.colors, tri.normals)
+
+
 def _orientation_sign(orientation, tri):
     if orientation == "auto":
         return 1 if float(_signed_volume(tri.verts, tri.faces)) >= 0 else -1
     if orientation in ("outward", "inward"):
         return 1 if orientation == "outward" else -1
-    raise ValueError(f'orientation must be "auto", "outward" or "inward", not {orientation!r}')
+    raise ValueError(f'orientation must be "auto", "outward", "inward" or "repair", not {orientation!r}')
 
 
 def _inside(q, tri, threshold, orientation):
@@ -313,8 +326,10 @@ def _inside(q, tri, threshold, orientation):
 
 def inside(points, mesh, threshold=0.5, orientation="auto", check=True):
     """-> (n,) bool device tensor: s w > threshold with w = winding_number(points, mesh) and s = +1 for orientation="outward",
-    -1 for "inward", mesh_orientation(mesh) for "auto".  `mesh` and `check` as for point_mesh_distance."""
+    -1 for "inward", mesh_orientation(mesh) for "auto".  orientation="repair" first makes the faces consistent and every patch
+    outward (meshops.orient), then takes s = +1.  `mesh` and `check` as for point_mesh_distance."""
     q, tri = _winding_inputs(points, mesh, check, "inside")
+    orientation, tri = _repair(orientation, tri)
     return _inside(q, tri, threshold, orientation)
 
 
@@ -322,10 +337,11 @@ def signed_distance(points, mesh, threshold=0.5, orientation="auto", closest=Fal
     """point_mesh_distance with the distance negated where inside(points, mesh, threshold, orientation): negative is inside.
     -> (sdist (n,) f32, face (n,) i32[, closest (n,3) f32]); the magnitude, the face and the closest point are
     point_mesh_distance's bit for bit, with or without `index` (which is passed through; the winding number itself is always
-    taken over all faces of `mesh`, so `mesh` is read also when index is a MeshIndex)."""
+    taken over all faces of `mesh`, so `mesh` is read also when index is a MeshIndex).  orientation="repair" as for inside."""
     q, tri = _winding_inputs(points, mesh, check, "signed_distance")
     out = point_mesh_distance(q, tri, closest=closest, check=False, index=index)     # both were checked above
-    flag = _inside(q, tri, threshold, orientation)
+    orientation, wound = _repair(orientation, tri)     # flipping a face moves no surface point: the distance is of `mesh` as given
+    flag = _inside(q, wound, threshold, orientation)
     return (torch.where(flag, -out[0], out[0]),) + tuple(out[1:])
 
 
@@ -347,7 +363,8 @@ def volume_iou(mesh_a, mesh_b, N=100000, seed=0, box=None, points=None, threshol
     explicit points instead.  Each is classified by inside(., mesh, threshold, orientation[k]).
     -> dict(iou, intersection, union, inside_a, inside_b, n (exact integer counts; iou = nan when union == 0), volume_a, volume_b
     (the inside share times the box volume; nan with points=, which have no box), orientation_a, orientation_b (+1 / -1 as used)).
-    Open meshes are welcome (the winding number closes a hole smoothly); inconsistently oriented ones are not."""
+    Open meshes are welcome (the winding number closes a hole smoothly); inconsistently oriented ones are not, unless their
+    orientation is "repair": that mesh goes through meshops.orient(..., outward=True) first and is reported as +1."""
     dev = _device()
     a = device_mesh(mesh_a, dev, what="volume_iou")
     b = device_mesh(mesh_b, dev, what="volume_iou")
@@ -363,7 +380,8 @@ def volume_iou(mesh_a, mesh_b, N=100000, seed=0, box=None, points=None, threshol
             raise ValueError("volume_iou needs N >= 1 points")
         host, volume = _box_points(np.random.default_rng(seed).random((int(N), 3)), box, (a, b))
         q = torch.from_numpy(host).to(dev)
-    sa, sb = _orientation_sign(orientation[0], a), _orientation_sign(orientation[1], b)
+    (oa, a), (ob, b) = _repair(orientation[0], a), _repair(orientation[1], b)
+    sa, sb = _orientation_sign(oa, a), _orientation_sign(ob, b)
     ia = _inside(q, a, threshold, "outward" if sa > 0 else "inward")
     ib = _inside(q, b, threshold, "outward" if sb > 0 else "inward")
     n = len(q)

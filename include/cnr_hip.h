@@ -1420,6 +1420,43 @@ int cnr_weld_runs(const int* rows, const int64_t* sorted_keys, const int64_t* pe
 int cnr_mesh_remap_faces(const int* faces, int64_t F, const int* remap, int drop_degenerate, int* out_faces, uint8_t* keep,
                          void* stream);
 
+/* ---- orientation repair: consistent winding per patch, outward patches (csrc/mesh_topo.hip) ----
+ * faces, F, V, err as above; integer atomics only, no floating-point atomic, every loop bounded, bit-identical run to run.
+ * A face with two equal corners is degenerate: it has no edges, is a patch of its own and is never flipped.  A LINK is a run of
+ * exactly two equal keys in the sorted edge keys: its faces f < g and rel = 1 when both run the edge in the same direction.
+ * Patches are the connected components of the faces under links, numbered by their smallest face.
+ *
+ * orient_keys: cnr_mesh_edge_keys with all three keys of a degenerate face -1.  Sort them stably as for union_edges.
+ * orient_union: words (F,) i32, word = parent << 1 | parity (F < 2^30); sets words[i] = i << 1, then joins the two faces of
+ * every link with the parity its rel demands (csrc/mesh_topo_common.h: find_parity, unite_parity).
+ * orient_flatten: pointer-jumping sweeps with the parities XOR-ed along (workspace >= cnr_mesh_flatten_workspace_bytes(F)),
+ * then labels[i] = the smallest face of i's patch (for cnr_mesh_roots_* / cnr_mesh_assign) and flip0 (F,) u8 = i's parity
+ * relative to it.
+ * orient_check: face_patch (F,) i32 from cnr_mesh_assign, C patches.  bad (C,) i32 = 1 where a link has
+ * flip0[f] ^ flip0[g] != rel (the patch is not orientable); counts (C,2) i32 = the edge slots of the patch that lie in no run
+ * of two (0: the patch is closed), and its links with rel == 1 in the input; both zeroed here.  Then flip0 = 0 on every face
+ * of a bad patch.
+ * orient_stats: order (F,) i64 = the faces stably sorted by patch, sorted_patch (F,) i32; n_faces, n_flipped (C,) i32,
+ * sign (C,) u8; workspace >= cnr_mesh_orient_stats_workspace_bytes(F).  With verts (V,3) f32 != NULL, per patch: its fp32
+ * vertex box (exact minima and maxima, taken by integer atomics on an order-preserving image of the floats), c = 0.5 * (min +
+ * max) in fp64, s = sum over its faces (flip0 applied) of (a - c) . ((b - c) x (d - c)) in fp64, one wave per patch in the fixed
+ * order written out in csrc/mesh_topo.hip; sign = outward != 0 and the patch is orientable and s < 0; signed_volume (C,) f64 =
+ * (sign ? -s : s) / 6.  Without verts sign = 0 and signed_volume may be NULL.  n_flipped counts flip0 ^ sign.
+ * orient_apply: flip (F,) u8 = flip0 ^ sign[face_patch]; out_faces = (a, d, b) where flip is set, (a, b, d) elsewhere. */
+int cnr_mesh_orient_keys(const int* faces, int64_t F, int64_t* keys, void* stream);
+int cnr_mesh_orient_union(const int64_t* sorted_keys, const int64_t* perm, const int* faces, int64_t F, int* words, int* err,
+                          void* stream);
+int cnr_mesh_orient_flatten(int* words, int64_t F, void* workspace, int* labels, uint8_t* flip0, int* err, void* stream);
+int cnr_mesh_orient_check(const int64_t* sorted_keys, const int64_t* perm, const int* faces, int64_t F, const int* face_patch,
+                          int64_t C, uint8_t* flip0, int* bad, int* counts, int* err, void* stream);
+int64_t cnr_mesh_orient_stats_workspace_bytes(int64_t F);
+int cnr_mesh_orient_stats(const float* verts, const int* faces, const int64_t* order, const int* sorted_patch,
+                          const int* face_patch, int64_t F, int64_t V, int64_t C, const uint8_t* flip0, const int* bad,
+                          int outward, void* workspace, int* n_faces, int* n_flipped, uint8_t* sign, double* signed_volume,
+                          void* stream);
+int cnr_mesh_orient_apply(const int* faces, int64_t F, const int* face_patch, int64_t C, const uint8_t* flip0,
+                          const uint8_t* sign, int* out_faces, uint8_t* flip, void* stream);
+
 /* ---- mesh simplification: uniform vertex clustering with quadric placement (csrc/mesh_simplify.hip) ----
  * The clusters are the cells of cnr_voxel_keys, numbered by cnr_weld_runs / cnr_mesh_roots_* / cnr_mesh_assign; the faces go
  * through cnr_mesh_remap_faces and cnr_mesh_compact_*.  These entry points add the fp64 part and the face rows.  No

@@ -2,8 +2,10 @@
 
     python tools/clean_mesh.py in.{obj,ply} out.obj [--weld CELL] [--connectivity edge|vertex] [--keep_largest K]
                                [--min_faces N] [--min_area A] [--min_diag D] [--min_area_fraction Q] [--largest_by area|faces|diag]
+                               [--orient]
 
---weld 0 welds bit-equal vertices first, --weld CELL those that round to the same point of a grid of that pitch.  A component is
+--orient then makes the winding of what is kept consistent and every patch outward (cnr_amd.meshops.orient) and
+prints the patch table.  --weld 0 welds bit-equal vertices first, --weld CELL those that round to the same point of a grid of that pitch.  A component is
 kept when it passes every threshold (>=) and, with --keep_largest K, is among the K largest of those; ties go to the lower
 component id, and the output is never empty unless the input is.  A file written by Mesh.export keeps its colours and normals;
 any other .obj / .ply is read for its geometry."""
@@ -43,18 +45,25 @@ def main(argv=None):
     ap.add_argument("--min_diag", type=float, default=0.0)
     ap.add_argument("--min_area_fraction", type=float, default=0.0)
     ap.add_argument("--largest_by", default="area", choices=("area", "faces", "diag"))
+    ap.add_argument("--orient", action="store_true", help="repair the orientation of what is kept: consistent winding per patch, "
+                                                          "patches outward (meshops.orient); prints the patch table")
     a = ap.parse_args(argv)
     import cnr_amd as cnr
     mesh = load(cnr, a.src)
     out, report = cnr.meshops.clean_mesh(mesh, weld=a.weld, connectivity=a.connectivity, keep_largest=a.keep_largest,
                                          min_faces=a.min_faces, min_area=a.min_area, min_diag=a.min_diag,
-                                         min_area_fraction=a.min_area_fraction, largest_by=a.largest_by)
+                                         min_area_fraction=a.min_area_fraction, largest_by=a.largest_by, orient=a.orient)
     table = report["components"]
     print(table.table())
     print("components: %d  kept: %d (%s)" % (report["n_components"], report["n_kept"],
                                              " ".join(str(c) for c in report["kept"].nonzero()[0])))
     print("boundary edges: %d  non-manifold edges: %d" % (table.boundary_edges, table.nonmanifold_edges))
     print("faces %d -> %d, vertices %d -> %d" % (report["faces_in"], report["faces_out"], report["vertices_in"], report["vertices_out"]))
+    if a.orient:
+        patches = report["orientation"]
+        print(patches.table())
+        print("patches: %d  not orientable: %d  faces flipped: %d" % (patches.n, int((~patches.orientable).sum()),
+                                                                      int(patches.n_flipped.sum())))
     out.export(a.dst)
 
 

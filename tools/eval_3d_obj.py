@@ -1,7 +1,7 @@
 """3-D metrics of the reconstructed meshes (metric/eval_3D_obj.py's command line and output files), on cnr_amd.metrics:
 
     python tools/eval_3d_obj.py --data_dir Datasets/Replica --log_dir logs/Replica [--log_dir_ref DIR] [--iteration 10000]
-                                [--clean keep_largest=1,...] [--surface [--index]] [--volume [N]]
+                                [--clean keep_largest=1,...] [--surface [--index]] [--volume [N] [--repair]]
 
 For every scene of the dataset (the last component of --data_dir: Replica or ScanNet) whose <log_dir>/<scene>/scene_mesh exists,
 every object mesh iteration_<it>_obj<id>.obj written by train.py is scored against its ground-truth mesh in
@@ -19,7 +19,9 @@ against the other MESH (accuracy, completion, completion ratio), precision / rec
 consistency; written to <log_dir>/<scene>/eval_mesh/metrics_3D_obj_surface.json.
 --volume [N] (default off; N = 100 000 points when not given) adds cnr_amd.metrics.volume_iou of the reconstruction and the
 ground truth per object and in the mean, counted in mesh_ref's oriented box, the one accuracy is clipped to (so what the
-reconstruction has outside that box counts for nothing); each mesh's orientation is found by mesh_orientation.  Written to
+reconstruction has outside that box counts for nothing); each mesh's orientation is found by mesh_orientation, or with
+--repair each mesh's bit-equal vertices are welded and it goes through cnr_amd.meshops.orient (consistent winding per patch,
+patches outward; volume_iou's orientation "repair").  Written to
 <log_dir>/<scene>/eval_mesh/metrics_3D_obj_volume.json.  An object with no point inside either mesh has no IoU: it is printed
 as "none", written as null and left out of the mean (objects_in_mean counts the rest).  The background (id 0), a room seen
 from inside, has no volume to compare; it is never listed (see above), so it gets no IoU either."""
@@ -109,7 +111,10 @@ def main(argv=None):
     ap.add_argument("--surface", action="store_true", help="also score against the meshes themselves: point-to-mesh distances, F-score, normal consistency (default: off)")
     ap.add_argument("--index", action="store_true", help="with --surface: take the point-to-mesh distances through a tile-box index of each mesh; the same numbers, faster on large meshes (default: off)")
     ap.add_argument("--volume", nargs="?", type=int, const=100000, default=None, metavar="N", help="also the volumetric IoU of reconstruction and ground truth from N points (100000 when N is not given) in the crop box, by winding numbers (default: off)")
+    ap.add_argument("--repair", action="store_true", help="with --volume: repair both meshes' orientation first (consistent winding per patch, patches outward) instead of trusting it (default: off)")
     args = ap.parse_args(argv)
+    if args.repair and args.volume is None:
+        ap.error("--repair goes with --volume")
     from cnr_amd.meshops import clean_mesh, parse_clean_options
     from cnr_amd.metrics import calc_3d_metric, calc_3d_metric_surface, oriented_bounds, volume_iou
     clean = parse_clean_options(args.clean) if args.clean else None
@@ -164,7 +169,10 @@ def main(argv=None):
                     surface[obj_id] = row
                     print("surface obj %d: " % obj_id + "  ".join("%s %.4f" % (k, row[k]) for k in SURFACE_COLUMNS))
             if args.volume is not None:
-                volume[obj_id] = row = volume_iou(mesh_rec, mesh_gt, N=args.volume, box=oriented_bounds(mesh_ref))
+                pair, orientation = (mesh_rec, mesh_gt), ("auto", "auto")
+                if args.repair:                 # a file holds a vertex once per polygon side: weld, or every side is a patch
+                    pair, orientation = [clean_mesh(m, weld=0.0)[0] for m in pair], ("repair", "repair")
+                volume[obj_id] = row = volume_iou(*pair, N=args.volume, box=oriented_bounds(mesh_ref), orientation=orientation)
                 if row["union"] == 0:           # no point inside either mesh: no IoU (None: JSON has no nan), not in the mean
                     row["iou"] = None
                 print("volume obj %d: " % obj_id + "  ".join("%s %s" % (k, _fmt(row[k])) for k in VOLUME_COLUMNS))
